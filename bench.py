@@ -14,13 +14,19 @@ scaling) and the survivors of all ranks are exchanged every step exactly as the 
 a launcher; under `python -m torch.distributed.run ... bench.py --gpus N` it uses the ranks it is given.
 
 Prints ONE JSON line (rank 0).  Objects beside the contract fields:
-  "roofline"      MFMA roofline of the forward (algorithmic FLOPs / HIP-event time) against the peak of the arithmetic the line ran in
-  "also"          the other BASELINE configs timed the same way in the headline's arithmetic: "dual_scale" (configs[2]) and "ch4"
-                  (configs[3], per GPU); and "f16": the opt-in 16-bit fast mode (fp16 storage, fp32 accumulate) on the same three
-                  workloads, each with its own roofline against the 2.5 PFLOP/s fp16 MFMA peak
+  "roofline"      MFMA roofline of the forward (algorithmic FLOPs / HIP-event time of the timed steps) against the peak of the
+                  arithmetic the line ran in
 The headline runs in fp32 arithmetic (obb_set_option precision 32: exact-f32 MFMA, peak 157.3 TFLOP/s) because that is what the
 reference computes (Detect_OBB.py:79-83, half=False); --precision f16 / bf16 makes the 16-bit mode the headline instead.
-  "cpu_baseline"  the CPU restatement of the same path (bounded sample; baseline only)
+A plain run measures the headline only.  --full adds the measurements that take runs of their own:
+  "also"          the other BASELINE configs timed the same way in the headline's arithmetic: "dual_scale" (configs[2]) and "ch4"
+                  (configs[3], per GPU); and "f16": the opt-in 16-bit fast mode (fp16 storage, fp32 accumulate) on the same three
+                  workloads, each with its own roofline against the 2.5 PFLOP/s fp16 MFMA peak  (--no-extras leaves them out)
+  "cpu_baseline"  the CPU restatement of the same path (bounded sample; baseline only)  (--no-cpu-baseline leaves it out)
+
+--dump-outputs DIR writes what the headline's last timed step returned -- the final detections after the whole-batch merge, in merge
+order -- as DIR/final_{boxes,cls,conf,angle}.npy (float64).  Inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -47,9 +53,11 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=int(os.environ.get("OBB_BENCH_BATCH", 1024)), help="tiles per GPU per step (SURVEY 8(d): B in {1, 16, 64, 256, 1024})")
     ap.add_argument("--no-pipeline", dest="pipeline", action="store_false", help="run the steps strictly one after the other (no forward / post-processing overlap)")
-    ap.add_argument("--precision", default="f32", choices=["f16", "bf16", "f32"], help="arithmetic of the HEADLINE line (default fp32 = the reference's; the f16 figures are reported under also.f16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the dual-scale / 4-channel / f16 measurements beside the headline")
+    ap.add_argument("--precision", default="f32", choices=["f16", "bf16", "f32"], help="arithmetic of the HEADLINE line (default fp32 = the reference's; with --full the f16 figures are reported under also.f16)")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beside the headline (other configs, the f16 mode, the CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the dual-scale / 4-channel / f16 measurements beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the final detections of the headline's last timed step as DIR/*.npy")
     ap.add_argument("--channels", type=int, default=3, choices=[3, 4], help="4 = BASELINE configs[3] as the headline: every step also builds the RGB + DT-edge "
                     "input of a 4-channel checkpoint from the BGR tiles (build_multich) before the forward")
     return ap.parse_args()
@@ -89,6 +97,25 @@ def cpu_baseline(budget_s=15.0):
     dt = time.time() - t0
     return {"value": n / dt, "unit": "tiles/s", "cores": torch.get_num_threads(), "host_logical_cpus": os.cpu_count(), "kind": "port",
             "sample": f"{n} synthetic 416x416x3 tiles, one model call per tile (reference loop), torch-CPU fp32 + C geometry, {dt:.1f} s"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(merged, out_dir):
+    """The final detections of one step (a DetSet, merge order) -> out_dir/final_{boxes,cls,conf,angle}.npy, float64.  Above
+    DUMP_MAX_BYTES a fixed seeded sample of rows is written (row order kept)."""
+    import numpy as np
+    cols = {"boxes": merged.boxes, "cls": merged.cls, "conf": merged.conf, "angle": merged.angle}
+    cols = {k: v.cpu().numpy().astype(np.float64) for k, v in cols.items()}
+    n = len(cols["cls"])
+    row_bytes = sum(v[:1].nbytes for v in cols.values()) or 1
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        cols = {k: v[rows] for k, v in cols.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in cols.items():
+        np.save(os.path.join(out_dir, f"final_{k}.npy"), v)
 
 
 def spawn_ranks(n):
@@ -278,7 +305,8 @@ def main():
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
         nmerged = len(merged)  # the final count is read once, outside the timed region
-        return {"dt": dt, "nrec": nrec, "nmerged": nmerged, "fwd_ms": [float(np.mean([a.elapsed_time(b) for a, b in sc.ev])) for sc in scales]}
+        return {"dt": dt, "nrec": nrec, "nmerged": nmerged, "merged": merged,
+                "fwd_ms": [float(np.mean([a.elapsed_time(b) for a, b in sc.ev])) for sc in scales]}
 
     def roofline(precision, flop_per_step, fwd_ms):
         ach = flop_per_step / (fwd_ms * 1e-3) / 1e12
@@ -358,6 +386,10 @@ def main():
 
     # ------------------------------------------------------------------ headline: configs[1] (or configs[3] with --channels 4)
     h, rf = run_single(args.precision, args.channels, args.steps, args.warmup)
+    merged = h.pop("merged")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(merged, args.dump_outputs)
+    del merged
     out = None
     if rank == 0:
         out = {
@@ -376,7 +408,7 @@ def main():
             "roofline": rf,
         }
 
-    extras = not args.no_extras and world == 1
+    extras = args.full and not args.no_extras and world == 1
     if extras:
         stepsd = max(3, args.steps // 2)
         also = {"dual_scale": run_dual(args.precision, stepsd)}
@@ -397,7 +429,7 @@ def main():
             out["also"] = also
 
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and args.channels == 3:
+        if args.full and not args.no_cpu_baseline and world == 1 and args.channels == 3:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

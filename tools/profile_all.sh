@@ -6,7 +6,7 @@ O=${OUT:-gpurun_out/final}; mkdir -p $O
 LP="python3 tools/layer_profile.py"
 # parts (a gpurun call is capped at 1200 s): a = benches + kernel traces, b = f32 counters, c = f16 counters + post-processing
 if [ "${PART:-a}" = a ]; then
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f32 -- python3 bench.py --no-cpu-baseline --no-extras --no-pipeline --steps 8 > $O/bench_prof_f32.log 2>&1
 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f16 -- python3 bench.py --no-cpu-baseline --no-extras --no-pipeline --precision f16 > $O/bench_prof_f16.log 2>&1
 python3 bench.py --no-cpu-baseline --no-extras --no-pipeline > $O/bench_nopipe.json
@@ -17,7 +17,7 @@ OBB_SIZE=128 OBB_PREC=f32 OBB_GRAPH=0 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace -
 OBB_SIZE=128 OBB_GRAPH=0 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --output-format csv -d $O/layers_128 -- $LP 8192 $O/layers_128 > $O/layers_128.log 2>&1 && $LP report $O/layers_128 > $O/layers_128.txt
 fi
 if [ "${PART:-a}" = a32 ]; then  # the fp32 subset of part a (after a change of the fp32 kernels only)
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_f32 -- python3 bench.py --no-cpu-baseline --no-extras --no-pipeline --steps 8 > $O/bench_prof_f32.log 2>&1
 OBB_PREC=f32 OBB_GRAPH=0 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --output-format csv -d $O/layers32 -- $LP 256 $O/layers32 > $O/layers32.log 2>&1 && $LP report $O/layers32 > $O/layers32.txt
 OBB_PREC=f32 OBB_GRAPH=0 OBB_FWD_SPLIT=1 rocprofv3 --kernel-trace --output-format csv -d $O/layers32_512 -- $LP 512 $O/layers32_512 > $O/layers32_512.log 2>&1 && $LP report $O/layers32_512 > $O/layers32_512.txt
