@@ -202,6 +202,32 @@ int obb_conv_fwd_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w,
 int obb_silu_bf16(obb_ctx *ctx, const uint16_t *z, uint16_t *a, int64_t n, obb_stream_t s);
 int obb_silu_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, uint16_t *dz, int64_t n, obb_stream_t s);
 int obb_bias_grad_bf16(obb_ctx *ctx, const uint16_t *dy, int64_t npix, int32_t cout, float *db, obb_stream_t s);
+/* Stride-2 3x3 convolution (pad 1; input H x W, output Ho = (H + 1) / 2 x Wo = (W + 1) / 2): the downsampling Convs of the backbone and the
+ * PAN (yolo11 models 3 / 5 / 7 / 17 / 20) in `model.train(...)` (Train_OBB.py:796-841), bf16 NHWC tensors, fp32 accumulation.
+ * obb_conv_s2_pack_bf16: fp32 OIHW master weights (device) -> the forward kernel's bf16 fragment order for an H x W input (n_elems from
+ *   obb_conv_s2_packed_elems).   obb_conv_fwd_s2_bf16: y[B][Ho][Wo][cout] = conv_s2(x[B][H][W][cin]) + bias (NULL: none), no activation.
+ * obb_conv_dgrad_s2_bf16: dx[B][H][W][cin] = sum_k dY_up[m + 1 - k] W[k] with dY_up = dy[B][Ho][Wo][cout] zero-inserted (dY_up[2i] = dy[i]):
+ *   the stride-1 forward on obb_conv_pack_bf16(w, cout, cin, 3, H, W, dgrad_form = 1) weights (4x the useful MACs).
+ * obb_conv_wgrad_s2_bf16: dw[cout][cin][3][3] fp32 = sum_{b,i,j} dy[b,i,j,co] x[b, 2i + ky - 1, 2j + kx - 1, ci]; cin and cout multiples of 64
+ *   (models 0 and 1, 3 -> 32 -> 64, are rejected); deterministic. */
+int obb_conv_s2_packed_elems(obb_ctx *ctx, int32_t cout, int32_t cin, int32_t H, int32_t W, int64_t *n_elems);
+int obb_conv_s2_pack_bf16(obb_ctx *ctx, const float *w_oihw, int32_t cout, int32_t cin, int32_t H, int32_t W, uint16_t *packed, obb_stream_t s);
+int obb_conv_fwd_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w, const float *bias, int32_t B, int32_t H, int32_t W, int32_t cin,
+                         int32_t cout, uint16_t *y, obb_stream_t s);
+int obb_conv_dgrad_s2_bf16(obb_ctx *ctx, const uint16_t *dy, const uint16_t *packed_dgrad, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                           uint16_t *dx, obb_stream_t s);
+int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, float *dw,
+                           obb_stream_t s);
+/* Training-mode BatchNorm2d + SiLU of the Ultralytics Conv block (Conv2d(bias=False) -> BatchNorm2d -> SiLU, `model.train(...)`), z / a / da / dz
+ * bf16 [npix][C] (NHWC rows), C % 8 == 0, npix >= 2; per-channel vectors fp32 [C], all on the device.
+ * obb_bn_silu_fwd_bf16: mean, invstd = 1 / sqrt(var + eps) of the batch (biased var); running_mean / running_var updated in place,
+ *   r = (1 - momentum) r + momentum * batch (running var: the unbiased var N / (N - 1)); a = silu(gamma (z - mean) invstd + beta).
+ * obb_bn_silu_bwd_bf16: xhat and y = gamma xhat + beta recomputed from z, g = da silu'(y): dbeta = sum g, dgamma = sum g xhat,
+ *   dz = gamma invstd (g - dbeta / N - xhat dgamma / N).  Reductions: per-block fp32 partials combined in a fixed order (deterministic). */
+int obb_bn_silu_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps, float momentum,
+                         float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, obb_stream_t s);
+int obb_bn_silu_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
+                         const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S1: model(...) -> results[0].obb  (Detect_OBB.py:26,81-83,228-231) */
 /* Weight blob ("OBBW" format, produced by the Python side from BN-folded conv weights) for a

@@ -47,6 +47,13 @@ SIGNATURES = {
     "obb_silu_bf16": [_V, _V, _V, C.c_int64, _V],
     "obb_silu_bwd_bf16": [_V, _V, _V, _V, C.c_int64, _V],
     "obb_bias_grad_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V],
+    "obb_conv_s2_packed_elems": [_V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "obb_conv_s2_pack_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_conv_fwd_s2_bf16": [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_conv_dgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_conv_wgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_bn_silu_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, _V],
+    "obb_bn_silu_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V],
     "obb_gather_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V, _V],
     "obb_letterbox": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V,
                       C.c_int32, C.c_int32, _V],

@@ -12,6 +12,13 @@
 //          accumulation in registers over all the tiles a persistent workgroup walks, one fp32 slab per workgroup, summed by a second
 //          kernel in a fixed order (deterministic; no float atomics).  The 16x-faster bf16 form (v_mfma_f32_16x16x32_bf16 fed by
 //          ds_read_b64_tr_b16 transposed LDS reads) is the next step: it needs the same tiles and the same walk.
+//
+// Stride 2 (3x3, pad 1, Hout = (H + 1) / 2: the downsampling convs of the backbone and the PAN, models 3 / 5 / 7 / 17 / 20 of yolo11s):
+//   forward  the same conv kernel with stride 2, pair = false (obb_conv_fwd_s2_bf16 on obb_conv_s2_pack_bf16 weights).
+//   dgrad    dX[m] = sum_k dY_up[m + 1 - k] W[k] with dY_up[2i] = dY[i] and zeros at odd positions: the stride-1 `same` forward of the
+//            zero-inserted dY on the dgrad-form weights.  dY_up only needs the H x W extent (positions H and -1 are zeros / padding either
+//            way), so the conv writes dX directly, no crop.  It spends 4x the useful MACs (three taps of four see an inserted zero).
+//   wgrad    k_conv_wgrad<3, 2>: R output rows stage 2R + 1 input rows of width 2 Wp + 1 (one 208-pixel row of model.3 at 416 px: R = 1).
 #include <algorithm>
 #include <vector>
 
@@ -27,17 +34,18 @@ __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_a
 // Workgroup = 4 waves = one (64-cout block, 64-cin block) pair of dW for all KS*KS taps; wave w owns the cin fragment w (16 channels)
 // and all four cout fragments: acc[4][TAPS] tiles of 16 x 16.  A tile of the input = R rows x W pixels of one image: dY rows padded
 // with zeros to a multiple of 4 pixels (the k step), X rows with the zero halo of the convolution's padding.
-template <int KS>
-__global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int cin, int cout,
-                                                   int R, float *__restrict__ slabs) {
+// S = 2: X is H x W, dY is Ho x Wo; R dY rows need (R - 1) S + KS X rows of (Wp - 1) S + KS pixels.
+template <int KS, int S = 1>
+__global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int Ho, int Wo,
+                                                   int cin, int cout, int R, float *__restrict__ slabs) {
     extern __shared__ __attribute__((aligned(16))) unsigned short swg[];
     constexpr int TAPS = KS * KS, PAD = KS / 2;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, r16 = lane & 15;
     const int cob = blockIdx.y, cib = blockIdx.z;
-    const int Wp = (W + 3) & ~3, Wx = Wp + 2 * PAD;  // padded widths of the dY / X tiles
-    unsigned short *sx = swg, *sdy = swg + (size_t)(R + 2 * PAD) * Wx * 64;
-    const int tiles_y = (H + R - 1) / R, ntiles = B * tiles_y;
+    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * S + KS, Rx = (R - 1) * S + KS;  // padded widths of the dY / X tiles, X rows
+    unsigned short *sx = swg, *sdy = swg + (size_t)Rx * Wx * 64;
+    const int tiles_y = (Ho + R - 1) / R, ntiles = B * tiles_y;
     f32x4g acc[4][TAPS];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
@@ -46,10 +54,10 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__rest
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int b = tile / tiles_y, y0 = (tile % tiles_y) * R;
         __syncthreads();
-        // stage X rows y0 - PAD .. y0 + R - 1 + PAD, pixels -PAD .. Wp - 1 + PAD, 64 channels of block cib (16-byte chunks, zeros outside)
-        for (int i = tid; i < (R + 2 * PAD) * Wx * 8; i += 256) {
+        // stage X rows y0 S - PAD .. (y0 + R - 1) S + PAD, pixels -PAD .. (Wp - 1) S + PAD, 64 channels of block cib (16-byte chunks, zeros outside)
+        for (int i = tid; i < Rx * Wx * 8; i += 256) {
             const int c8 = i & 7, px = (i >> 3) % Wx, ry = (i >> 3) / Wx;
-            const int yy = y0 + ry - PAD, xx = px - PAD;
+            const int yy = y0 * S + ry - PAD, xx = px - PAD;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
             if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = *reinterpret_cast<const uint4 *>(x + (((int64_t)b * H + yy) * W + xx) * cin + cib * 64 + c8 * 8);
             *reinterpret_cast<uint4 *>(sx + ((size_t)ry * Wx + px) * 64 + c8 * 8) = v;
@@ -58,7 +66,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__rest
             const int c8 = i & 7, px = (i >> 3) % Wp, ry = (i >> 3) / Wp;
             const int yy = y0 + ry;
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (yy < H && px < W) v = *reinterpret_cast<const uint4 *>(dy + (((int64_t)b * H + yy) * W + px) * cout + cob * 64 + c8 * 8);
+            if (yy < Ho && px < Wo) v = *reinterpret_cast<const uint4 *>(dy + (((int64_t)b * Ho + yy) * Wo + px) * cout + cob * 64 + c8 * 8);
             *reinterpret_cast<uint4 *>(sdy + ((size_t)ry * Wp + px) * 64 + c8 * 8) = v;
         }
         __syncthreads();
@@ -70,7 +78,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__rest
 #pragma unroll
                 for (int t = 0; t < TAPS; ++t) {
                     const int ky = t / KS, kx = t % KS;
-                    const float bv = bf16_to_f32(sx[((size_t)(ry + ky) * Wx + x0 + g + kx) * 64 + wave * 16 + r16]);
+                    const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + (x0 + g) * S + kx) * 64 + wave * 16 + r16]);
 #pragma unroll
                     for (int c = 0; c < 4; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
                 }
@@ -162,6 +170,102 @@ __global__ __launch_bounds__(256) void k_bias_grad_bf16(const unsigned short *__
     if (rowg == 0 && c < cout) db[c] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
+// dY bf16 [B][Ho][Wo][C] -> dY_up [B][H][W][C]: dY[i][j] at (2i, 2j), zeros elsewhere; one 16-byte chunk per thread and step
+__global__ __launch_bounds__(256) void k_zero_insert_s2(const unsigned short *__restrict__ dy, int H, int W, int Ho, int Wo, int C8, int64_t nchunk,
+                                                        unsigned short *__restrict__ up) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * 256) {
+        const int c8 = (int)(i % C8);
+        const int64_t pix = i / C8;
+        const int xx = (int)(pix % W), yy = (int)((pix / W) % H);
+        const int64_t b = pix / ((int64_t)W * H);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u);
+        if (((xx | yy) & 1) == 0) v = reinterpret_cast<const uint4 *>(dy)[((b * Ho + yy / 2) * Wo + xx / 2) * C8 + c8];
+        reinterpret_cast<uint4 *>(up)[i] = v;
+    }
+}
+
+namespace {
+
+// the layer shapes of the training entry points: (stride 1) H x W -> H x W, (stride 2, 3x3) H x W -> (H + 1) / 2 x (W + 1) / 2
+int out_dim(int n, int stride) { return stride == 2 ? (n + 1) / 2 : n; }
+
+int wgrad_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *dy, int B, int H, int W, int cin, int cout, int ks, int stride, float *dw,
+                 hipStream_t st) {
+    const int taps = ks * ks, Ho = out_dim(H, stride), Wo = out_dim(W, stride);
+    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * stride + ks;
+    auto lds_of = [&](int R) { return ((size_t)((R - 1) * stride + ks) * Wx + (size_t)R * Wp) * 128; };
+    int R = 1;  // rows per tile: as many as 64 KiB of LDS hold
+    while (R < Ho && lds_of(R + 1) <= 64 * 1024) ++R;
+    const size_t lds = lds_of(R);
+    OBB_REQUIRE(ctx, lds <= 64 * 1024, "%s: a row of %d pixels does not fit the LDS tile", fn, W);
+    const int ncob = cout / 64, ncib = cin / 64;
+    OBB_REQUIRE(ctx, ncob >= 1 && ncib >= 1, "%s: cin = %d, cout = %d: at least 64 channels each", fn, cin, cout);  // (0 % 64 == 0: no division by zero below)
+    const int ntiles = B * ((Ho + R - 1) / R);
+    int nwalk = std::max(1, std::min(ntiles, 512 / (ncob * ncib)));
+    const size_t per = (size_t)ncob * ncib * taps * 4096;
+    float *slabs = (float *)ctx->workspace(WS_TRAIN_C, (size_t)nwalk * per * 4);
+    if (!slabs) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
+    const dim3 grid((unsigned)nwalk, (unsigned)ncob, (unsigned)ncib);
+    if (stride == 2) hipLaunchKernelGGL((k_conv_wgrad<3, 2>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
+    else if (ks == 3) hipLaunchKernelGGL((k_conv_wgrad<3>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
+    else hipLaunchKernelGGL((k_conv_wgrad<1>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, ncob, ncib, taps, cin, cout, dw);
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
+}
+
+// packed size / device packing of the forward-kernel weights of a layer whose INPUT is H x W
+int packed_elems(obb_ctx *ctx, const char *fn, int cout, int cin, int ks, int stride, int H, int W, int dgrad_form, int64_t *n_elems) {
+    OBB_REQUIRE(ctx, ctx && n_elems && cout > 0 && cin > 0 && (ks == 1 || ks == 3) && H > 0 && W > 0, "%s: bad arguments", fn);
+    const int coutL = dgrad_form ? cin : cout, cinL = dgrad_form ? cout : cin;
+    const ConvTiling t = plan_conv(ks, stride, cinL, coutL, out_dim(H, stride), out_dim(W, stride), false);
+    const int nstage = (cinL + t.CK - 1) / t.CK, ncb = (coutL + 16 * t.NF - 1) / (16 * t.NF);
+    *n_elems = (int64_t)ncb * nstage * conv_ksteps(ks, t.CK) * t.NF * 64 * 8;
+    return OBB_OK;
+}
+
+int pack_launch(obb_ctx *ctx, const char *fn, const float *w_oihw, int cout, int cin, int ks, int stride, int H, int W, int dgrad_form, uint16_t *packed, hipStream_t st) {
+    OBB_REQUIRE(ctx, ctx && w_oihw && packed, "%s: NULL buffer", fn);
+    int64_t n = 0;
+    int rc = packed_elems(ctx, fn, cout, cin, ks, stride, H, W, dgrad_form, &n);
+    if (rc) return rc;
+    const int coutL = dgrad_form ? cin : cout, cinL = dgrad_form ? cout : cin;
+    const ConvTiling t = plan_conv(ks, stride, cinL, coutL, out_dim(H, stride), out_dim(W, stride), false);
+    hipLaunchKernelGGL(k_pack_conv_bf16, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, w_oihw, coutL, cinL, ks, t.CK, t.NF, dgrad_form ? 1 : 0, packed, n);
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
+}
+
+// y = conv(x) + bias, no activation, input H x W, output out_dim(H, stride) x out_dim(W, stride)
+int fwd_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *packed_w, const float *bias, int B, int H, int W, int cin, int cout, int ks, int stride,
+               uint16_t *y, hipStream_t st) {
+    const int Ho = out_dim(H, stride), Wo = out_dim(W, stride);
+    const ConvTiling t = plan_conv(ks, stride, cin, cout, Ho, Wo, false);
+    // [bias padded to the kernel's 64-float granule (zeros without one)][2 KiB: the `lut` argument = the sink of the kernel's unconditional stores]
+    const size_t bbytes = (((size_t)cout + 63) / 64 * 64 * 4 + 256 + 255) & ~(size_t)255;
+    char *ws = (char *)ctx->workspace(WS_TRAIN_A, bbytes + 2048);
+    if (!ws) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
+    OBB_HIP(ctx, hipMemsetAsync(ws, 0, bbytes, st));
+    if (bias) OBB_HIP(ctx, hipMemcpyAsync(ws, bias, (size_t)cout * 4, hipMemcpyDeviceToDevice, st));
+    ConvLaunch L;
+    L.in.p = (void *)x; L.in.bs = (int64_t)H * W * cin; L.in.cs = cin; L.in.co = 0;
+    L.out.p = (void *)y; L.out.bs = (int64_t)Ho * Wo * cout; L.out.cs = cout; L.out.co = 0;
+    L.wpk = (const bf16_t *)packed_w; L.bias = (const float *)ws; L.lut = (const bf16_t *)(ws + bbytes);
+    L.B = B; L.Hin = H; L.Hout = Ho; L.Win = W; L.Wout = Wo; L.cin = cin; L.cout = cout; L.ks = ks; L.stride = stride; L.act = 0; L.f16 = 0;
+    L.TH = t.TH; L.TW = t.TW; L.MF = t.MF; L.NF = t.NF; L.CK = t.CK;
+    L.tiles_y = (Ho + t.TH - 1) / t.TH; L.tiles_x = (Wo + t.TW - 1) / t.TW;
+    if (ks == 1) {
+        const int64_t npx = (int64_t)B * H * W;
+        OBB_REQUIRE(ctx, npx < (1ll << 31) / 4, "%s: too many pixels for one launch", fn);
+        L.B = 1; L.Hin = L.Hout = 1; L.Win = L.Wout = (int)npx;
+        L.tiles_y = 1; L.tiles_x = (int)((npx + L.TW - 1) / L.TW);
+    }
+    hipError_t e = launch_conv(L, st);
+    if (e != hipSuccess) return set_error(ctx, OBB_ERR_HIP, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return OBB_OK;
+}
+
+}  // namespace
 }  // namespace obb
 
 using namespace obb;
@@ -217,47 +321,16 @@ int obb_conv_wgrad_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int
     OBB_REQUIRE(ctx, ctx && B >= 1 && H > 0 && W > 0 && (ks == 1 || ks == 3), "obb_conv_wgrad_bf16: bad arguments");
     OBB_REQUIRE(ctx, cin % 64 == 0 && cout % 64 == 0, "obb_conv_wgrad_bf16: channel counts must be multiples of 64 (one workgroup = a 64 x 64 block of dW)");
     OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_bf16: NULL buffer");
-    hipStream_t st = (hipStream_t)s;
-    const int taps = ks * ks, pad = ks / 2;
-    const int Wp = (W + 3) & ~3, Wx = Wp + 2 * pad;
-    int R = 1;  // rows per tile: as many as 64 KiB of LDS hold
-    while (R < H && ((size_t)(R + 1 + 2 * pad) * Wx + (size_t)(R + 1) * Wp) * 128 <= 64 * 1024) ++R;
-    const size_t lds = ((size_t)(R + 2 * pad) * Wx + (size_t)R * Wp) * 128;
-    OBB_REQUIRE(ctx, lds <= 64 * 1024, "obb_conv_wgrad_bf16: a row of %d pixels does not fit the LDS tile", W);
-    const int ncob = cout / 64, ncib = cin / 64;
-    const int ntiles = B * ((H + R - 1) / R);
-    int nwalk = std::max(1, std::min(ntiles, 512 / (ncob * ncib)));
-    const size_t per = (size_t)ncob * ncib * taps * 4096;
-    float *slabs = (float *)ctx->workspace(WS_TRAIN_C, (size_t)nwalk * per * 4);
-    if (!slabs) return set_error(ctx, OBB_ERR_HIP, "obb_conv_wgrad_bf16: workspace allocation failed");
-    const dim3 grid((unsigned)nwalk, (unsigned)ncob, (unsigned)ncib);
-    if (ks == 3) hipLaunchKernelGGL((k_conv_wgrad<3>), grid, dim3(256), lds, st, x, dy, (int)B, (int)H, (int)W, (int)cin, (int)cout, R, slabs);
-    else hipLaunchKernelGGL((k_conv_wgrad<1>), grid, dim3(256), lds, st, x, dy, (int)B, (int)H, (int)W, (int)cin, (int)cout, R, slabs);
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, ncob, ncib, taps, (int)cin, (int)cout, dw);
-    OBB_LAUNCH_CHECK(ctx);
-    return OBB_OK;
+    return wgrad_launch(ctx, "obb_conv_wgrad_bf16", x, dy, B, H, W, cin, cout, ks, 1, dw, (hipStream_t)s);
 }
 
 int obb_conv_packed_elems(obb_ctx *ctx, int32_t cout, int32_t cin, int32_t ks, int32_t H, int32_t W, int32_t dgrad_form, int64_t *n_elems) {
-    OBB_REQUIRE(ctx, ctx && n_elems && cout > 0 && cin > 0 && (ks == 1 || ks == 3) && H > 0 && W > 0, "obb_conv_packed_elems: bad arguments");
-    const int coutL = dgrad_form ? cin : cout, cinL = dgrad_form ? cout : cin;
-    const ConvTiling t = plan_conv(ks, 1, cinL, coutL, H, W, false);
-    const int nstage = (cinL + t.CK - 1) / t.CK, ncb = (coutL + 16 * t.NF - 1) / (16 * t.NF);
-    *n_elems = (int64_t)ncb * nstage * conv_ksteps(ks, t.CK) * t.NF * 64 * 8;
-    return OBB_OK;
+    return packed_elems(ctx, "obb_conv_packed_elems", cout, cin, ks, 1, H, W, dgrad_form, n_elems);
 }
 
 int obb_conv_pack_bf16(obb_ctx *ctx, const float *w_oihw, int32_t cout, int32_t cin, int32_t ks, int32_t H, int32_t W, int32_t dgrad_form, uint16_t *packed,
                        obb_stream_t s) {
-    OBB_REQUIRE(ctx, ctx && w_oihw && packed, "obb_conv_pack_bf16: NULL buffer");
-    int64_t n = 0;
-    int rc = obb_conv_packed_elems(ctx, cout, cin, ks, H, W, dgrad_form, &n);
-    if (rc) return rc;
-    const int coutL = dgrad_form ? cin : cout, cinL = dgrad_form ? cout : cin;
-    const ConvTiling t = plan_conv(ks, 1, cinL, coutL, H, W, false);
-    hipLaunchKernelGGL(k_pack_conv_bf16, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)s, w_oihw, coutL, cinL, (int)ks, t.CK, t.NF, dgrad_form ? 1 : 0, packed, n);
-    OBB_LAUNCH_CHECK(ctx);
-    return OBB_OK;
+    return pack_launch(ctx, "obb_conv_pack_bf16", w_oihw, cout, cin, ks, 1, H, W, dgrad_form, packed, (hipStream_t)s);
 }
 
 int obb_conv_fwd_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w, const float *bias, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
@@ -266,30 +339,50 @@ int obb_conv_fwd_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w,
     OBB_REQUIRE(ctx, cin % 8 == 0 && cout % 8 == 0 && cin >= 8 && cout >= 8, "obb_conv_fwd_bf16: channel counts must be multiples of 8");
     if (B == 0) return OBB_OK;
     OBB_REQUIRE(ctx, x && packed_w && y, "obb_conv_fwd_bf16: NULL buffer");
+    return fwd_launch(ctx, "obb_conv_fwd_bf16", x, packed_w, bias, B, H, W, cin, cout, ks, 1, y, (hipStream_t)s);
+}
+
+// ---- stride 2 (3x3, pad 1): H x W -> (H + 1) / 2 x (W + 1) / 2
+int obb_conv_s2_packed_elems(obb_ctx *ctx, int32_t cout, int32_t cin, int32_t H, int32_t W, int64_t *n_elems) {
+    return packed_elems(ctx, "obb_conv_s2_packed_elems", cout, cin, 3, 2, H, W, 0, n_elems);
+}
+
+int obb_conv_s2_pack_bf16(obb_ctx *ctx, const float *w_oihw, int32_t cout, int32_t cin, int32_t H, int32_t W, uint16_t *packed, obb_stream_t s) {
+    return pack_launch(ctx, "obb_conv_s2_pack_bf16", w_oihw, cout, cin, 3, 2, H, W, 0, packed, (hipStream_t)s);
+}
+
+int obb_conv_fwd_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w, const float *bias, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                         uint16_t *y, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && B >= 0 && H > 0 && W > 0, "obb_conv_fwd_s2_bf16: bad arguments");
+    OBB_REQUIRE(ctx, cin % 8 == 0 && cout % 8 == 0 && cin >= 8 && cout >= 8, "obb_conv_fwd_s2_bf16: channel counts must be multiples of 8");
+    if (B == 0) return OBB_OK;
+    OBB_REQUIRE(ctx, x && packed_w && y, "obb_conv_fwd_s2_bf16: NULL buffer");
+    return fwd_launch(ctx, "obb_conv_fwd_s2_bf16", x, packed_w, bias, B, H, W, cin, cout, 3, 2, y, (hipStream_t)s);
+}
+
+int obb_conv_dgrad_s2_bf16(obb_ctx *ctx, const uint16_t *dy, const uint16_t *packed_dgrad, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, uint16_t *dx,
+                           obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && B >= 0 && H > 0 && W > 0, "obb_conv_dgrad_s2_bf16: bad arguments");
+    OBB_REQUIRE(ctx, cin % 8 == 0 && cout % 8 == 0 && cin >= 8 && cout >= 8, "obb_conv_dgrad_s2_bf16: channel counts must be multiples of 8");
+    if (B == 0) return OBB_OK;
+    OBB_REQUIRE(ctx, dy && packed_dgrad && dx, "obb_conv_dgrad_s2_bf16: NULL buffer");
     hipStream_t st = (hipStream_t)s;
-    const ConvTiling t = plan_conv(ks, 1, cin, cout, H, W, false);
-    // [bias padded to the kernel's 64-float granule (zeros without one)][2 KiB: the `lut` argument = the sink of the kernel's unconditional stores]
-    const size_t bbytes = (((size_t)cout + 63) / 64 * 64 * 4 + 256 + 255) & ~(size_t)255;
-    char *ws = (char *)ctx->workspace(WS_TRAIN_A, bbytes + 2048);
-    if (!ws) return set_error(ctx, OBB_ERR_HIP, "obb_conv_fwd_bf16: workspace allocation failed");
-    OBB_HIP(ctx, hipMemsetAsync(ws, 0, bbytes, st));
-    if (bias) OBB_HIP(ctx, hipMemcpyAsync(ws, bias, (size_t)cout * 4, hipMemcpyDeviceToDevice, st));
-    ConvLaunch L;
-    L.in.p = (void *)x; L.in.bs = (int64_t)H * W * cin; L.in.cs = cin; L.in.co = 0;
-    L.out.p = (void *)y; L.out.bs = (int64_t)H * W * cout; L.out.cs = cout; L.out.co = 0;
-    L.wpk = (const bf16_t *)packed_w; L.bias = (const float *)ws; L.lut = (const bf16_t *)(ws + bbytes);
-    L.B = B; L.Hin = L.Hout = H; L.Win = L.Wout = W; L.cin = cin; L.cout = cout; L.ks = ks; L.stride = 1; L.act = 0; L.f16 = 0;
-    L.TH = t.TH; L.TW = t.TW; L.MF = t.MF; L.NF = t.NF; L.CK = t.CK;
-    L.tiles_y = (H + t.TH - 1) / t.TH; L.tiles_x = (W + t.TW - 1) / t.TW;
-    if (ks == 1) {
-        const int64_t npx = (int64_t)B * H * W;
-        OBB_REQUIRE(ctx, npx < (1ll << 31) / 4, "obb_conv_fwd_bf16: too many pixels for one launch");
-        L.B = 1; L.Hin = L.Hout = 1; L.Win = L.Wout = (int)npx;
-        L.tiles_y = 1; L.tiles_x = (int)((npx + L.TW - 1) / L.TW);
-    }
-    hipError_t e = launch_conv(L, st);
-    if (e != hipSuccess) return set_error(ctx, OBB_ERR_HIP, "obb_conv_fwd_bf16: launch failed: %s", hipGetErrorString(e));
-    return OBB_OK;
+    const int64_t nchunk = (int64_t)B * H * W * (cout / 8);
+    uint16_t *up = (uint16_t *)ctx->workspace(WS_TRAIN_D, (size_t)nchunk * 16);
+    if (!up) return set_error(ctx, OBB_ERR_HIP, "obb_conv_dgrad_s2_bf16: workspace allocation failed");
+    hipLaunchKernelGGL(k_zero_insert_s2, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nchunk, 256), 2048))), dim3(256), 0, st, dy, (int)H, (int)W,
+                       out_dim(H, 2), out_dim(W, 2), (int)(cout / 8), nchunk, up);
+    OBB_LAUNCH_CHECK(ctx);
+    return fwd_launch(ctx, "obb_conv_dgrad_s2_bf16", up, packed_dgrad, nullptr, B, H, W, cout, cin, 3, 1, dx, st);
+}
+
+int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, float *dw, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && B >= 1 && H > 0 && W > 0, "obb_conv_wgrad_s2_bf16: bad arguments");
+    OBB_REQUIRE(ctx, cin % 64 == 0 && cout % 64 == 0,
+                "obb_conv_wgrad_s2_bf16: cin = %d, cout = %d: channel counts must be multiples of 64 (one workgroup = a 64 x 64 block of dW); "
+                "models 0 and 1 of the backbone (3 -> 32, 32 -> 64) have no stride-2 wgrad", (int)cin, (int)cout);
+    OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_s2_bf16: NULL buffer");
+    return wgrad_launch(ctx, "obb_conv_wgrad_s2_bf16", x, dy, B, H, W, cin, cout, 3, 2, dw, (hipStream_t)s);
 }
 
 int obb_silu_bf16(obb_ctx *ctx, const uint16_t *z, uint16_t *a, int64_t n, obb_stream_t s) {

@@ -244,6 +244,20 @@ def _adamw_step(param: T, grad: T, exp_avg: T, exp_avg_sq: T, step: int, lr: flo
           float(eps), float(weight_decay), _stream())
 
 
+@_op("bn_silu_fwd", ("running_mean", "running_var", "mean", "invstd", "a"))
+def _bn_silu_fwd(z: T, gamma: T, beta: T, eps: float, momentum: float, running_mean: T, running_var: T, mean: T, invstd: T, a: T) -> None:
+    C = z.shape[-1]
+    _call("obb_bn_silu_fwd_bf16", ctx(z.device), _p(z), z.numel() // C, C, _p(gamma), _p(beta), float(eps), float(momentum), _p(running_mean), _p(running_var),
+          _p(mean), _p(invstd), _p(a), _stream())
+
+
+@_op("bn_silu_bwd", ("dgamma", "dbeta", "dz"))
+def _bn_silu_bwd(z: T, da: T, gamma: T, beta: T, mean: T, invstd: T, dgamma: T, dbeta: T, dz: T) -> None:
+    C = z.shape[-1]
+    _call("obb_bn_silu_bwd_bf16", ctx(z.device), _p(z), _p(da), z.numel() // C, C, _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dgamma), _p(dbeta), _p(dz),
+          _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -421,38 +435,110 @@ def conv_dgrad_bf16(dy, weight):
     return dx
 
 
-def conv_wgrad_bf16(x, dy, ks):
-    """x bf16 [B,H,W,cin], dy bf16 [B,H,W,cout] (NHWC, device) -> dw fp32 [cout,cin,ks,ks]: the weight gradient of the stride-1 `same`
-    convolution, fp32 accumulation, deterministic."""
+def _stride_ok(ks, stride):
+    if stride not in (1, 2) or (stride == 2 and ks != 3):
+        raise ValueError(f"stride {stride} with k = {ks}: stride 1 (k 1 or 3) and stride 2 (k 3) are built")
+
+
+def conv_wgrad_bf16(x, dy, ks, stride=1, out=None):
+    """x bf16 [B,H,W,cin], dy bf16 [B,Ho,Wo,cout] (NHWC, device) -> dw fp32 [cout,cin,ks,ks] (into `out` if given): the weight gradient of the
+    `same`-padded convolution (stride 1: Ho = H; stride 2, k 3: Ho = (H + 1) // 2), fp32 accumulation, deterministic."""
+    _stride_ok(ks, stride)
     xx, d = _chk(x, torch.bfloat16, "x"), _chk(dy, torch.bfloat16, "dy")
     B, H, W, cin = xx.shape
     cout = d.shape[3]
-    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=xx.device)
-    _call("obb_conv_wgrad_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), _p(dw), _stream())
+    if tuple(d.shape[:3]) != (B, (H + stride - 1) // stride, (W + stride - 1) // stride):
+        raise ValueError(f"conv_wgrad_bf16: dy {tuple(d.shape)} does not match x {tuple(xx.shape)} at stride {stride}")
+    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=xx.device) if out is None else _chk(out, torch.float32, "out")
+    if dw.shape != (cout, cin, ks, ks):
+        raise ValueError("conv_wgrad_bf16: out has the wrong shape")
+    if stride == 2:
+        _call("obb_conv_wgrad_s2_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, _p(dw), _stream())
+    else:
+        _call("obb_conv_wgrad_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), _p(dw), _stream())
     return dw
 
 
-def conv_pack_bf16(w, H, W, dgrad_form=False):
-    """fp32 OIHW master weights (device) -> the bf16 MFMA fragment order of the conv kernel for H x W maps, packed ON THE DEVICE (no host
-    repack, no synchronisation); dgrad_form: the flipped / channel-transposed weights whose forward convolution is the input gradient."""
+def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
+    """fp32 OIHW master weights (device) -> the bf16 MFMA fragment order of the conv kernel for H x W input maps, packed ON THE DEVICE (no
+    host repack, no synchronisation); dgrad_form: the flipped / channel-transposed weights whose forward convolution is the input gradient.
+    The dgrad form does not depend on the stride: the stride-2 input gradient (conv_dgrad_s2_bf16) is a stride-1 conv on the H x W map."""
     ww = _chk(w, torch.float32, "w")
     cout, cin, ks, _ = ww.shape
+    _stride_ok(ks, stride)
     n = C.c_int64(0)
+    out_of = lambda n: torch.empty(n.value, dtype=torch.bfloat16, device=ww.device)
+    if stride == 2 and not dgrad_form:
+        _call("obb_conv_s2_packed_elems", ctx(ww.device), cout, cin, int(H), int(W), C.byref(n))
+        out = out_of(n)
+        _call("obb_conv_s2_pack_bf16", ctx(ww.device), _p(ww), cout, cin, int(H), int(W), _p(out), _stream())
+        return out
     _call("obb_conv_packed_elems", ctx(ww.device), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), C.byref(n))
-    out = torch.empty(n.value, dtype=torch.bfloat16, device=ww.device)
+    out = out_of(n)
     _call("obb_conv_pack_bf16", ctx(ww.device), _p(ww), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), _p(out), _stream())
     return out
 
 
-def conv_fwd_bf16(x, packed, bias, cout, ks):
-    """y = conv(x) + bias (stride 1, `same` padding, no activation): x bf16 [B,H,W,cin] NHWC, packed = conv_pack_bf16 of the [cout,cin,ks,ks]
-    weights for this H x W, bias fp32 [cout] or None -> bf16 [B,H,W,cout]."""
+def conv_fwd_bf16(x, packed, bias, cout, ks, stride=1):
+    """y = conv(x) + bias (`same` padding, no activation): x bf16 [B,H,W,cin] NHWC, packed = conv_pack_bf16 of the [cout,cin,ks,ks]
+    weights for this H x W and stride, bias fp32 [cout] or None -> bf16 [B,Ho,Wo,cout] (stride 2, k 3: Ho = (H + 1) // 2)."""
+    _stride_ok(ks, stride)
     xx = _chk(x, torch.bfloat16, "x")
     B, H, W, cin = xx.shape
-    y = torch.empty((B, H, W, cout), dtype=torch.bfloat16, device=xx.device)
     b = _chk(bias, torch.float32, "bias") if bias is not None else None
-    _call("obb_conv_fwd_bf16", ctx(xx.device), _p(xx), _p(_chk(packed, torch.bfloat16, "packed")), _p(b), B, H, W, cin, int(cout), int(ks), _p(y), _stream())
+    pk = _chk(packed, torch.bfloat16, "packed")
+    if stride == 2:
+        y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, cout), dtype=torch.bfloat16, device=xx.device)
+        _call("obb_conv_fwd_s2_bf16", ctx(xx.device), _p(xx), _p(pk), _p(b), B, H, W, cin, int(cout), _p(y), _stream())
+        return y
+    y = torch.empty((B, H, W, cout), dtype=torch.bfloat16, device=xx.device)
+    _call("obb_conv_fwd_bf16", ctx(xx.device), _p(xx), _p(pk), _p(b), B, H, W, cin, int(cout), int(ks), _p(y), _stream())
     return y
+
+
+def conv_dgrad_s2_bf16(dy, packed_dgrad, cin, H, W):
+    """Input gradient of the stride-2 3x3 conv: dy bf16 [B,Ho,Wo,cout] -> dx bf16 [B,H,W,cin] (H, W: the forward's input size, Ho = (H + 1) // 2),
+    packed_dgrad = conv_pack_bf16(w, H, W, dgrad_form=True).  Zero insertion + the stride-1 forward kernel: 4x the useful MACs."""
+    d = _chk(dy, torch.bfloat16, "dy")
+    B, Ho, Wo, cout = d.shape
+    if (Ho, Wo) != ((H + 1) // 2, (W + 1) // 2):
+        raise ValueError(f"conv_dgrad_s2_bf16: dy {tuple(d.shape)} is not the stride-2 output of {H} x {W}")
+    dx = torch.empty((B, H, W, cin), dtype=torch.bfloat16, device=d.device)
+    _call("obb_conv_dgrad_s2_bf16", ctx(d.device), _p(d), _p(_chk(packed_dgrad, torch.bfloat16, "packed_dgrad")), B, int(H), int(W), int(cin), cout, _p(dx),
+          _stream())
+    return dx
+
+
+def bn_silu_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, momentum=0.03):
+    """Training-mode BatchNorm2d + SiLU over the rows of z bf16 [..., C] (NHWC): -> (a bf16 like z, batch mean fp32 [C], invstd fp32 [C]);
+    running_mean / running_var (fp32 [C]) are updated in place with `momentum`, the running variance unbiased (torch's rule)."""
+    zz = _chk(z, torch.bfloat16, "z")
+    Cn = zz.shape[-1]
+    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var"))]
+    if any(t.numel() != Cn for t in vecs):
+        raise ValueError("bn_silu_fwd_bf16: per-channel vectors must have C entries")
+    a = torch.empty_like(zz)
+    mean = torch.empty(Cn, dtype=torch.float32, device=zz.device)
+    invstd = torch.empty_like(mean)
+    _O.bn_silu_fwd(zz, vecs[0], vecs[1], float(eps), float(momentum), vecs[2], vecs[3], mean, invstd, a)
+    return a, mean, invstd
+
+
+def bn_silu_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None):
+    """Backward of bn_silu_fwd_bf16 (batch statistics): z, da bf16 [..., C] -> (dz bf16 like z, dgamma fp32 [C], dbeta fp32 [C]); dgamma / dbeta
+    go into the given tensors (e.g. views of an optimiser group's gradient buffer) when passed."""
+    zz, d = _chk(z, torch.bfloat16, "z"), _chk(da, torch.bfloat16, "da")
+    if d.shape != zz.shape:
+        raise ValueError("bn_silu_bwd_bf16: da must have the shape of z")
+    Cn = zz.shape[-1]
+    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
+    dg = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dgamma is None else _chk(dgamma, torch.float32, "dgamma")
+    db = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dbeta is None else _chk(dbeta, torch.float32, "dbeta")
+    if any(t.numel() != Cn for t in vecs + [dg, db]):
+        raise ValueError("bn_silu_bwd_bf16: per-channel vectors must have C entries")
+    dz = torch.empty_like(zz)
+    _O.bn_silu_bwd(zz, d, *vecs, dg, db, dz)
+    return dz, dg, db
 
 
 def silu_bf16(z):

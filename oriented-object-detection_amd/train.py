@@ -10,7 +10,9 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
   * `allreduce_gradients`: the DDP gradient average of `device="0,1"` (Train_OBB.py: DEVICE) as bucketed all-reduces over
     torch.distributed (backend "nccl" = RCCL over xGMI on the GPU box; gloo in the CPU test): the flat gradient buffers are already
     contiguous, so a bucket is a view, not a copy; buckets of `bucket_mb` keep a ring all-reduce per-link bandwidth-bound rather than
-    latency-bound (7 xGMI links x ~153 GB/s per GPU: a 25 MB bucket is ~0.1 ms of wire time per hop)."""
+    latency-bound (7 xGMI links x ~153 GB/s per GPU: a 25 MB bucket is ~0.1 ms of wire time per hop);
+  * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
+    training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded."""
 import math
 
 import torch
@@ -150,4 +152,137 @@ class BoxBranchStep:
         loss, dx = self.forward_backward(x, target_ltrb, weight, target_scores_sum)
         allreduce_gradients([self.opt_w.grad, self.opt_b.grad], group)           # DDP: the gradient average (no-op on one rank)
         self.opt_w.step(); self.opt_b.step()
+        return loss, dx
+
+
+class ParamGroups:
+    """The trainer's three optimiser groups (`param_group_of`: 0 = weights with decay, 1 = norm weights, 2 = biases; no decay in 1 and 2) as
+    FlatOptimizers.  Layers `add` their initial tensors before `build()` allocates the flat buffers; afterwards `param[i]` / `grad[i]` are
+    views of them, so the layers' kernels write gradients straight into the groups' gradient buffers."""
+
+    def __init__(self, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, betas=None):
+        self.cfg = dict(name=optimizer, lr=lr, momentum=momentum, nesterov=nesterov, betas=betas)
+        self.weight_decay = weight_decay
+        self.items, self.opts, self.param, self.grad = [], None, None, None
+
+    def add(self, group, init):
+        if self.opts is not None:
+            raise RuntimeError("ParamGroups.add after build()")
+        self.items.append((int(group), init))
+        return len(self.items) - 1
+
+    def build(self):
+        dev = self.items[0][1].device
+        shapes = [[tuple(t.shape) for g, t in self.items if g == k] for k in range(3)]
+        self.opts = [FlatOptimizer(sum(int(math.prod(s)) for s in shapes[k]), dev, weight_decay=self.weight_decay if k == 0 else 0.0, **self.cfg)
+                     for k in range(3)]
+        pv = [FlatOptimizer.views(o.param, sh) for o, sh in zip(self.opts, shapes)]
+        gv = [FlatOptimizer.views(o.grad, sh) for o, sh in zip(self.opts, shapes)]
+        self.param, self.grad, nxt = [], [], [0, 0, 0]
+        for g, t in self.items:
+            self.param.append(pv[g][nxt[g]]); self.grad.append(gv[g][nxt[g]])
+            self.param[-1].copy_(t)
+            nxt[g] += 1
+        return self
+
+    def flat_grads(self):
+        return [o.grad for o in self.opts if o.n]
+
+    def step(self, lr=None):
+        for o in self.opts:
+            if o.n:
+                o.step(lr)
+
+
+class ConvBN:
+    """ONE Ultralytics `Conv(c1, c2, k, s)` block in training mode -- Conv2d(bias=False) -> BatchNorm2d (batch statistics, running statistics
+    updated) -> SiLU -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
+    k = 1 or 3; s = 2 with k = 3 only (the downsampling convs).  Ultralytics' initialize_weights sets eps = 1e-3, momentum = 0.03 (recalled:
+    the package is not installed here, so these defaults are unpinned like optimizer_config; both are arguments).  Every arithmetic step on
+    the device is a libobbhip kernel; running statistics are buffers of the block, not parameters."""
+
+    def __init__(self, groups, w, gamma=None, beta=None, s=1, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
+        c2, c1, k, k2 = w.shape
+        if k != k2 or k not in (1, 3) or s not in (1, 2) or (s == 2 and k != 3):
+            raise ValueError(f"ConvBN: k = {k}, s = {s}: k 1 or 3 at stride 1, k 3 at stride 2")
+        self.c1, self.c2, self.k, self.s, self.eps, self.momentum = c1, c2, k, s, eps, momentum
+        dev = w.device
+        self.groups = groups
+        self._iw = groups.add(0, w)
+        self._ig = groups.add(1, gamma if gamma is not None else torch.ones(c2, device=dev))
+        self._ib = groups.add(2, beta if beta is not None else torch.zeros(c2, device=dev))
+        self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c2, device=dev)).float().contiguous()
+        self.running_var = (running_var.clone() if running_var is not None else torch.ones(c2, device=dev)).float().contiguous()
+        self.saved = None
+
+    w = property(lambda self: self.groups.param[self._iw])
+    gamma = property(lambda self: self.groups.param[self._ig])
+    beta = property(lambda self: self.groups.param[self._ib])
+    dw = property(lambda self: self.groups.grad[self._iw])
+    dgamma = property(lambda self: self.groups.grad[self._ig])
+    dbeta = property(lambda self: self.groups.grad[self._ib])
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> a bf16 [B,Ho,Wo,c2]; keeps (x, z, mean, invstd) for the backward."""
+        H, W = x.shape[1], x.shape[2]
+        z = ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, H, W, stride=self.s), None, self.c2, self.k, stride=self.s)
+        a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
+        self.saved = (x, z, mean, invstd)
+        return a
+
+    def backward(self, da):
+        """da bf16 like the forward's output -> dx bf16 like its input; dW, dgamma, dbeta are written into the groups' gradient buffers."""
+        x, z, mean, invstd = self.saved
+        H, W = x.shape[1], x.shape[2]
+        dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
+        ops.conv_wgrad_bf16(x, dz, self.k, stride=self.s, out=self.dw)
+        bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
+        if self.s == 2:
+            return ops.conv_dgrad_s2_bf16(dz, bw, self.c1, H, W)
+        return ops.conv_fwd_bf16(dz, bw, None, self.c1, self.k)
+
+    def fold(self):
+        """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32."""
+        f = self.gamma / torch.sqrt(self.running_var + self.eps)
+        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+
+class DetectBoxBranchStep:
+    """Ultralytics Detect.cv2[i] trained as the reference trains it, BatchNorm UNFOLDED: ConvBN 3x3 -> ConvBN 3x3 -> Conv2d 1x1 (+bias) ->
+    4 x 16 DFL logits per anchor -> DFL loss -> backward -> DDP gradient average -> optimiser step, over the trainer's three parameter groups
+    (the unfolded counterpart of BoxBranchStep).  convs: two (w, gamma, beta) triples (gamma / beta None: 1 / 0); w3 [c_out, c, 1, 1], b3 [c_out]."""
+
+    def __init__(self, convs, w3, b3, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3, bn_momentum=0.03):
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        self.blocks = [ConvBN(self.groups, w, g, b, eps=eps, momentum=bn_momentum) for (w, g, b) in convs]
+        self._i3, self._ib3 = self.groups.add(0, w3), self.groups.add(2, b3)
+        self.groups.build()
+        self.cout3 = w3.shape[0]
+
+    w3 = property(lambda self: self.groups.param[self._i3])
+    b3 = property(lambda self: self.groups.param[self._ib3])
+    dw3 = property(lambda self: self.groups.grad[self._i3])
+    db3 = property(lambda self: self.groups.grad[self._ib3])
+
+    def forward_backward(self, x, target_ltrb, weight=None, target_scores_sum=1.0):
+        """x bf16 [B,H,W,cin]; target_ltrb fp32 [B*H*W, 4] (bins), weight fp32 [B*H*W] or None -> (loss fp32[1], dx bf16 like x); every parameter
+        gradient is left in the groups' gradient buffers."""
+        H, W = x.shape[1], x.shape[2]
+        a = x
+        for blk in self.blocks:
+            a = blk.forward(a)
+        out = ops.conv_fwd_bf16(a, ops.conv_pack_bf16(self.w3, H, W), self.b3, self.cout3, 1)
+        loss, g = ops.dfl_loss(out.float().reshape(-1, self.cout3), target_ltrb, weight, target_scores_sum)
+        d3 = g.reshape(out.shape).to(torch.bfloat16)
+        ops.conv_wgrad_bf16(a, d3, 1, out=self.dw3)
+        ops.bias_grad_bf16(d3, self.db3)
+        d = ops.conv_fwd_bf16(d3, ops.conv_pack_bf16(self.w3, H, W, dgrad_form=True), None, self.w3.shape[1], 1)
+        for blk in reversed(self.blocks):
+            d = blk.backward(d)
+        return loss, d
+
+    def step(self, x, target_ltrb, weight=None, target_scores_sum=1.0, group=None):
+        loss, dx = self.forward_backward(x, target_ltrb, weight, target_scores_sum)
+        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
+        self.groups.step()
         return loss, dx
