@@ -9,11 +9,13 @@
 //
 // Reductions (deterministic, no float atomics -- the rule of convgrad.hip): the pixel dimension is split into nbx contiguous blocks, one
 // workgroup per (pixel block, 256-channel group); a thread owns 8 channels (one 16-byte load per pixel) and every RP-th pixel of the block,
-// its partial sums meet in LDS and are added in row order.  The per-block results go to an fp32 slab [nbx][C]; a second kernel combines the
+// its partial sums meet in LDS and are added in a fixed pairwise tree over the rows.  The per-block results go to an fp32 slab [nbx][C]; a second kernel combines the
 // slab in a fixed order (64 strided walkers per channel, then a pairwise tree: walker w takes in walker w + s for s = 32, 16, .., 1).
 // The forward's slab holds (mean, M2) pairs of each block -- the block's mean first, then the sum of squares about it, read back from
 // cache -- combined with Chan's parallel formula, so the variance never comes from E[z^2] - E[z]^2 (which cancels catastrophically when
-// |mean| >> std).  The backward's slab holds plain sums.  Both directions share the geometry (bn_geo) and the LDS reduction (block_reduce8).
+// |mean| >> std).  Every statistic is taken of z - z[pixel 0] (per channel; exact in fp32): the block means and the deviations between them
+// that Chan's formula squares are then of the size of std, not of |mean| -- without the shift, the fp32 spacing of a mean of 8 (4.8e-7) made
+// the variance of a std-0.05 channel wrong by 3e-6 relative.  The backward's slab holds plain sums.  Both directions share the geometry (bn_geo) and the LDS reduction (block_reduce8).
 #include <algorithm>
 
 #include "ctx.h"
@@ -59,18 +61,29 @@ BnGeo bn_geo(int64_t npix, int C) {
     return g;
 }
 
-// Sums the 8 per-thread values s[] over the RP rows of the workgroup in row order; thread t < CW*8 gets channel chunk t / 8, lane t % 8.
-// red: 256 * 8 floats of LDS.  Returns the sum for threads t < CW*8 (0 elsewhere).  Ends with every thread past a barrier.
+// Sums the 8 per-thread values s[] over the RP rows of the workgroup in a fixed pairwise tree (row r takes in row r + st for st = 128, .., 1;
+// RP need not be a power of two); thread t < CW*8 gets channel chunk t / 8, lane t % 8.  (A serial walk over the rows was a 256-term fp32 chain
+// at C = 8: 2e-6 of the variance of a mean-8, std-0.05 channel.)  red: 256 * 8 floats of LDS.  Returns the sum for threads t < CW*8 (0
+// elsewhere).  Ends with every thread past a barrier.
 __device__ __forceinline__ float block_reduce8(float *red, const float s[8], int row, int col, int CW, int RP) {
+    float4 *r4 = reinterpret_cast<float4 *>(red + (row * CW + col) * 8);
     if (row < RP) {
-        float4 *r4 = reinterpret_cast<float4 *>(red + (row * CW + col) * 8);
         r4[0] = make_float4(s[0], s[1], s[2], s[3]);
         r4[1] = make_float4(s[4], s[5], s[6], s[7]);
     }
+    int st = 1;
+    while (st < RP) st <<= 1;
+    for (st >>= 1; st >= 1; st >>= 1) {
+        __syncthreads();
+        if (row < st && row + st < RP) {
+            const float4 *o4 = reinterpret_cast<const float4 *>(red + ((row + st) * CW + col) * 8);
+            const float4 a0 = r4[0], a1 = r4[1], b0 = o4[0], b1 = o4[1];
+            r4[0] = make_float4(a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w);
+            r4[1] = make_float4(a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w);
+        }
+    }
     __syncthreads();
-    float t = 0.f;
-    if ((int)threadIdx.x < CW * 8)
-        for (int r = 0; r < RP; ++r) t += red[r * CW * 8 + threadIdx.x];
+    const float t = (int)threadIdx.x < CW * 8 ? red[threadIdx.x] : 0.f;
     __syncthreads();
     return t;
 }
@@ -97,12 +110,13 @@ __global__ __launch_bounds__(256) void k_bn_stats_part(const unsigned short *__r
     const bool act = row < RP && c8 < C8;
     const int64_t p0 = (int64_t)blockIdx.x * PB, p1 = min(p0 + PB, npix);
     const float inv_n = 1.0f / (float)(p1 - p0);
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8];
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8], k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (act) unpack8(*reinterpret_cast<const uint4 *>(z + c8 * 8), k);  // the shift: pixel 0's value
     if (act)
         for (int64_t p = p0 + row; p < p1; p += RP) {
             unpack8(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) s[j] += v[j];
+            for (int j = 0; j < 8; ++j) s[j] += v[j] - k[j];
         }
     const float mu = block_reduce8(red, s, row, col, CW, RP) * inv_n;
     if (tid < CW * 8) bmean[tid] = mu;
@@ -114,16 +128,16 @@ __global__ __launch_bounds__(256) void k_bn_stats_part(const unsigned short *__r
         for (int64_t p = p0 + row; p < p1; p += RP) {
             unpack8(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float d = v[j] - m[j]; s[j] += d * d; }
+            for (int j = 0; j < 8; ++j) { const float d = (v[j] - k[j]) - m[j]; s[j] += d * d; }
         }
     const float m2 = block_reduce8(red, s, row, col, CW, RP);
     const int c = (blockIdx.y * kGroupChunks) * 8 + tid;
     if (tid < CW * 8 && c < C) { slab_mean[(size_t)blockIdx.x * C + c] = mu; slab_m2[(size_t)blockIdx.x * C + c] = m2; }
 }
 
-// forward, pass 2: combine the slab (walkers, then the tree) -> mean, invstd; running statistics updated in place
-__global__ __launch_bounds__(256) void k_bn_stats_final(const float *__restrict__ slab_mean, const float *__restrict__ slab_m2, int nbx, int64_t PB, int64_t npix,
-                                                        int C, float eps, float momentum, float *__restrict__ running_mean, float *__restrict__ running_var,
+// forward, pass 2: combine the slab (walkers, then the tree) -> mean (shift added back), invstd; running statistics updated in place
+__global__ __launch_bounds__(256) void k_bn_stats_final(const unsigned short *__restrict__ z, const float *__restrict__ slab_mean, const float *__restrict__ slab_m2, int nbx,
+                                                        int64_t PB, int64_t npix, int C, float eps, float momentum, float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ mean, float *__restrict__ invstd) {
     __shared__ float sn[kWalkers][kWalkCh], smu[kWalkers][kWalkCh], sm2[kWalkers][kWalkCh];
     const int cl = threadIdx.x % kWalkCh, w = threadIdx.x / kWalkCh, c = blockIdx.x * kWalkCh + cl;
@@ -140,10 +154,10 @@ __global__ __launch_bounds__(256) void k_bn_stats_final(const float *__restrict_
         }
     }
     if (w != 0 || c >= C) return;
-    const float N = (float)npix, var = m2 / N;
-    mean[c] = mu;
+    const float N = (float)npix, var = m2 / N, mc = bn_from_bf16(z[c]) + mu;
+    mean[c] = mc;
     invstd[c] = 1.0f / sqrtf(var + eps);
-    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mu;
+    running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mc;
     running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (m2 / (N - 1.0f));
 }
 
@@ -258,7 +272,7 @@ int obb_bn_silu_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t 
     if (!slab) return set_error(ctx, OBB_ERR_HIP, "obb_bn_silu_fwd_bf16: workspace allocation failed");
     float *slab_m2 = slab + (size_t)g.nbx * C;
     hipLaunchKernelGGL(k_bn_stats_part, dim3((unsigned)g.nbx, (unsigned)g.ny), dim3(256), 0, st, z, npix, (int)C, g.PB, g.CW, g.RP, slab, slab_m2);
-    hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, slab, slab_m2, g.nbx, g.PB, npix, (int)C, eps, momentum, running_mean,
+    hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, z, slab, slab_m2, g.nbx, g.PB, npix, (int)C, eps, momentum, running_mean,
                        running_var, mean, invstd);
     const int64_t nchunk = npix * g.C8;
     hipLaunchKernelGGL(k_bn_silu_apply, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, nchunk, g.C8, gamma, beta, mean, invstd, a);

@@ -479,6 +479,19 @@ def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
     return out
 
 
+def _check_packed(pk, fn, cout, cin, ks, H, W, stride=1, dgrad_form=False):
+    """plan_conv picks the packed layout from the map size (13-multiple maps: single-stage WRES, CK = cin; others CK = 16): a blob packed for
+    another H x W would be read in the wrong layout.  Its length tells the layouts apart."""
+    n = C.c_int64(0)
+    if stride == 2 and not dgrad_form:
+        _call("obb_conv_s2_packed_elems", ctx(pk.device), cout, cin, int(H), int(W), C.byref(n))
+    else:
+        _call("obb_conv_packed_elems", ctx(pk.device), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), C.byref(n))
+    if pk.numel() != n.value:
+        raise ValueError(f"{fn}: packed weights hold {pk.numel()} elements, {n.value} expected for {cin} -> {cout}, k {ks}, stride {stride} at {H} x {W}: "
+                         "packed for another map size or layer?")
+
+
 def conv_fwd_bf16(x, packed, bias, cout, ks, stride=1):
     """y = conv(x) + bias (`same` padding, no activation): x bf16 [B,H,W,cin] NHWC, packed = conv_pack_bf16 of the [cout,cin,ks,ks]
     weights for this H x W and stride, bias fp32 [cout] or None -> bf16 [B,Ho,Wo,cout] (stride 2, k 3: Ho = (H + 1) // 2)."""
@@ -487,6 +500,7 @@ def conv_fwd_bf16(x, packed, bias, cout, ks, stride=1):
     B, H, W, cin = xx.shape
     b = _chk(bias, torch.float32, "bias") if bias is not None else None
     pk = _chk(packed, torch.bfloat16, "packed")
+    _check_packed(pk, "conv_fwd_bf16", int(cout), cin, ks, H, W, stride)
     if stride == 2:
         y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, cout), dtype=torch.bfloat16, device=xx.device)
         _call("obb_conv_fwd_s2_bf16", ctx(xx.device), _p(xx), _p(pk), _p(b), B, H, W, cin, int(cout), _p(y), _stream())
@@ -503,8 +517,10 @@ def conv_dgrad_s2_bf16(dy, packed_dgrad, cin, H, W):
     B, Ho, Wo, cout = d.shape
     if (Ho, Wo) != ((H + 1) // 2, (W + 1) // 2):
         raise ValueError(f"conv_dgrad_s2_bf16: dy {tuple(d.shape)} is not the stride-2 output of {H} x {W}")
+    pk = _chk(packed_dgrad, torch.bfloat16, "packed_dgrad")
+    _check_packed(pk, "conv_dgrad_s2_bf16", cout, int(cin), 3, H, W, dgrad_form=True)
     dx = torch.empty((B, H, W, cin), dtype=torch.bfloat16, device=d.device)
-    _call("obb_conv_dgrad_s2_bf16", ctx(d.device), _p(d), _p(_chk(packed_dgrad, torch.bfloat16, "packed_dgrad")), B, int(H), int(W), int(cin), cout, _p(dx),
+    _call("obb_conv_dgrad_s2_bf16", ctx(d.device), _p(d), _p(pk), B, int(H), int(W), int(cin), cout, _p(dx),
           _stream())
     return dx
 
@@ -558,8 +574,10 @@ def silu_bwd_bf16(z, da):
 def bias_grad_bf16(dy, out=None):
     d = _chk(dy, torch.bfloat16, "dy")
     cout = d.shape[-1]
-    db = out if out is not None else torch.empty(cout, dtype=torch.float32, device=d.device)
-    _call("obb_bias_grad_bf16", ctx(d.device), _p(d), d.numel() // cout, cout, _p(_chk(db, torch.float32, "db")), _stream())
+    db = _chk(out, torch.float32, "out") if out is not None else torch.empty(cout, dtype=torch.float32, device=d.device)
+    if db.numel() != cout:
+        raise ValueError(f"bias_grad_bf16: out has {db.numel()} entries, dy has {cout} channels")
+    _call("obb_bias_grad_bf16", ctx(d.device), _p(d), d.numel() // cout, cout, _p(db), _stream())
     return db
 
 
