@@ -306,11 +306,12 @@ int obb_bce_loss(obb_ctx *ctx, const float *logits, const float *targets, int64_
 /* f1 (optimiser step): the update behind `model.train(...)` (Train_OBB.py:796-841; ultralytics `build_optimizer`: torch.optim.SGD with
  * nesterov momentum or torch.optim.AdamW, three parameter groups).  A group = flat fp32 device buffers of n elements, 16-byte aligned.
  * obb_sgd_step: d = grad + weight_decay * param; buf = first_step ? d : momentum * buf + d; d = nesterov ? d + momentum * buf : buf;
- * param -= lr * d (momentum 0: no buffer touched).  obb_adamw_step: torch.optim.AdamW's single-tensor order with step counted from 1. */
+ * param -= lr * d (momentum 0: no buffer touched).  obb_adamw_step: torch.optim.AdamW's single-tensor order with step counted from 1;
+ * the betas are double, as torch's Python floats: the bias corrections and 1 - beta come from them (1 - 0.999f is 1.3e-5 off 0.001). */
 int obb_sgd_step(obb_ctx *ctx, float *param, const float *grad, float *momentum_buf, int64_t n, float lr, float momentum, float weight_decay,
                  int32_t nesterov, int32_t first_step, obb_stream_t s);
-int obb_adamw_step(obb_ctx *ctx, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, obb_stream_t s);
+int obb_adamw_step(obb_ctx *ctx, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr, double beta1,
+                   double beta2, float eps, float weight_decay, obb_stream_t s);
 
 #ifdef __cplusplus
 }

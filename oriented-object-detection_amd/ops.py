@@ -890,6 +890,8 @@ def probiou_loss(pred, target, weight=None, target_scores_sum=1.0):
         raise ValueError("probiou_loss: shape mismatch")
     if weight is not None:
         weight = _chk(weight, torch.float32, "weight").reshape(-1)
+        if weight.shape[0] != p.shape[0]:
+            raise ValueError("probiou_loss: weight length mismatch")
     loss = torch.zeros(1, dtype=torch.float32, device=p.device)
     grad = torch.empty_like(p)
     _O.probiou_loss(p, t, weight, float(target_scores_sum), loss, grad)

@@ -19,12 +19,12 @@ import torch
 import torch.nn.functional as F
 
 import train_shapes as TS
+from bounds import Guarded, _check, _same_thrice
 
 pytestmark = pytest.mark.gpu
 
 U, UBF = 2.0 ** -24, 2.0 ** -8
 R = 1e-6
-GUARD = 4096
 EPS, MOM = 1e-3, 0.03  # Ultralytics' BatchNorm settings
 BF16_MAX = float(torch.finfo(torch.bfloat16).max)
 
@@ -33,41 +33,6 @@ def _ops():
     import oriented_object_detection_amd  # noqa: F401
     from oriented_object_detection_amd import _lib, ops
     return ops, _lib
-
-
-class Guarded:
-    """[4 KiB guard | output (16-byte aligned) | 4 KiB guard] in one device allocation, every byte 0xff; `init` fills the output part."""
-
-    def __init__(self, shape, dtype, init=None):
-        n = math.prod(shape)
-        self.nb = n * torch.empty((), dtype=dtype).element_size()
-        self.raw = torch.full((GUARD + self.nb + GUARD,), 0xFF, dtype=torch.uint8, device="cuda")
-        assert self.raw.data_ptr() % 16 == 0
-        self.out = self.raw[GUARD:GUARD + self.nb].view(dtype).view(shape)
-        if init is not None:
-            self.out.copy_(init)
-
-    def guards_intact(self):
-        return bool((self.raw[:GUARD] == 0xFF).all()) and bool((self.raw[GUARD + self.nb:] == 0xFF).all())
-
-    def get(self, what):
-        torch.cuda.synchronize()
-        assert self.guards_intact(), f"{what}: write outside the output"
-        assert bool(torch.isfinite(self.out.float()).all()), f"{what}: output element not written (NaN fill left) or not finite"
-        return self.out.clone()
-
-
-def _check(what, got, ref, bound):
-    """|got - ref| <= bound element-wise (fp64); prints the worst ratio (the margin)."""
-    got = got.double().cpu().reshape(ref.shape)
-    d = (got - ref).abs()
-    ratio = torch.where(d == 0, torch.zeros_like(d), d / bound)
-    worst = float(ratio.max()) if ratio.numel() else 0.0
-    print(f"  {what}: max |got - ref| / bound = {worst:.3f}")
-    if worst > 1:
-        i = int(ratio.argmax())
-        raise AssertionError(f"{what}: element {i} (of shape {tuple(ref.shape)}) got {float(got.flatten()[i])!r}, ref {float(ref.flatten()[i])!r}, "
-                             f"bound {float(bound.flatten()[i]):.3e}")
 
 
 def _bf16_bound(ref, S, K):
@@ -80,16 +45,6 @@ def _nhwc(t):
 
 def _bf(t):
     return t.to(torch.bfloat16)
-
-
-def _same_thrice(what, run, grow):
-    """run() -> tensor; grow() runs the op at a larger shape (its workspace slot grows); the first and the third result are bit-identical."""
-    a = run().clone()
-    grow()
-    b = run()
-    torch.cuda.synchronize()
-    assert torch.equal(a.view(torch.uint8) if a.dtype != torch.uint8 else a, b.view(torch.uint8) if b.dtype != torch.uint8 else b), \
-        f"{what}: not bit-identical after the workspace grew"
 
 
 # ---------------------------------------------------------------------------------------------- convolutions
