@@ -45,6 +45,7 @@ ALL_TAPS = ["model.0", "model.1", "model.2.cv1", "model.2.m.0.cv1", "model.2.m.0
             "model.13.cv2", "model.16.cv2", "model.17", "model.19.cv2", "model.20", "model.22.cv2",
             "model.23.cv2.0.1", "model.23.cv3.0.0.0", "model.23.cv3.0.1.1", "model.23.cv4.2.1"]
 def test_layer_taps_match_bf16_oracle(ops, net_n):
+    # (statistical, unfused plan only: test_gpu_forward_elems.py checks every element per group of each plan against fp64 bounds)
     x = _tiles(1, 2, 416, 416)
     taps = {}
     net_n.forward_raw(x, net_n.prec, taps)

@@ -1,0 +1,199 @@
+"""Every forward kernel, per element, against fp64 from its own inputs (forward_ref.py: reference and bound derivation).
+
+Per case: load the model, run ONE ops.forward with the head in a guarded buffer, read back every tensor ops.debug_activation knows in that
+plan, and check every group -- the smallest piece of the graph between observable tensors -- with forward_ref.check_group: |got - fp64| <= E
+for EVERY element, E derived from fp32 accumulation and the 16-bit stores inside the group.  The union of the conv records inside checked
+groups must be all 96, with the attention core, the three SPPF pools, both upsample + concat reads and all 77 head columns of all three
+levels inside checked groups.  Then the forward runs again on a side stream (hipGraph capture + launch): bit-identical head, and the
+worst group of the first run is checked again.
+
+Measured margins (worst |err| / bound over all 25 cases, MI355X; every group prints its own with -s):
+  f16   single-layer groups 0.996 (model.10.m.0.attn.pe), 0.994 (model.23.cv3.1.1.0); multi-layer 0.918 (upsample + concat -> model.16.cv1)
+  bf16  single-layer groups 0.996 (model.10.m.0.attn.pe), 0.995 (model.23.cv3.2.0.0); multi-layer 0.976 (upsample + concat -> model.16.cv1)
+  f32   single-layer groups 0.354 (model.10.m.0.attn.pe);                             multi-layer 0.040 (DW -> model.23.cv3.0.0.1)
+In the 16-bit modes the single-layer groups are within 2x of their bound, and have to be: the store term u16 |a| is ATTAINED by
+round-to-nearest (a value just above a power of two sits u16 |a| from its neighbours), so a correct kernel reaches ~1.0 and anything
+beyond one rounding fails.  The fp32 path sits lower because gamma_K is a worst case over K roundings.
+
+Groups with hidden layers are much coarser, and what they catch should not be overstated.  Their worst-case E grows about 30x per hidden
+3x3 layer (1e3 .. 1e4 on values of 0.25 behind the six hidden layers of c3kimg.hip: vacuous), so they use the smaller of E and the
+statistical bound LAM s of forward_ref.py (independent mean-zero roundings, Hoeffding, LAM = 8; not a proof).  Median bound measured,
+in units of one rounding u16 |median ref|: front (model.2.cv1 from the tile) 23 .. 24, Bottleneck + closing 1x1 about 15, the seven-conv
+C3k of c3kimg.hip 30 .. 35 -- that is 1.1 % / 1.5 .. 1.7 % of the median magnitude in f16 and 9.5 % / 12 .. 13 % in bf16; measured
+|err| / bound there 0.18 .. 0.24.  A zeroed tap, a dropped bias of usual size or a swapped channel fails these groups
+(test_forward_ref_cpu.py, c3k group included); an error of a few units in the last place inside a fused group does NOT: for that
+resolution the per-layer comparison stays with the tail=False cases here (same packing routines, separate kernels) and with the
+device-versus-device tests of test_gpu_forward.py.  group_bound refuses (assertion) any group whose median bound exceeds half the median
+magnitude, so a group whose bound says nothing cannot count towards the 96."""
+import numpy as np
+import pytest
+import torch
+
+import bounds
+import forward_ref as fr
+from oracle.yolo11_obb import Yolo11OBB
+
+pytestmark = pytest.mark.gpu
+
+_MODELS = {}
+
+
+def _model(scale, ch):
+    if (scale, ch) not in _MODELS:
+        _MODELS[scale, ch] = Yolo11OBB(scale, nc=12, ch=ch, seed=0)
+    return _MODELS[scale, ch]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available()
+    import oriented_object_detection_amd  # noqa: F401
+    from oriented_object_detection_amd import ops as o
+    return o
+
+
+# Named tensors that are overwritten in place by the time the forward returns.  A tabled name is used neither as input nor as output: the
+# groups around it extend across it with propagated E.  (engine.hip, Builder)
+#   model.10.cv1 (b half), model.10.m.0.attn.proj
+#       build(): `conv(nm + ".attn.proj", whole(po), H32, W32, bsl, bsl);  // x = x + attn(x), in place on the b half` and
+#                `conv(nm + ".ffn.1", whole(ff), H32, W32, bsl, bsl);      // x = x + ffn(x)`: the b half of psa.ab is written by cv1, by
+#       attn.proj and by ffn.1; only the last (ffn.1) survives.  The a half is read back as "model.10.a".
+#   <C3k>.cv1 where cv1|cv2 run as one merged launch
+#       c3k(): "cv1 and cv2 read the same tensor: one launch writes [a | b]; the last Bottleneck later overwrites the (then dead) `a`
+#       member, so the same buffer is cv3's concat input."  (<C3k>.m.1.cv2 is that same slot and is what survives.)
+STALE_ALWAYS = ("model.10.cv1", "model.10.m.0.attn.proj")
+C3K_BLOCKS = ("model.6.m.0", "model.8.m.0", "model.22.m.0")
+
+
+def _stale(plan):
+    return set(STALE_ALWAYS) | {b + ".cv1" for b in C3K_BLOCKS if any(f"{b}.cv1|{b}.cv2" in l for l in plan)}
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).double().cpu()
+
+
+def _read(ops, m, name, B, h, w):
+    """debug_activation(name) as an NCHW fp64 tensor in the oracle's channel order, or None where the plan has no such tensor"""
+    from oriented_object_detection_amd import _lib
+    try:
+        t = _nchw(ops.debug_activation(name, B, h, w))
+    except _lib.ObbHipError as e:
+        if "no activation named" not in str(e):  # any other failure must not pass for "hidden" and silently merge groups
+            raise
+        return None
+    if name.endswith(".attn.qkv"):  # device order [q heads | k heads | v heads]
+        nh = m.psa_heads
+        hd = m.psa_c // nh
+        o = torch.empty_like(t)
+        o[:, fr.qkv_device_order(nh, hd // 2, hd)] = t
+        t = o
+    return t
+
+
+def _head_obs(m, head, h, w):
+    """head [B, A, >= 77] -> the nine final convs' outputs, NCHW"""
+    obs, off = {}, 0
+    for i, s in enumerate((8, 16, 32)):
+        H, W = h // s, w // s
+        t = _nchw(head[:, off:off + H * W, :77].reshape(head.shape[0], H, W, 77))
+        off += H * W
+        for n, c in zip(fr.head_names(i), ((0, 64), (64, 64 + m.nc), (64 + m.nc, 65 + m.nc))):
+            obs[n] = t[:, c[0]:c[1]]
+    assert off == head.shape[1]
+    return obs
+
+
+def _observe(ops, m, plan, head, x, B, h, w):
+    stale = _stale(plan)
+    obs = {"tile": x}
+    for name in list(m.convs) + [f"model.10.m.{i}.attn" for i in range(m.psa_n)]:
+        t = _read(ops, m, name, B, h, w)
+        if t is None:
+            continue
+        if name == "model.10.cv1":
+            obs["model.10.a"] = t[:, :m.psa_c]
+        if name not in stale:
+            obs[name] = t
+    obs.update(_head_obs(m, head.cpu(), h, w))
+    return obs
+
+
+def _assert_fused_forms(plan, h, w):
+    """the default plan of the n model really contains the fused forms this file is meant to cover, each where the shape admits it"""
+    has = lambda f: any(f(l) for l in plan)
+    if (h, w) in ((416, 416), (128, 128)):
+        assert sum(l.startswith("bneck ") and ".m.0+model." in l for l in plan) == 3, plan
+        assert sum(l.startswith("dwpw ") for l in plan) == 4, plan
+    if (h, w) == (416, 416):
+        assert sum(l.startswith("c3kimg ") for l in plan) == 2, plan
+        assert has(lambda l: "CK64" in l and "cv2.0.0" in l), plan
+        assert has(lambda l: "model.23.cv2.0.0|model.23.cv4.0.0" in l and "cout80" in l), plan
+    if (h, w) == (128, 128):
+        assert has(lambda l: " NI4 " in l), plan
+
+
+CASES = [(p, True, "n", 3, h, w, B) for p in ("f16", "bf16") for (h, w, B) in ((416, 416, 3), (128, 128, 70), (416, 288, 2), (192, 416, 2), (64, 96, 3), (832, 416, 1))] + \
+        [(p, False, "n", 3, h, w, B) for p in ("f16", "bf16") for (h, w, B) in ((416, 416, 2), (128, 128, 5))] + \
+        [("f16", True, "n", 4, 416, 416, 2), ("f16", True, "s", 3, 128, 160, 2), ("f16", True, "s", 3, 416, 416, 1)] + \
+        [("f32", True, "n", ch, h, w, B) for ch in (3, 4) for (h, w, B) in ((416, 416, 2), (128, 128, 5), (64, 96, 3))]
+
+
+@pytest.mark.parametrize("prec,tail,scale,ch,h,w,B", CASES, ids=lambda v: str(v))
+def test_every_group_per_element(ops, prec, tail, scale, ch, h, w, B):
+    m = _model(scale, ch)
+    ops.model_load(m.to_blob(), precision=prec, tail=tail)
+    try:
+        plan = ops.debug_plan(h, w)
+        label = f"{prec} {'default' if tail else 'tail=False'} {scale} ch{ch} {h}x{w} B{B}: "
+        if tail and scale == "n" and ch == 3 and prec != "f32":
+            _assert_fused_forms(plan, h, w)
+        if tail and prec != "f32" and scale == "n" and h % 52 == 0 and w % 52 == 0:
+            assert any(l.startswith("front model.0+model.1+model.2.cv1") for l in plan), plan
+        if not tail:
+            assert not any(l.startswith(("bneck ", "c3kimg ", "dwpw ", "front ")) or "+model." in l for l in plan), plan
+        x = np.random.default_rng(1000 + h + w + B).integers(0, 256, (B, h, w, ch), dtype=np.uint8)
+        xd = torch.as_tensor(x).cuda()
+        info = ops.model_info(h, w)
+        g = bounds.Guarded((B, info["anchors"], 80), torch.float32)
+        ops.forward(xd, out=g.out)
+        torch.cuda.synchronize()
+        assert g.guards_intact(), label + "write outside the head tensor"
+        head = g.out.clone()
+        assert bool(torch.isfinite(head[..., :77]).all()), label + "head element not written or not finite"
+
+        obs = _observe(ops, m, plan, head, x, B, h, w)
+        ev = fr.Evaluator(m, prec, obs)
+        outputs = [k for k in obs if k != "tile"]
+        ratios, covered = fr.check_all(ev, outputs, label=label)
+        # coverage is asserted, not assumed
+        assert len(m.convs) == 96 and {c for c in covered if c in m.convs} == set(m.convs), set(m.convs) - covered
+        assert {"attn:model.10.m.0.attn", "up:up13", "up:up16", "pool:model.9.pool0", "pool:model.9.pool1", "pool:model.9.pool2"} <= covered, covered
+        assert all(n in ratios for i in range(3) for n in fr.head_names(i))
+        if not tail:  # every layer observable: nothing but the tabled in-place tensors is missing
+            assert set(m.convs) - set(obs) == _stale(plan), set(m.convs) - set(obs)
+        worst = max(ratios, key=ratios.get)
+        print(f"{label}{len(outputs)} groups, worst ratio {ratios[worst]:.3f} at {worst}", flush=True)
+
+        # replay: the second sighting of (batch, tiles, head) on a side stream is where the engine captures a hipGraph and launches it.
+        # (NOT verified here that the graph path was taken: the engine falls back to eager launches silently if capture or instantiation
+        #  fails and exposes no counter; test_hipgraph_capture_and_replay has the same limit.  Either way the head must be identical.)
+        g.raw.fill_(0xFF)
+        st = torch.cuda.Stream()
+        st.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(st):
+            ops.forward(xd, out=g.out)
+        st.synchronize()
+        torch.cuda.synchronize()
+        assert g.guards_intact(), label + "replay: write outside the head tensor"
+        assert torch.equal(g.out.view(torch.int32), head.view(torch.int32)), label + "replay: head not bit-identical"
+        if fr.is_head(worst):
+            again = _head_obs(m, g.out.cpu(), h, w)[worst]
+        elif worst == "model.10.a":
+            again = _read(ops, m, "model.10.cv1", B, h, w)[:, :m.psa_c]
+        else:
+            again = _read(ops, m, worst, B, h, w)
+        ref, E, _ = ev.node(worst)
+        fr.check_group(label + "replay " + worst, again, ref, E)
+    finally:
+        ops.model_load(m.to_blob())
