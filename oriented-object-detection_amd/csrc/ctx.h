@@ -13,7 +13,7 @@
 #include "../../include/obbhip.h"
 
 namespace obb {
-struct Model;  // engine.hip
+struct Model;  // plan.h
 // obb_set_option switches of the forward engine.  Every fused form keeps a switch that restores its separate launches: the A/B parity
 // tests compare the two on identical inputs.  graph / fwd_split / microbatch steer how a forward is issued (their defaults may be
 // preset from the environment for profiling runs: OBB_GRAPH, OBB_FWD_SPLIT, OBB_MICROBATCH -- read once per context).

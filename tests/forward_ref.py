@@ -177,7 +177,7 @@ def is_head(name):
 
 
 def qkv_device_order(nh, kd, hd):
-    """device channel c of the qkv tensor holds oracle channel perm[c]: [q heads | k heads | v heads] (engine.hip, C2PSA)"""
+    """device channel c of the qkv tensor holds oracle channel perm[c]: [q heads | k heads | v heads] (netplan.hip, Builder::build, C2PSA)"""
     return [h * (2 * kd + hd) + d for h in range(nh) for d in range(kd)] + [h * (2 * kd + hd) + kd + d for h in range(nh) for d in range(kd)] + \
            [h * (2 * kd + hd) + 2 * kd + d for h in range(nh) for d in range(hd)]
 

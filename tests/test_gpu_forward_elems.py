@@ -53,7 +53,7 @@ def ops():
 
 
 # Named tensors that are overwritten in place by the time the forward returns.  A tabled name is used neither as input nor as output: the
-# groups around it extend across it with propagated E.  (engine.hip, Builder)
+# groups around it extend across it with propagated E.  (netplan.hip, Builder)
 #   model.10.cv1 (b half), model.10.m.0.attn.proj
 #       build(): `conv(nm + ".attn.proj", whole(po), H32, W32, bsl, bsl);  // x = x + attn(x), in place on the b half` and
 #                `conv(nm + ".ffn.1", whole(ff), H32, W32, bsl, bsl);      // x = x + ffn(x)`: the b half of psa.ab is written by cv1, by
