@@ -1,0 +1,225 @@
+"""The post-processing kernels of csrc/decode.hip against the fp64 reference of postproc_ref.py (written from the Ultralytics semantics,
+not from the kernels; test_postproc_ref_cpu.py checks the reference, its mutations and the inputs without a GPU).
+
+  decode        k_decode into a guarded buffer, EVERY element within E of fp64 (E: counted fp32 roundings + 4 ulp of libm, never below the
+                spread floor), nc in {1, 4, 12, 15, 16, 17, 80} (row widths 68 .. 148) at 64x96, 128x128, 416x288, 832x416, DFL logits to
+                +-60, one-hot / uniform rows, saturated angles; padding columns NaN against +1e30: bit-identical output.
+  decode + NMS  decision-exact: on inputs that the reference proves fully decided (one correct output), counts equal and every row equals the
+                reference's row at the same position -- cls exact, box / theta / conf within their decode bound -- for obb_decode_nms,
+                the full form and (nc <= 16) the cmax gate; guarded outputs, rows past count untouched.  nc in {1, 12, 16, 17, 80}
+                (k_cand_nms<false> for 17 and 80) x conf {0.25, 0.6, 0.001} x iou {5e-4, 0.1, 0.45, 0.7, 0.9} x max_det {5, 40, 300} on
+                128x128 images of 0, 1, 40, 256, 257 and 330 candidates (k_heavy_prep + k_heavy_rows above 256, the round form at conf
+                0.001), with tie blocks of bit-identical rows; 640x640 with 1500 candidates (k_heavy_sort / k_heavy_nms / k_heavy_out);
+                416x416, B = 2; the class mask (angle logit +50, padding +1e30) for nc in {1, 4, 12, 15}.
+  probiou_nms   n in {1, 2, 65, 257} at the five thresholds, order and keep flags exact.
+  results       per element against fp64 with a derived bound, angles on both sides of 0 and pi / 2; undecided swap rows dropped.
+
+Measured on MI355X, worst |err| / E of decode per nc (every case prints its own with -s):
+  nc 1: 0.487   4: 0.424   12: 0.435   15: 0.417   16: 0.445   17: 0.451   80: 0.554
+The kept rows of the NMS cases are held to the same per-element bound (each test prints its worst ratio).  Decided margin of the tightest pair per threshold (|iou64 - thr| / floor, must exceed MARGIN =
+8; the committed redraw table was searched at 8.4; make_postproc_attempts.py prints them): 5e-4: 8.99, 0.1: 8.56, 0.45: 8.41,
+0.7: 8.58, 0.9: 9.34.
+
+What this does not prove: decisions inside the undecided band (|iou - thr| <= 8 floors, about 1e-5) stay with the bit-exact comparison
+against the fp32 oracle in test_gpu_postproc.py; boxes below 1 px and nc > 80 are out of scope (every box here is above 4 px: the
+far-apart bound of decode.hip assumes the log term of the Bhattacharyya distance >= 0, which holds only there)."""
+import contextlib
+
+import pytest
+import torch
+
+import bounds
+import postproc_ref as R
+from oracle.yolo11_obb import Yolo11OBB
+
+pytestmark = pytest.mark.gpu
+
+_BLOBS = {}
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available()
+    import oriented_object_detection_amd  # noqa: F401
+    from oriented_object_detection_amd import ops as o
+    return o
+
+
+def _blob(nc):
+    if nc not in _BLOBS:
+        _BLOBS[nc] = Yolo11OBB("n", nc=nc, ch=3, seed=0).to_blob()
+    return _BLOBS[nc]
+
+
+@contextlib.contextmanager
+def _model(ops, nc):
+    """nc comes from the loaded model (its weights are irrelevant here); the module's default is restored afterwards"""
+    ops.model_load(_blob(nc))
+    try:
+        yield
+    finally:
+        ops.model_load(_blob(12))
+
+
+def _pad(head, nc, value):
+    hd = head.clone()
+    hd[..., 64 + nc + 1:] = value
+    return hd.cuda()
+
+
+@pytest.mark.parametrize("nc", [1, 4, 12, 15, 16, 17, 80])
+def test_decode_every_element_within_the_derived_bound(ops, nc):
+    worst = 0.0
+    with _model(ops, nc):
+        for h, w in ((64, 96), (128, 128), (416, 288), (832, 416)):
+            head = R.decode_inputs(h, w, nc, seed=h + nc)
+            assert ops.model_info(h, w)["anchors"] == head.shape[1] and head.shape[2] == R.no_of(nc)
+            ref, E = R.decode_bounds(head, h, w, nc)
+            outs = []
+            for fill in (float("nan"), 1e30):
+                g = bounds.Guarded(tuple(ref.shape), torch.float32)
+                torch.ops.obbhip.decode(_pad(head, nc, fill), h, w, g.out)
+                outs.append(g.get(f"decode nc {nc} {h}x{w}"))
+            assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "the padding columns leak into the output"
+            got = outs[0].double().cpu()
+            r = (got - ref).abs() / E
+            print(f"  decode nc {nc} {h}x{w}: worst |err| / E  box {float(r[..., :4].max()):.3f}  cls {float(r[..., 4:4 + nc].max()):.3f}  theta {float(r[..., -1].max()):.3f}")
+            worst = max(worst, float(r.max()))
+            bounds._check(f"decode nc {nc} {h}x{w}", got, ref, E)
+    print(f"  decode nc {nc}: worst |err| / E = {worst:.3f}")
+
+
+def _row_bounds(E, c, kept, nc):
+    a = c.anchor[kept]
+    return torch.cat([E[a, :4], E[a, 4:4 + nc].gather(1, c.cls[kept, None]), torch.zeros(len(a), 1, dtype=torch.float64), E[a, 4 + nc:]], 1)
+
+
+def _run_form(form, hd, cmax, h, w, conf, thr, md):
+    B = hd.shape[0]
+    det, cnt = bounds.Guarded((B, md, 7), torch.float32), bounds.Guarded((B,), torch.int32)
+    O = torch.ops.obbhip
+    if form == "cmax":
+        O.decode_nms_gate(hd, cmax, h, w, float(conf), float(thr), int(md), det.out, cnt.out)
+    else:
+        (O.decode_nms_full if form == "full" else O.decode_nms)(hd, h, w, float(conf), float(thr), int(md), det.out, cnt.out)
+    torch.cuda.synchronize()
+    assert det.guards_intact() and cnt.guards_intact(), f"{form}: write outside the output"
+    return det.out.cpu(), cnt.out.cpu()
+
+
+def _check_rows(what, det, cnt, cases, E, nc, thr, md):
+    worst = 0.0
+    for b, c in enumerate(cases):
+        rows, kept, _ = R.nms_run(c, thr, md)
+        n = int(cnt[b])
+        assert n == len(kept), f"{what} image {b}: count {n}, reference {len(kept)}"
+        assert bool((det[b, n:].contiguous().view(torch.int32) == -1).all()), f"{what} image {b}: a row past count was written"
+        if not n:
+            continue
+        got = det[b, :n].double()
+        assert torch.equal(got[:, 5].long(), c.cls[kept]), f"{what} image {b}: classes {got[:, 5].long().tolist()} != {c.cls[kept].tolist()}"
+        Eb = _row_bounds(E[b], c, kept, nc)
+        d = (got - rows).abs()
+        ok = d <= Eb
+        if not bool(ok.all()):
+            i, k = [int(v) for v in torch.nonzero(~ok)[0]]
+            raise AssertionError(f"{what} image {b}: row {i} column {k}: got {float(got[i, k])!r}, reference {float(rows[i, k])!r} (anchor "
+                                 f"{int(c.anchor[kept[i]])}), bound {float(Eb[i, k]):.3e}")
+        worst = max(worst, float((d / Eb.clamp_min(1e-300)).max()))
+    return worst
+
+
+def _nms_against_reference(ops, syn, cases, thresholds, max_dets, fill=float("nan")):
+    nc, h, w = syn.nc, syn.h, syn.w
+    head = syn.tensor()
+    _, E = R.decode_bounds(head, h, w, nc)
+    hd = _pad(head, nc, fill)
+    cmax = hd[..., 64:64 + nc].amax(-1).contiguous()
+    ncand = (torch.sigmoid(hd[..., 64:64 + nc]).amax(-1) > R.f32v(syn.conf)).sum(1).cpu().tolist()
+    assert ncand == [c.n for c in cases], (ncand, [c.n for c in cases])
+    worst = 0.0
+    with _model(ops, nc):
+        for thr in thresholds:
+            for md in max_dets:
+                for form in ("default", "full") + (("cmax",) if nc <= 16 else ()):
+                    det, cnt = _run_form(form, hd, cmax, h, w, syn.conf, thr, md)
+                    worst = max(worst, _check_rows(f"{form} nc {nc} conf {syn.conf} iou {thr} max_det {md}", det, cnt, cases, E, nc, thr, md))
+    print(f"  nc {nc} conf {syn.conf}: candidates per image {ncand}, worst row |err| / E = {worst:.3f}")
+    return ncand
+
+
+@pytest.mark.parametrize("conf", R.NMS_CONF)
+@pytest.mark.parametrize("nc", R.NMS_NC)
+def test_decode_nms_rows_equal_the_reference(ops, nc, conf):
+    """k_cand_nms<true> (nc <= 16) / <false> (17, 80) up to 256 candidates; above: k_heavy_prep + k_heavy_rows (conf >= 0.05; the histogram
+    cut of k_heavy_rows where the survivors of the 330-candidate image exceed max_det 5 and 40) or the round form (conf 0.001)"""
+    syn, cases = R.nms_matrix_case(nc, conf)
+    ncand = _nms_against_reference(ops, syn, cases, R.THRESHOLDS, R.NMS_MAX_DET)
+    assert ncand == list(R.NMS_TILES) and 256 in ncand and 257 in ncand and max(ncand) > 257
+    assert len(R.nms_run(cases[-1], 0.7, 300)[1]) > 40
+
+
+def test_decode_nms_three_kernel_form_640(ops):
+    """8400 anchors do not fit the LDS of k_heavy_rows: k_heavy_sort / k_heavy_nms / k_heavy_out finish the 1500-candidate image"""
+    syn, cases, thr = R.big_case("640")
+    ncand = _nms_against_reference(ops, syn, cases, thr, (300, 40))
+    assert ncand[0] > 256 and syn.A == 8400 and ((syn.A + 3) // 4 * 4) * 37 + 16416 > 156 * 1024
+
+
+def test_decode_nms_lds_resident_form_416(ops):
+    syn, cases, thr = R.big_case("416")
+    ncand = _nms_against_reference(ops, syn, cases, thr, (300, 40))
+    assert min(ncand) > 256 and ((syn.A + 3) // 4 * 4) * 37 + 16416 <= 156 * 1024
+
+
+@pytest.mark.parametrize("nc", [1, 4, 12, 15])
+def test_angle_logit_and_padding_stay_out_of_the_class_maximum(ops, nc):
+    """class_best loads whole float4s: the lanes past nc hold the angle logit (+50 here, above every class logit) and the padding
+    (+1e30): neither may become the confidence or the class"""
+    syn, cases = R.mask_case(nc)
+    assert float(syn.head[..., 64:64 + nc].max()) < 50.0
+    _nms_against_reference(ops, syn, cases, R.MASK_THR, (300,), fill=1e30)
+
+
+def test_first_of_two_bit_identical_class_maxima_is_the_class(ops):
+    syn, cases = R.dup_max_case()
+    lg = torch.from_numpy(syn.head[..., 64:76])
+    top = torch.topk(lg, 2, -1).values
+    assert int(((top[..., 0] == top[..., 1]) & (top[..., 0] > 0)).sum()) >= 10
+    _nms_against_reference(ops, syn, cases, R.THRESHOLDS, (300,))
+
+
+@pytest.mark.parametrize("n", [1, 2, 65, 257])
+def test_probiou_nms_list_decisions_equal_the_reference(ops, n):
+    _, cases = R.nms_matrix_case(1, 0.25)  # (class 0 only: no offset, whose fp32 rounding would be an input error here)
+    src = cases[-1]
+    box32 = src.box[:n].float()
+    box32[:, :2] += src.cls[:n, None].float() * R.MAX_WH           # the list kernel takes offset boxes
+    s32 = torch.flip(src.conf[:n].float(), (0,)).contiguous()     # ascending scores: the kernel has to sort
+    box32 = torch.flip(box32, (0,)).contiguous()
+    c = R.list_case(box32, s32)
+    assert not torch.equal(c.order, torch.arange(n)) or n == 1
+    for thr in R.THRESHOLDS:
+        assert R.pair_report(c, thr)["n_und_pairs"] == 0
+        _, kept, _ = R.nms_run(c, thr, n)
+        exp = torch.zeros(n, dtype=torch.uint8)
+        exp[kept] = 1
+        order, keep = ops.probiou_nms(box32.cuda(), s32.cuda(), thr)
+        assert torch.equal(order.cpu().long(), c.order), (n, thr)
+        assert torch.equal(keep.cpu(), exp), (n, thr, torch.nonzero(keep.cpu() != exp)[:, 0].tolist())
+
+
+@pytest.mark.parametrize("letterbox", [False, True])
+def test_results_every_element_within_the_derived_bound(ops, letterbox):
+    det = R.results_rows()
+    n = det.shape[0]
+    lb = None
+    if letterbox:
+        p = ops.letterbox_shape(175, 263, 416)
+        lb = torch.tensor([[p["gain"], p["pad_x"], p["pad_y"]]], dtype=torch.float32).repeat(n, 1)
+    xywhr, pts, Ex, Ep, dec = R.results64(det, lb)
+    assert int((~dec).sum()) == 2  # theta = 0 and theta = fp32(pi / 2): on a boundary, dropped
+    gx, gp = bounds.Guarded((n, 5), torch.float32), bounds.Guarded((n, 8), torch.float32)
+    torch.ops.obbhip.results(det.cuda(), None if lb is None else lb.cuda(), gx.out, gp.out)
+    bounds._check("results xywhr", gx.get("results xywhr")[dec.cuda()], xywhr[dec], Ex[dec])
+    bounds._check("results corners", gp.get("results corners")[dec.cuda()], pts[dec], Ep[dec])
