@@ -228,6 +228,29 @@ int obb_bn_silu_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t 
                          float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, obb_stream_t s);
 int obb_bn_silu_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
                          const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, obb_stream_t s);
+/* Gradient routing through what is not a convolution (`model.train(...)`, Train_OBB.py:796-841 -> ultralytics SPPF / nn.Upsample / Concat:
+ * yolo11 models 9, 11/12, 14/15, 18, 21), bf16 NHWC device tensors, channel counts multiples of 8 (>= 8), B, H, W >= 1.  No atomics, fixed
+ * summation order (bit-reproducible), no workspace.
+ * obb_sppf_pools_fwd_bf16: cat[B][H][W][4C] = [x, y1, y2, y3], y_k = maxpool5x5(y_{k-1}), y0 = x[B][H][W][C] (stride 1, pad 2, padding never
+ *   wins); one launch, the map of a workgroup's channels resident in LDS: H <= 32 and W <= 32, larger maps are OBB_ERR_INVALID.  Values are
+ *   copied, not re-rounded: bit-equal to F.max_pool2d on the same bf16 values.
+ * obb_sppf_pools_bwd_bf16: dx[B][H][W][C] from cat and dcat[B][H][W][4C] alone.  The argmax of level k is recomputed from member k - 1 of cat
+ *   as the first maximum of a row-major scan of the window (strict >, torch's rule); gather form, level 3 -> 1, fp32 sums in LDS, the dcat
+ *   member of each level added there, one bf16 rounding at the store.
+ *   Both pool kernels require FINITE inputs (SiLU outputs are): on those the selection is torch's.  A NaN is not propagated (torch's scan has
+ *   an isnan clause) and a window that is all -inf passes no gradient (torch sends it to the window's first element).
+ * obb_upcat_fwd_bf16: out[B][up H][up W][Ca + Cb] = cat(nearest_upsample_up(a[B][H][W][Ca]), b[B][up H][up W][Cb]) along C, a first
+ *   (Ultralytics' Concat([-1, skip])), up in {1, 2}; up = 1 is the plain concat.  Bit-exact copies.
+ * obb_upcat_bwd_bf16: da[p] = the sum of the up^2 elements of dout[..., :Ca] that p was copied to (fp32, dy then dx, one bf16 rounding),
+ *   db = dout[..., Ca:].  accum_a / accum_b = 1: the existing bf16 value of da / db is read and added in fp32 before the one rounding (the
+ *   gradient sum of a tensor with two consumers).  da or db NULL: that half is skipped. */
+int obb_sppf_pools_fwd_bf16(obb_ctx *ctx, const uint16_t *x, int32_t B, int32_t H, int32_t W, int32_t C, uint16_t *cat, obb_stream_t s);
+int obb_sppf_pools_bwd_bf16(obb_ctx *ctx, const uint16_t *cat, const uint16_t *dcat, int32_t B, int32_t H, int32_t W, int32_t C, uint16_t *dx,
+                            obb_stream_t s);
+int obb_upcat_fwd_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int32_t B, int32_t H, int32_t W, int32_t Ca, int32_t Cb, int32_t up,
+                       uint16_t *out, obb_stream_t s);
+int obb_upcat_bwd_bf16(obb_ctx *ctx, const uint16_t *dout, int32_t B, int32_t H, int32_t W, int32_t Ca, int32_t Cb, int32_t up, uint16_t *da,
+                       uint16_t *db, int32_t accum_a, int32_t accum_b, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S1: model(...) -> results[0].obb  (Detect_OBB.py:26,81-83,228-231) */
 /* Weight blob ("OBBW" format, produced by the Python side from BN-folded conv weights) for a

@@ -54,6 +54,10 @@ SIGNATURES = {
     "obb_conv_wgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_bn_silu_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, _V],
     "obb_bn_silu_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V],
+    "obb_sppf_pools_fwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_sppf_pools_bwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_upcat_fwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_upcat_bwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32, C.c_int32, _V],
     "obb_gather_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V, _V],
     "obb_letterbox": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V,
                       C.c_int32, C.c_int32, _V],

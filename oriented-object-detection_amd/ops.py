@@ -258,6 +258,30 @@ def _bn_silu_bwd(z: T, da: T, gamma: T, beta: T, mean: T, invstd: T, dgamma: T, 
           _stream())
 
 
+@_op("sppf_pools_fwd", ("cat",))
+def _sppf_pools_fwd(x: T, cat: T) -> None:
+    B, H, W, C = x.shape
+    _call("obb_sppf_pools_fwd_bf16", ctx(x.device), _p(x), B, H, W, C, _p(cat), _stream())
+
+
+@_op("sppf_pools_bwd", ("dx",))
+def _sppf_pools_bwd(cat: T, dcat: T, dx: T) -> None:
+    B, H, W, C = dx.shape
+    _call("obb_sppf_pools_bwd_bf16", ctx(cat.device), _p(cat), _p(dcat), B, H, W, C, _p(dx), _stream())
+
+
+@_op("upcat_fwd", ("out",))
+def _upcat_fwd(a: T, b: T, up: int, out: T) -> None:
+    B, H, W, Ca = a.shape
+    _call("obb_upcat_fwd_bf16", ctx(a.device), _p(a), _p(b), B, H, W, Ca, b.shape[-1], int(up), _p(out), _stream())
+
+
+@_op("upcat_bwd", ("da", "db"))
+def _upcat_bwd(dout: T, H: int, W: int, Ca: int, up: int, da: Optional[T], db: Optional[T], accum_a: bool, accum_b: bool) -> None:
+    _call("obb_upcat_bwd_bf16", ctx(dout.device), _p(dout), dout.shape[0], int(H), int(W), int(Ca), dout.shape[-1] - int(Ca), int(up), _p(da), _p(db),
+          int(accum_a), int(accum_b), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -555,6 +579,67 @@ def bn_silu_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None):
     dz = torch.empty_like(zz)
     _O.bn_silu_bwd(zz, d, *vecs, dg, db, dz)
     return dz, dg, db
+
+
+def sppf_pools_fwd_bf16(x):
+    """The three chained 5x5 max pools of SPPF (stride 1, pad 2): x bf16 [B,H,W,C] -> cat bf16 [B,H,W,4C] = [x, y1, y2, y3], bit-equal to
+    F.max_pool2d on the same values.  H, W <= 32 (the map of a workgroup's channels is resident in LDS)."""
+    xx = _chk(x, torch.bfloat16, "x")
+    if xx.dim() != 4:
+        raise ValueError("sppf_pools_fwd_bf16: x must be [B,H,W,C]")
+    B, H, W, Cn = xx.shape
+    cat = torch.empty((B, H, W, 4 * Cn), dtype=torch.bfloat16, device=xx.device)
+    _O.sppf_pools_fwd(xx, cat)
+    return cat
+
+
+def sppf_pools_bwd_bf16(cat, dcat):
+    """Backward of sppf_pools_fwd_bf16 from cat and dcat (bf16 [B,H,W,4C]) alone -> dx bf16 [B,H,W,C]; the argmax is recomputed (first maximum
+    in row-major scan of the window, torch's rule), fp32 sums, one bf16 rounding."""
+    c, d = _chk(cat, torch.bfloat16, "cat"), _chk(dcat, torch.bfloat16, "dcat")
+    if c.dim() != 4 or c.shape != d.shape or c.shape[-1] % 4:
+        raise ValueError("sppf_pools_bwd_bf16: cat and dcat must both be [B,H,W,4C]")
+    B, H, W, C4 = c.shape
+    dx = torch.empty((B, H, W, C4 // 4), dtype=torch.bfloat16, device=c.device)
+    _O.sppf_pools_bwd(c, d, dx)
+    return dx
+
+
+def upcat_fwd_bf16(a, b, up=1):
+    """cat(nearest_upsample_up(a), b) along C, a first (Ultralytics' Concat([-1, skip])): a bf16 [B,H,W,Ca], b bf16 [B,up H,up W,Cb] ->
+    bf16 [B,up H,up W,Ca+Cb]; up = 1 is the plain concat."""
+    aa, bb = _chk(a, torch.bfloat16, "a"), _chk(b, torch.bfloat16, "b")
+    if aa.dim() != 4 or bb.dim() != 4 or up < 1 or tuple(bb.shape[:3]) != (aa.shape[0], aa.shape[1] * up, aa.shape[2] * up):
+        raise ValueError(f"upcat_fwd_bf16: a {tuple(aa.shape)} upsampled by {up} does not match b {tuple(bb.shape)}")
+    out = torch.empty((*bb.shape[:3], aa.shape[3] + bb.shape[3]), dtype=torch.bfloat16, device=aa.device)
+    _O.upcat_fwd(aa, bb, int(up), out)
+    return out
+
+
+def upcat_bwd_bf16(dout, Ca, up=1, da=None, db=None, need_da=True, need_db=True):
+    """Backward of upcat_fwd_bf16: dout bf16 [B,up H,up W,Ca+Cb] -> (da bf16 [B,H,W,Ca], db bf16 [B,up H,up W,Cb]).  A GIVEN da / db is
+    accumulated into (read, fp32 add, one rounding: the gradient sum of a tensor with two consumers); None allocates and overwrites.
+    need_da / need_db = False skips that half (None is returned for it)."""
+    d = _chk(dout, torch.bfloat16, "dout")
+    if d.dim() != 4 or up < 1 or d.shape[1] % up or d.shape[2] % up:
+        raise ValueError(f"upcat_bwd_bf16: dout {tuple(d.shape)} is not a map upsampled by {up}")
+    B, uH, uW, Co = d.shape
+    H, W, Cb = uH // up, uW // up, Co - int(Ca)
+    acc_a, acc_b = need_da and da is not None, need_db and db is not None
+    if need_da:
+        da = torch.empty((B, H, W, int(Ca)), dtype=torch.bfloat16, device=d.device) if da is None else _chk(da, torch.bfloat16, "da")
+        if tuple(da.shape) != (B, H, W, int(Ca)):
+            raise ValueError("upcat_bwd_bf16: da must be [B,H,W,Ca]")
+    else:
+        da = None
+    if need_db:
+        db = torch.empty((B, uH, uW, Cb), dtype=torch.bfloat16, device=d.device) if db is None else _chk(db, torch.bfloat16, "db")
+        if tuple(db.shape) != (B, uH, uW, Cb):
+            raise ValueError("upcat_bwd_bf16: db must be [B,up H,up W,Cb]")
+    else:
+        db = None
+    _O.upcat_bwd(d, H, W, int(Ca), int(up), da, db, acc_a, acc_b)
+    return da, db
 
 
 def silu_bf16(z):

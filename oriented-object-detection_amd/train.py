@@ -12,7 +12,9 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     contiguous, so a bucket is a view, not a copy; buckets of `bucket_mb` keep a ring all-reduce per-link bandwidth-bound rather than
     latency-bound (7 xGMI links x ~153 GB/s per GPU: a 25 MB bucket is ~0.1 ms of wire time per hop);
   * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
-    training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded."""
+    training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded;
+  * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
+    the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip)."""
 import math
 
 import torch
@@ -245,6 +247,49 @@ class ConvBN:
         """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32."""
         f = self.gamma / torch.sqrt(self.running_var + self.eps)
         return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+
+class SPPF:
+    """Ultralytics `SPPF(c1, c2, k=5)` (yolo11 model 9) in training mode: cv1 = Conv 1x1 (c1 -> c1 / 2), three chained 5x5 max pools (stride 1,
+    pad 2), cv2 = Conv 1x1 over cat([a1, y1, y2, y3]) (2 c1 -> c2).  cv1 / cv2: (w, gamma, beta[, running_mean, running_var]) of the two ConvBN
+    blocks, registered in `groups` in that order.  `forward` / `backward` follow ConvBN's contract; the only tensor kept for the pools' backward
+    is `cat` (cv2's input, kept for its wgrad anyway): the argmax is recomputed from it (csrc/routegrad.hip).  Maps up to 32 x 32."""
+
+    def __init__(self, groups, cv1, cv2, eps=1e-3, momentum=0.03):
+        mk = lambda t: ConvBN(groups, t[0], t[1] if len(t) > 1 else None, t[2] if len(t) > 2 else None, 1, t[3] if len(t) > 3 else None,
+                              t[4] if len(t) > 4 else None, eps, momentum)
+        self.cv1, self.cv2 = mk(cv1), mk(cv2)
+        if self.cv1.k != 1 or self.cv2.k != 1 or self.cv2.c1 != 4 * self.cv1.c2:
+            raise ValueError(f"SPPF: cv1 and cv2 are 1x1 convs with cv2 reading 4 x cv1's {self.cv1.c2} channels, got k = {self.cv1.k}, {self.cv2.k}, "
+                             f"cv2 c1 = {self.cv2.c1}")
+        self.cat = None
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
+        self.cat = ops.sppf_pools_fwd_bf16(self.cv1.forward(x))
+        return self.cv2.forward(self.cat)
+
+    def backward(self, da):
+        """da bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
+        return self.cv1.backward(ops.sppf_pools_bwd_bf16(self.cat, self.cv2.backward(da)))
+
+
+class UpCat:
+    """`nn.Upsample(scale_factor=up, mode="nearest")` + `Concat([-1, skip])` of the FPN (up = 2; yolo11 models 11/12, 14/15) or the plain
+    `Concat` of the PAN (up = 1; models 18, 21): forward(a, b) = cat(upsample(a), b) along C.  backward(dout, da, db) -> (da, db): a given
+    da / db already holds the gradient of that tensor's other consumer and is added to (fp32 add, one bf16 rounding); None allocates."""
+
+    def __init__(self, up=1):
+        if up not in (1, 2):
+            raise ValueError(f"UpCat: up = {up}: 1 (concat) or 2 (upsample + concat)")
+        self.up, self.ca = up, None
+
+    def forward(self, a, b):
+        self.ca = a.shape[-1]
+        return ops.upcat_fwd_bf16(a, b, self.up)
+
+    def backward(self, dout, da=None, db=None):
+        return ops.upcat_bwd_bf16(dout, self.ca, self.up, da=da, db=db)
 
 
 class DetectBoxBranchStep:
