@@ -66,6 +66,9 @@ const char *obb_last_error(const obb_ctx *ctx);
  *     "blk32"     (fp32) the tensors read by 3x3 convs in 8- / 16-channel stages stored as 8-channel blocks per image
  *     "c3k2f"     (fp32) Bottleneck + closing 1x1 of the 104 x 104 C3k2 block in one launch (k_c3k2_f32)
  *     "pw32"      (fp32) 1x1 layers with >= 64 input channels on k_pw_f32: weights resident in LDS, activations straight from global memory
+ *     "upacc"     (fp32, with "upfold") the 1x1 behind [Upsample x2 | skip] as two launches: the upsampled half's product once per COARSE pixel
+ *                 (raw accumulators), then the skip half at full resolution with its accumulators starting from it -- the same fma chain, bit
+ *                 for bit, without 3/4 of the upsampled half's multiply-adds
  *   issue of a forward (take effect at the next obb_forward): "graph" 1 = capture / replay hipGraphs (default), "fwd_split" 0..4
  *   concurrent sub-batch chains (default 0 = 2), "microbatch" 416 x 416 tiles per round (default and maximum 1024; smaller tiles
  *   get proportionally more per round, at most 16 384: 128 px -> 11 264). */
@@ -272,6 +275,12 @@ int obb_forward_gate(obb_ctx *ctx, const uint8_t *tiles, int32_t B, int32_t h, i
 /* Debug: text dump of the lowered forward for an (h, w) input -- one line per kernel launch (layer name, tiling,
  * grid, LDS bytes, MACs).  buf_host may be NULL to query *needed. */
 int obb_debug_plan(obb_ctx *ctx, int32_t h, int32_t w, char *buf_host, int64_t buf_bytes, int64_t *needed);
+/* Debug, host only (no context, no device): the packed fp32 weights of columns [c0, c0 + nc) of the 1x1 matrix w[cout][cin] exactly as the plan
+ * builder packs them.  form 0: k_pw_f32 order (the coarse launch of "upacc"), 1: the two-fragment k_conv_f32 order (its fine launch), 2: the
+ * order of the one-launch form over the whole virtual concat.  tiling_host (optional, forms 1 / 2): {channels per stage, waves along cout,
+ * cout fragments per wave}.  out may be NULL to query *needed (floats). */
+int obb_debug_pack_1x1(int32_t form, const float *w, int32_t cout, int32_t cin, int32_t c0, int32_t nc, float *out, int64_t max_floats,
+                       int64_t *needed, int32_t *tiling_host);
 /* Debug/parity tap: copy the activation called `name` (a conv's state-dict path such as "model.2.cv1", or a
  * layer output "x0".."x22") of the last forward to out as dense float[B*H*W*C] (bf16 widened).  out may be NULL to
  * query *n_elems / shape only. */

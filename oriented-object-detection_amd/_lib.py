@@ -67,6 +67,7 @@ SIGNATURES = {
     "obb_forward": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_forward_gate": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],
     "obb_debug_plan": [_V, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, c_lp],
+    "obb_debug_pack_1x1": [C.c_int32, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int64, c_lp, c_ip],
     "obb_debug_activation": [_V, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, _V, C.c_int64, c_lp, c_ip, _V],
     "obb_decode_nms": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _V, _V, _V],
     "obb_decode_nms_gate": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_int32, _V, _V, _V],
@@ -100,6 +101,8 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(SO_PATH)
         for name, argt in SIGNATURES.items():
+            if os.environ.get("OBB_LIB") and not hasattr(L, name):  # (an older diagnostic build may lack the newest entry points: A/B timing only)
+                continue
             fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly
             fn.argtypes = argt
             fn.restype = _RESTYPE.get(name, C.c_int)

@@ -136,6 +136,10 @@ static hipError_t launch_op(const Plan &P, const Model &M, const Op &op, const u
             // (a channel-blocked output is per image: the flattened pixel row of a 1-D launch is split back into (image, pixel))
             bind_conv(L, P, M, op, tiles, head, B, boff, op.one_d && op.out.buf >= 0 && P.bufs[op.out.buf].blk32 ? op.Ho * op.Wo : 0, true, !emit_cmax);
             if (emit_cmax) { L.cmax = cmax + P.lvl_off[op.head_level]; L.cmax_bs = P.A; }
+            if (op.upacc) {  // the skip member alone; the upsampled member's share arrives as the accumulators' initial value
+                L.in = L.in2; L.in2 = TensorRef(); L.up_c = 0;
+                L.acc_init = T(op.ini);
+            }
             return launch_conv32(L, st);
         }
         case OP_CONV: {
@@ -328,7 +332,7 @@ int obb_set_option(obb_ctx *ctx, const char *key, int64_t value) {
         struct { const char *key; bool *flag; } sw[] = {
             {"tail", &ctx->opt.tail}, {"tail16", &ctx->opt.tail16}, {"bneck", &ctx->opt.bneck}, {"bneck_cv2", &ctx->opt.bneck_cv2},
             {"c3kimg", &ctx->opt.c3kimg}, {"dwpw", &ctx->opt.dwpw}, {"upfold", &ctx->opt.upfold}, {"stem", &ctx->opt.stem}, {"front", &ctx->opt.front}, {"pair", &ctx->opt.pair},
-            {"hmerge", &ctx->opt.hmerge}, {"sppf_fuse", &ctx->opt.sppf_fuse}, {"attn_mfma", &ctx->opt.attn_mfma}, {"xtile", &ctx->opt.xtile}, {"nitile", &ctx->opt.nitile}, {"nc2", &ctx->opt.nc2}, {"blk32", &ctx->opt.blk32}, {"c3k2f", &ctx->opt.c3k2f}, {"pw32", &ctx->opt.pw32}, {"graph", &ctx->opt.graph}};
+            {"hmerge", &ctx->opt.hmerge}, {"sppf_fuse", &ctx->opt.sppf_fuse}, {"attn_mfma", &ctx->opt.attn_mfma}, {"xtile", &ctx->opt.xtile}, {"nitile", &ctx->opt.nitile}, {"nc2", &ctx->opt.nc2}, {"blk32", &ctx->opt.blk32}, {"c3k2f", &ctx->opt.c3k2f}, {"pw32", &ctx->opt.pw32}, {"upacc", &ctx->opt.upacc}, {"graph", &ctx->opt.graph}};
         for (auto &e : sw)
             if (k == e.key) { *e.flag = value != 0; return OBB_OK; }
         if (k == "fuse") return OBB_OK;  // (retired: the LDS-resident layer chains were slower than layer-by-layer on MI355X and are gone)
@@ -445,8 +449,9 @@ int obb_debug_plan(obb_ctx *ctx, int32_t h, int32_t w, char *buf, int64_t buf_by
         switch (op.type) {
             case OP_CONV32: {
                 const Conv32Launch &L = op.c32;
-                snprintf(line, sizeof line, "conv32 %s k%d s%d cin%d cout%d out%dx%d TH%d TW%d NI%d CK%d WC%d NC%d MFM%d dw%d tail%d vcat%d lds%d macs%.0f\n", op.name.c_str(), L.ks,
-                         L.stride, L.cin, L.cout, op.Ho, op.Wo, L.TH, L.TW, L.NI, L.CK, L.WC, L.NC, L.MFM, L.dw, L.tail_cout, op.vin ? 1 : 0, (int)conv32_lds_bytes(L), op.macs);
+                snprintf(line, sizeof line, "conv32 %s k%d s%d cin%d cout%d out%dx%d TH%d TW%d NI%d CK%d WC%d NC%d MFM%d dw%d tail%d vcat%d upacc%d lds%d macs%.0f\n", op.name.c_str(), L.ks,
+                         L.stride, L.cin, L.cout, op.Ho, op.Wo, L.TH, L.TW, L.NI, L.CK, L.WC, L.NC, L.MFM, L.dw, L.tail_cout, op.vin ? 1 : 0, op.upacc ? 1 : 0, (int)conv32_lds_bytes(L),
+                         op.macs);
                 break;
             }
             case OP_CONV: {
@@ -466,8 +471,8 @@ int obb_debug_plan(obb_ctx *ctx, int32_t h, int32_t w, char *buf, int64_t buf_by
             case OP_POOL: snprintf(line, sizeof line, "pool %s c%d out%dx%d macs0\n", op.name.c_str(), op.in.C, op.Ho, op.Wo); break;
             case OP_UP: snprintf(line, sizeof line, "upsample %s c%d out%dx%d macs0\n", op.name.c_str(), op.in.C, op.Ho, op.Wo); break;
             case OP_PW32:
-                snprintf(line, sizeof line, "pw32 %s k1 s1 cin%d cout%d out%dx%d waves%d lds%d macs%.0f\n", op.name.c_str(), op.pw32.cin, op.pw32.cout, op.Ho, op.Wo,
-                         op.pw32.cin * 256 <= 80 * 1024 ? 8 : 16, op.pw32.cin * 256, op.macs);
+                snprintf(line, sizeof line, "pw32 %s k1 s1 cin%d cout%d out%dx%d waves%d raw%d lds%d macs%.0f\n", op.name.c_str(), op.pw32.cin, op.pw32.cout, op.Ho, op.Wo,
+                         op.pw32.cin * 256 <= 80 * 1024 ? 8 : 16, op.pw32.raw ? 1 : 0, op.pw32.cin * 256, op.macs);
                 break;
             case OP_C3K2F32: {
                 int th, tw;

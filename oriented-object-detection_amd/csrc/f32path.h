@@ -27,6 +27,10 @@ struct Conv32Launch {
     // channels [up_c, cin) = `in2` (full resolution); neither the upsampled tensor nor the concat exists.  1-D launches only.
     TensorRef in2;
     int up_c = 0, up_W = 0, up_HW = 0;  // full-resolution width and pixels per image
+    // the same 1x1 as two launches (acc_init.p set, up_c = 0): `in` is the skip tensor alone (cin = its channels, plain NHWC or 8-channel blocks
+    // per image) and the accumulators of fine pixel (image, y, x) start from acc_init[(image, y >> 1, x >> 1)][cout] -- the raw partial product
+    // over the upsampled channels, computed once per coarse pixel (Pw32Launch::raw) -- instead of zero.  1-D launches, NC = 2, up_W / up_HW as above.
+    TensorRef acc_init;
     // optional fused trailing 1x1 conv (tail_cout > 0): consumes THIS layer's activated output tile straight from LDS (this layer's
     // own output is then never written); tail_act = SiLU on the tail; its rows go to tail_out (an activation slice or the head tensor)
     const float *tail_w = nullptr;  // pack_conv32_weights(w2, tail_cout, cout, 1, {1, *, CK = cout, *})

@@ -55,6 +55,9 @@ struct C32Params {
     int in_blk, in2_blk, out_blk, in_ps, in2_ps, out_ps, up_stages;
     int64_t in2_bs;
     unsigned in_sadd, in2_sadd;  // bytes from one channel stage to the next
+    // AINIT: the accumulators of fine pixel (image, y, x) start from ini[(image, y >> 1, x >> 1)][cout] (plain NHWC at half the resolution;
+    // up_W / up_HW = the fine level's width and pixels per image) instead of zero
+    const float *ini; int ini_cs; unsigned ini_span_bytes;
 };
 
 // SiLU with the hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each): relative error <= ~1e-6 for |x| <= 10, below the
@@ -85,8 +88,16 @@ __device__ __forceinline__ float silu32(float x) { return x * __builtin_amdgcn_r
 //     (pack_conv32_weights permutes the rows accordingly).
 //   * BLK: some operand lives in 8-channel blocks (C32Params::in_blk / in2_blk / out_blk); a template switch, so that the plain forms carry
 //     none of its address arithmetic or parameters (with run-time flags only, every 1x1 form lost 5-10 % to the extra scalar registers)
-template <int KS, int MFM, int WC, int NW, bool IN_U8, bool VCAT, int TAIL, bool DW = false, int NC = 1, bool BLK = false>
+//   * AINIT (1-D 1x1, NC = 2): the remainder of a 1x1 over [Upsample x2 | skip].  A 1x1 commutes with nearest-neighbour upsampling, and the
+//     VCAT form runs the upsampled channels first, into zeroed accumulators: the four fine pixels of a 2 x 2 block hold the same bits after
+//     those stages.  k_pw_f32 (RAW) computes that partial once per COARSE pixel; here the accumulators start from it (two 16-byte loads per
+//     lane and pixel fragment, the epilogue's own lane-to-cout layout, issued once per tile -- nothing of it in the stage loop) and the k
+//     chain goes on over the skip channels only: the same fma chain as VCAT, bit for bit, with 3/4 of the upsampled half's MFMAs gone.
+//     The input is the skip tensor alone (plain NHWC or 8-channel blocks per image), so the form keeps the plain 1x1's 64-channel stages and
+//     its cross-tile prefetch.
+template <int KS, int MFM, int WC, int NW, bool IN_U8, bool VCAT, int TAIL, bool DW = false, int NC = 1, bool BLK = false, bool AINIT = false>
 __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P) {  // <= 128 VGPRs: two workgroups per CU
+    static_assert(!AINIT || (KS == 1 && NC == 2 && !VCAT), "accumulator init: the 1-D 1x1 two-fragment form only");
     static_assert(NC == 1 || (NC == 2 && TAIL == 0 && !DW && !IN_U8), "two cout fragments per wave: plain / VCAT forms only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SKS = DW ? 3 : KS;  // kernel size the STAGING sees (halo); the MFMA loop sees KS
@@ -149,7 +160,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
     // staging plan: this thread moves the 16-B chunks idx = tid + k * NT of the [in_px][CK] tile.  Activations come through buffer
     // loads (descriptor in SGPRs, one 32-bit byte offset per chunk): an offset past the descriptor's range reads zeros, which is how
     // the zero padding is written
-    constexpr int MAXLD = IN_U8 ? 3 : (KS == 1 ? (DW ? 3 : (VCAT ? 4 : 7)) : 5);  // plan_conv32 keeps a stage within that many x NT chunks of 16 B
+    constexpr int MAXLD = IN_U8 ? 3 : (KS == 1 ? (DW ? 3 : (VCAT ? 4 : (AINIT ? 6 : 7))) : 5);  // plan_conv32 keeps a stage within that many x NT chunks of 16 B (AINIT: 192 pixels x 64 channels)
     constexpr int MAXW = (WC * NC * (KS == 3 ? 9 : 4) * 64 + (DW ? 10 * 8 : 0) + NT - 1) / NT;  // weight chunks per thread and stage (kst <= 9 / 4; DW: + 10 x CK floats, CK <= 32)
     constexpr unsigned NOPIX = 0xffffffffu;
     const int nchunk = in_px * cpk;
@@ -194,6 +205,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
                         const int c2 = P.in2_blk ? (cch >> 3) * P.in2_ps + (cch & 7) : cch;
                         goff2[k] = ok ? (unsigned)(((int64_t)bb * P.in2_bs + (int64_t)r * P.in2_cs + c2) * 4) : NOPIX;
                     } else goff2[k] = ok ? (unsigned)(((int64_t)gx * P.in2_cs + cch) * 4) : NOPIX;
+                } else if constexpr (AINIT) {  // 1-D over a per-image (possibly channel-blocked) tensor: gx = flattened (image, pixel)
+                    const int bb = gx / P.up_HW, r = gx - bb * P.up_HW;
+                    const int c1 = (BLK && P.in_blk) ? (cch >> 3) * P.in_ps + (cch & 7) : cch;
+                    goff[k] = ok ? (unsigned)(((int64_t)bb * P.in_bs + (int64_t)r * P.in_cs + c1) * 4) : NOPIX;
                 } else {
                     const int c1 = (BLK && P.in_blk) ? (cch >> 3) * P.in_ps + (cch & 7) : cch;
                     goff[k] = ok ? (unsigned)(((int64_t)il * P.in_bs + ((int64_t)gy * P.Win + gx) * P.in_cs + c1) * 4) : NOPIX;
@@ -244,7 +259,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
             int tidc = tid;
             // (KS 3 x 64 couts, the forms at the register limit: opaque, i.e. the LDS addresses are recomputed per commit -- a few VALU ops per
             // 250 MFMAs -- instead of living in MAXLD registers across the k loops; the 1x1 forms have the room and 4.5x fewer MFMAs per commit)
-            if constexpr (KS == 3 && WC == 4) asm volatile("" : "+v"(tidc));
+            if constexpr ((KS == 3 && WC == 4) || AINIT) asm volatile("" : "+v"(tidc));  // (AINIT: the plain two-fragment form sits at 127 registers already)
 #pragma unroll
             for (int k = 0; k < MAXLD; ++k) {
                 const int idx = tidc + k * NT;
@@ -296,6 +311,26 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
     float4 bvn[NC];  // bias is padded: always readable
 #pragma unroll
     for (int nc = 0; nc < NC; ++nc) bvn[nc] = TAIL > 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4 *>(P.bias + cbase + 4 * nc);
+    // AINIT: the tile's accumulators <- the coarse partial product (pixels past the tile or the tensor: offset past the range = zeros)
+    auto init_acc = [&](const Tile &T) {
+        if constexpr (AINIT) {
+            const __amdgpu_buffer_rsrc_t ini_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)P.ini, 0, (int)P.ini_span_bytes, 0x00020000);
+            int plv = pl;
+            asm volatile("" : "+v"(plv));  // (opaque, as in `plan`: recomputed per tile)
+#pragma unroll
+            for (int mf = 0; mf < MFM; ++mf) {
+                const int p = (wp + WP * mf) * 16 + plv, gx = T.ox0 + p;
+                const int bb = gx / P.up_HW, r = gx - bb * P.up_HW;
+                const int yy = r / P.up_W, xx = r - yy * P.up_W;
+                const int64_t sp = (int64_t)bb * (P.up_HW >> 2) + (int64_t)(yy >> 1) * (P.up_W >> 1) + (xx >> 1);
+                const bool ok = p < npix && gx < P.Wout && cbase + 4 * NC <= P.cout;
+#pragma unroll
+                for (int nc = 0; nc < NC; ++nc)
+                    acc[nc][mf] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ini_rsrc, ok ? (unsigned)((sp * P.ini_cs + cbase + 4 * nc) * 4) : NOPIX, 0, 0));
+            }
+        }
+    };
+    init_acc(cur);
     for (;;) {
     bool more = false;  // (XT) the next tile's first stage is in flight / in LDS
     for (int stage = 0; stage < P.nstage; ++stage) {
@@ -565,10 +600,13 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
     __syncthreads();  // the next tile's first stage is in LDS
     t += P.tstep;
     cur = nxt;
+    if constexpr (AINIT) init_acc(cur);
+    else {
 #pragma unroll
-    for (int nc = 0; nc < NC; ++nc)
+        for (int nc = 0; nc < NC; ++nc)
 #pragma unroll
-        for (int mf = 0; mf < MFM; ++mf) acc[nc][mf] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int mf = 0; mf < MFM; ++mf) acc[nc][mf] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     }
 }
 
@@ -742,9 +780,9 @@ size_t conv32_lds_bytes(const Conv32Launch &L) {
     return lds;
 }
 
-template <int KS, int MFM, int WC, bool IN_U8, bool VCAT, int TAIL, bool DW = false, int NC = 1, bool BLK = false>
+template <int KS, int MFM, int WC, bool IN_U8, bool VCAT, int TAIL, bool DW = false, int NC = 1, bool BLK = false, bool AINIT = false>
 static hipError_t launch32_k(const C32Params &P0, dim3 grid, size_t lds, hipStream_t st) {
-    const void *fn = (const void *)k_conv_f32<KS, MFM, WC, kNW, IN_U8, VCAT, TAIL, DW, NC, BLK>;
+    const void *fn = (const void *)k_conv_f32<KS, MFM, WC, kNW, IN_U8, VCAT, TAIL, DW, NC, BLK, AINIT>;
     static bool attr_set = false;  // (per instantiation) up to 80 KiB of dynamic LDS: two workgroups per CU
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
@@ -783,7 +821,7 @@ static hipError_t launch32_k(const C32Params &P0, dim3 grid, size_t lds, hipStre
             grid = dim3((unsigned)(slots * 8 * P.ncb));
         }
     }
-    hipLaunchKernelGGL((k_conv_f32<KS, MFM, WC, kNW, IN_U8, VCAT, TAIL, DW, NC, BLK>), grid, dim3(kNW * 64), lds, st, P);
+    hipLaunchKernelGGL((k_conv_f32<KS, MFM, WC, kNW, IN_U8, VCAT, TAIL, DW, NC, BLK, AINIT>), grid, dim3(kNW * 64), lds, st, P);
     return hipGetLastError();
 }
 
@@ -818,6 +856,10 @@ template <int KS, bool BLK>
 static hipError_t launch32_wc(const Conv32Launch &L, const C32Params &P, int tail_wc2, dim3 grid, size_t lds, hipStream_t st) {
     if (L.NC == 2) {  // two cout fragments per wave: 2 waves along cout, 3 or 4 pixel fragments per wave; plain and (1x1) VCAT forms
         if (L.WC != 2 || tail_wc2 || L.dw || L.in_u8) return hipErrorInvalidValue;
+        if (L.acc_init.p) {  // the remainder of a 1x1 over [Upsample | skip]: accumulators start from the coarse partial product
+            if constexpr (KS == 1) { if (L.MFM == 3 && !L.up_c) return launch32_k<KS, 3, 2, false, false, 0, false, 2, BLK, true>(P, grid, lds, st); }
+            return hipErrorInvalidValue;
+        }
         if (L.up_c > 0) {
             if constexpr (KS == 1) {
                 if (L.MFM == 4) return launch32_k<KS, 4, 2, false, true, 0, false, 2, BLK>(P, grid, lds, st);
@@ -849,7 +891,7 @@ hipError_t launch_conv32(const Conv32Launch &L, hipStream_t st) {
     if (L.res.cpb || L.tail_out.cpb) return hipErrorInvalidValue;  // plain NHWC only
     {   // channel-blocked (by 8) tensors: see C32Params
         auto blk8 = [](const TensorRef &t) { return t.cpb == 2 && t.cs == 8 && t.co % 8 == 0 && t.ps > 0 && t.ps < (1ll << 28); };
-        if (L.in.cpb && (!blk8(L.in) || L.in_u8 || L.up_c > 0 || (L.ks != 3 && !L.dw) || L.CK % 8 || L.cin % 8)) return hipErrorInvalidValue;
+        if (L.in.cpb && (!blk8(L.in) || L.in_u8 || L.up_c > 0 || (L.ks != 3 && !L.dw && !L.acc_init.p) || L.CK % 8 || L.cin % 8)) return hipErrorInvalidValue;
         if (L.in2.cpb && (!blk8(L.in2) || L.up_c <= 0 || L.CK % 8)) return hipErrorInvalidValue;
         // (1x1 layers are issued over the flattened batch: their blocked output needs the per-image split of out_hw)
         if (L.out.cpb && (!blk8(L.out) || L.tail_cout > 0 || L.cout % 8 || (L.ks == 1 && !L.dw && L.out_hw <= 0))) return hipErrorInvalidValue;
@@ -912,10 +954,23 @@ hipError_t launch_conv32(const Conv32Launch &L, hipStream_t st) {
             P.in2_span_bytes = (unsigned)s2;
             P.up_c = L.up_c; P.up_W = L.up_W; P.up_HW = L.up_HW; P.up_stages = L.up_c / L.CK;
         }
+        if (L.acc_init.p) {  // (see AINIT in k_conv_f32) 1-D 1x1 over the skip tensor of `Win / up_HW` whole images
+            if (L.ks != 1 || L.in_u8 || L.dw || L.up_c || L.tail_cout > 0 || L.B != 1 || L.Hin != 1 || NI != 1 || L.NC != 2 || L.cout % 32 || L.up_W < 2 || (L.up_W & 1) ||
+                L.up_HW < 4 || (L.up_HW % L.up_W) || ((L.up_HW / L.up_W) & 1) || L.Win % L.up_HW || L.acc_init.cpb || ((L.acc_init.cs | L.acc_init.co) & 3) ||
+                L.acc_init.cs < L.acc_init.co + L.cout)
+                return hipErrorInvalidValue;
+            const int64_t nimg = L.Win / L.up_HW;
+            if (L.in.cpb) span = (nimg * L.in.bs - (int64_t)(L.in.co >> 3) * L.in.ps) * 4;
+            else if (L.in.bs != (int64_t)L.up_HW * L.in.cs) return hipErrorInvalidValue;  // dense images: the flattened pixel row
+            const int64_t si = (nimg * (L.up_HW / 4) * L.acc_init.cs - L.acc_init.co) * 4;
+            if (si <= 0 || si >= (1ll << 32) - 65536) return hipErrorInvalidValue;
+            P.ini = (const float *)L.acc_init.p + L.acc_init.co; P.ini_cs = L.acc_init.cs; P.ini_span_bytes = (unsigned)si;
+            P.up_W = L.up_W; P.up_HW = L.up_HW;
+        }
         if (!L.in_u8 && (span <= 0 || span >= (1ll << 32) - 65536)) return hipErrorInvalidValue;  // 32-bit buffer offsets
         P.in_span_bytes = L.in_u8 ? 0u : (unsigned)span;
     }
-    if ((int64_t)NI * THin * TWin * (L.in_u8 ? 1 : L.CK / 4) > (int64_t)(L.dw ? 3 : (L.up_c > 0 ? 4 : c32_maxld(L.ks, L.in_u8))) * kNW * 64) return hipErrorInvalidValue;  // staging plan: chunks per thread
+    if ((int64_t)NI * THin * TWin * (L.in_u8 ? 1 : L.CK / 4) > (int64_t)(L.dw ? 3 : (L.up_c > 0 ? 4 : (L.acc_init.p ? 6 : c32_maxld(L.ks, L.in_u8)))) * kNW * 64) return hipErrorInvalidValue;  // staging plan: chunks per thread
     int tail_wc2 = 0;
     if (L.tail_cout > 0) {
         const Conv32Tiling t{L.TH, L.TW, L.CK, L.WC, L.MFM, NI};

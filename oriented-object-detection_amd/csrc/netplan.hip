@@ -49,6 +49,13 @@ int parse_blob(obb_ctx *ctx, Model &M) {
     return OBB_OK;
 }
 
+// columns [c0, c0 + nc) of a 1x1 record's [cout][cin] matrix as a dense [cout][nc] one
+static std::vector<float> split_cols(const float *w, int cout, int cin, int c0, int nc) {
+    std::vector<float> o((size_t)cout * nc);
+    for (int co = 0; co < cout; ++co) std::copy(w + (size_t)co * cin + c0, w + (size_t)co * cin + c0 + nc, o.begin() + (size_t)co * nc);
+    return o;
+}
+
 // ---------------------------------------------------------------------------------------------- graph builder
 static int make_divisible(double x, int d) { return (int)std::ceil(x / d) * d; }
 static int out_dim(int in, int k, int s) { return (in + 2 * (k / 2) - k) / s + 1; }  // "same" padding k / 2
@@ -220,6 +227,7 @@ struct Builder {
             err = set_error(ctx, OBB_ERR_STATE, "layer %s: residual / fused-1x1 output in a channel-blocked buffer", name.c_str());
             return;
         }
+        if (op.vin && !perm && !tail_name && head_level < 0 && !res.C && upacc_ok(r, P.bufs[in.buf], Hin, Win)) return emit_upacc(op, r);
         if (M.f32 && M.o.pw32 && r->k == 1 && !in_u8 && !op.vin && !tail_name && head_level < 0 && !P.bufs[in.buf].blk32 && pw32_supported(cin, r->c2) &&
             !(res.C && P.bufs[res.buf].blk32))
             return emit_pw32(op, r, perm);
@@ -249,6 +257,38 @@ struct Builder {
         L.bias = bias_padded(r, perm);
         emit(op, r->name, op.out);
     }
+    // fp32 mode, the 1x1 `r` over the virtual concat `vb` = [Upsample x2 of va | vb] as TWO launches ("upacc"): a 1x1 commutes with nearest
+    // upsampling, so the product over va's channels is computed once per coarse pixel and the fine launch starts its accumulators from it
+    // (bit for bit what the one-launch VCAT form computes: see AINIT in k_conv_f32).  The shapes that have both kernels:
+    bool upacc_ok(const ConvRecord *r, const Buf &vb, int H, int W) const {
+        if (!M.f32 || !M.o.upacc || !M.o.pw32 || !M.o.nc2 || r->k != 1 || vb.va_C % 16 || (H & 1) || (W & 1) || P.bufs[vb.va_buf].blk32) return false;
+        if (!pw32_supported(vb.va_C, r->c2) || vb.vb_C < 64 || r->c2 % 32) return false;
+        const Conv32Tiling t = plan_conv32(1, 1, vb.vb_C, r->c2, H, W, false, false, true);
+        return t.NC == 2 && t.WC == 2 && t.MFM == 3 && vb.vb_C % t.CK == 0;
+    }
+    void emit_upacc(Op op, const ConvRecord *r) {
+        const Buf vb = P.bufs[op.in.buf];
+        const int up_c = vb.va_C, sk = vb.vb_C, Hc = op.H / 2, Wc = op.W / 2;
+        const int part = buf(Hc, Wc, r->c2, r->name + ".up", true);  // the raw fp32 accumulators, plain NHWC at the coarse resolution
+        Op oc;
+        oc.type = OP_PW32; oc.name = r->name + ".up"; oc.in = Slice{vb.va_buf, vb.va_co, up_c}; oc.out = whole(part);
+        oc.H = oc.Ho = Hc; oc.W = oc.Wo = Wc; oc.one_d = true;
+        oc.pw32.cin = up_c; oc.pw32.cout = r->c2; oc.pw32.act = 0; oc.pw32.raw = true;
+        oc.pw32.wpk = upload(pack_pw32_weights(split_cols(r->w, r->c2, r->c1, 0, up_c).data(), r->c2, up_c, nullptr));
+        oc.macs = (double)Hc * Wc * r->c2 * up_c;
+        emit(oc);
+        op.type = OP_CONV32; op.upacc = true; op.ini = whole(part);
+        op.macs = (double)op.Ho * op.Wo * r->c2 * sk;
+        Conv32Launch &L = op.c32;
+        const Conv32Tiling t = plan_conv32(1, 1, sk, r->c2, op.Ho, op.Wo, false, false, true);
+        L.ks = 1; L.stride = 1; L.cin = sk; L.cout = r->c2; L.act = r->act;
+        L.TH = t.TH; L.TW = t.TW; L.CK = t.CK; L.WC = t.WC; L.MFM = t.MFM; L.NI = t.NI; L.NC = t.NC;
+        L.Hin = L.Hout = op.H; L.Win = L.Wout = op.W; L.tiles_y = 1; L.tiles_x = 1;  // (1-D: bound per sub-batch)
+        L.wpk = upload(pack_conv32_weights(split_cols(r->w, r->c2, r->c1, up_c, sk).data(), r->c2, sk, 1, t, nullptr, false));
+        L.bias = bias_padded(r);
+        emit(op, r->name, op.out);
+    }
+
     // fp32-arithmetic mode: exact-f32 MFMA kernels (f32path.hip)
     void emit_conv32(Op op, const ConvRecord *r, const int *perm, const char *tail_name) {
         const bool in_u8 = op.in.buf < 0;
@@ -775,3 +815,25 @@ struct Builder {
 int build_plan(obb_ctx *ctx, Model &M, Plan &P) { return Builder{ctx, M, P}.build(); }
 
 }  // namespace obb
+
+// Host only: the packed fp32 weights of columns [c0, c0 + nc) of the 1x1 matrix w[cout][cin], as the plan builder packs them for
+// form 0: k_pw_f32 (the coarse partial product of "upacc"), 1: the plain two-fragment k_conv_f32 form (its fine remainder), 2: the VCAT form
+// over the whole virtual concat.  tiling_host (optional) receives {CK, WC, NC} of forms 1 / 2.
+extern "C" int obb_debug_pack_1x1(int32_t form, const float *w, int32_t cout, int32_t cin, int32_t c0, int32_t nc, float *out, int64_t max_floats, int64_t *needed,
+                                  int32_t *tiling_host) {
+    using namespace obb;
+    if (!w || !needed || form < 0 || form > 2 || cout < 1 || cin < 1 || c0 < 0 || nc < 1 || c0 + nc > cin) return OBB_ERR_INVALID;
+    const std::vector<float> m = split_cols(w, cout, cin, c0, nc);
+    std::vector<float> pk;
+    if (form == 0) {
+        if (!pw32_supported(nc, cout)) return OBB_ERR_INVALID;
+        pk = pack_pw32_weights(m.data(), cout, nc, nullptr);
+    } else {
+        const Conv32Tiling t = plan_conv32(1, 1, nc, cout, 2, 2, false, form == 2, true);
+        if (tiling_host) { tiling_host[0] = t.CK; tiling_host[1] = t.WC; tiling_host[2] = std::max(1, t.NC); }
+        pk = pack_conv32_weights(m.data(), cout, nc, 1, t, nullptr, false);
+    }
+    *needed = (int64_t)pk.size();
+    if (out && max_floats >= *needed) memcpy(out, pk.data(), pk.size() * sizeof(float));
+    return OBB_OK;
+}

@@ -64,6 +64,8 @@ struct Op {
     double macs = 0;         // MACs of all layers of the op (an integer: sums of them are exact in any order)
     bool one_d = false;
     bool vin = false;        // OP_CONV: the input is a virtual upsample-concat buffer
+    bool upacc = false;      // OP_CONV32 with vin: reads the skip member only, its accumulators start from the coarse partial product in `ini`
+    Slice ini;               //   (written by the OP_PW32 launch "<name>.up" in front of it)
     const bf16_t *dw_w = nullptr;  // OP_DW (device): 16-bit [9][C]
     const float *dw_b = nullptr;
     const float *dw_w32 = nullptr;  // OP_DW in fp32 mode: fp32 [9][C]

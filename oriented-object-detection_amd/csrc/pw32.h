@@ -17,6 +17,8 @@ struct Pw32Launch {
     int64_t npix = 0;             // B * H * W
     int hw = 0;                   // pixels per image (the blocked output needs (image, pixel))
     int cin = 0, cout = 0, act = 1;
+    bool raw = false;             // the accumulators themselves (no bias, activation, residual) into a plain NHWC `out`: the coarse partial product of
+                                  // a 1x1 over [Upsample x2 | skip], which the fine launch's accumulators start from (Conv32Launch::acc_init)
 };
 
 bool pw32_supported(int cin, int cout);

@@ -16,7 +16,8 @@
 // Measured (profiles/r04_summary.md): the 25 layers 3.65 -> 3.3 ms per 512 tiles, forward 32.13 -> 31.45 ms per 1024 tiles.  Timing-only
 // ablations of the 26 x 26 layers (177 us): without the in-loop loads 163, without the stores 161 -- neither the loads nor the stores are
 // the bound; the 52 x 52 layers move 1.24 GB for 34 GFLOP (HBM and MFMA time about equal).  The two virtual upsample-concat layers were tried
-// on this kernel and stay on k_conv_f32 (no gain: the coarse-pixel arithmetic costs the registers of the cross-tile prefetch).
+// on this kernel and stay on k_conv_f32 (no gain: the coarse-pixel arithmetic costs the registers of the cross-tile prefetch); what runs here
+// is their upsampled half at COARSE resolution (RAW: the accumulators stored unchanged, see AINIT in f32path.hip and profiles/upacc.md).
 // Row order of the weights (pack_pw32_weights): a lane ends with 16 consecutive output channels of its pixel (64 contiguous bytes / two
 // 8-channel blocks).
 #include "pw32.h"
@@ -44,7 +45,7 @@ __device__ __forceinline__ float silu32p(float x) { return x * __builtin_amdgcn_
 // this tile and leave loaded with pieces 0 / 1 of the next one (its first `nxt` fragments, 48 pixels further on: a wave's range is contiguous),
 // so that the epilogue of a tile runs under the first loads of the next and a wave never waits for a cold load between tiles.
 // Pixels past the end of the tensor need no lane test on the way in: their offsets are past the buffer range and read as zero.
-template <int M>
+template <int M, bool RAW>
 __device__ __forceinline__ void pw_tile(const Pw32Params &P, const __amdgpu_buffer_rsrc_t in_rsrc, const char *wl, const int p0, const int pl, const int g,
                                         const int cbase, u32x4 (&b0)[3], u32x4 (&b1)[3], const int nxt) {
     constexpr int NCF = 4;
@@ -90,6 +91,17 @@ __device__ __forceinline__ void pw_tile(const Pw32Params &P, const __amdgpu_buff
         }
     }
     // ---- epilogue: + bias, SiLU, + residual, store (a lane: 16 consecutive channels of its pixel)
+    if constexpr (RAW) {  // the accumulators as they are (plain NHWC): a partial product that another launch's k chain continues
+#pragma unroll
+        for (int f = 0; f < M; ++f) {
+            const int p = p0 + f * 16 + pl;
+            if (p >= P.npix) continue;
+            float *op = P.out + (int64_t)p * P.out_cs + P.out_co + cbase;
+#pragma unroll
+            for (int nf = 0; nf < NCF; ++nf) *reinterpret_cast<f32x4 *>(op + 4 * nf) = acc[nf][f];
+        }
+        return;
+    }
 #pragma unroll
     for (int f = 0; f < M; ++f) {
         const int p = p0 + f * 16 + pl;
@@ -122,7 +134,9 @@ __device__ __forceinline__ void pw_tile(const Pw32Params &P, const __amdgpu_buff
 // one XCD and read the same lines through its L2) owns the contiguous range [ww F / NWV, (ww + 1) F / NWV), ww = t NW + w, and walks it three
 // fragments at a time, the rest as a 2- or 1-fragment tile.  (Whole 384-pixel tiles dealt out per workgroup left 3.5 tiles per workgroup on
 // the 26 x 26 levels -- a quarter of the chip idle during the fourth; per wave it is 10.6 fragments against a maximum of 11.)
-template <int NW>
+// RAW: no bias, activation or residual -- the fp32 accumulators go to memory unchanged (Pw32Launch::raw); a template flag, so that the
+// plain form carries nothing of it
+template <int NW, bool RAW = false>
 __global__ __launch_bounds__(NW * 64, 4) void k_pw_f32(const Pw32Params P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [piece][cout fragment 4][lane][16 B]
     constexpr int NT = NW * 64, NCF = 4;
@@ -158,9 +172,9 @@ __global__ __launch_bounds__(NW * 64, 4) void k_pw_f32(const Pw32Params P) {
     __syncthreads();
     const char *wl = smem + lane * 16;
     const int cbase = cb * 64 + 16 * g;  // this lane's 16 consecutive output channels
-    for (; fr_end - fr >= 3; fr += 3) pw_tile<3>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, min(3, fr_end - fr - 3));
-    if (fr_end - fr == 2) pw_tile<2>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, 0);
-    else if (fr_end - fr == 1) pw_tile<1>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, 0);
+    for (; fr_end - fr >= 3; fr += 3) pw_tile<3, RAW>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, min(3, fr_end - fr - 3));
+    if (fr_end - fr == 2) pw_tile<2, RAW>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, 0);
+    else if (fr_end - fr == 1) pw_tile<1, RAW>(P, in_rsrc, wl, fr * 16, pl, g, cbase, b0, b1, 0);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -182,9 +196,9 @@ std::vector<float> pack_pw32_weights(const float *w, int cout, int cin, const in
     return out;
 }
 
-template <int NW>
+template <int NW, bool RAW>
 static hipError_t launch_pw(const Pw32Params &P0, size_t lds, hipStream_t st) {
-    const void *fn = (const void *)k_pw_f32<NW>;
+    const void *fn = (const void *)k_pw_f32<NW, RAW>;
     static std::mutex mu;
     static std::map<std::pair<int, size_t>, int> occ;  // (device, LDS bytes) -> resident workgroups on the chip
     int dev = 0;
@@ -209,15 +223,16 @@ static hipError_t launch_pw(const Pw32Params &P0, size_t lds, hipStream_t st) {
     const int64_t want8 = ((int64_t)P.nfrag + 3 * NW * 8 - 1) / (3 * NW * 8);
     const int64_t slots = std::max<int64_t>(1, std::min<int64_t>(want8, resident / (8 * P.ncb)));
     P.nwalk = (int)(slots * 8);
-    hipLaunchKernelGGL((k_pw_f32<NW>), dim3((unsigned)(P.nwalk * P.ncb)), dim3(NW * 64), lds, st, P);
+    hipLaunchKernelGGL((k_pw_f32<NW, RAW>), dim3((unsigned)(P.nwalk * P.ncb)), dim3(NW * 64), lds, st, P);
     return hipGetLastError();
 }
 
 hipError_t launch_pw32(const Pw32Launch &L, hipStream_t st) {
-    if (!pw32_supported(L.cin, L.cout) || L.in.cpb || L.res.cpb || !L.in.p || !L.out.p || !L.wpk || !L.bias || L.npix < 1 || L.npix >= (1ll << 31)) return hipErrorInvalidValue;
+    if (!pw32_supported(L.cin, L.cout) || L.in.cpb || L.res.cpb || !L.in.p || !L.out.p || !L.wpk || (!L.bias && !L.raw) || L.npix < 1 || L.npix >= (1ll << 31)) return hipErrorInvalidValue;
     if ((L.in.cs | L.in.co) & 3 || (L.res.p && ((L.res.cs | L.res.co) & 3))) return hipErrorInvalidValue;
     if (L.out.cpb && !(L.out.cpb == 2 && L.out.cs == 8 && L.out.co % 8 == 0 && L.out.ps > 0 && L.hw > 0)) return hipErrorInvalidValue;
     if (!L.out.cpb && ((L.out.cs | L.out.co) & 3)) return hipErrorInvalidValue;
+    if (L.raw && (L.out.cpb || L.res.p)) return hipErrorInvalidValue;
     Pw32Params P;
     P.in = (const float *)L.in.p; P.in_cs = L.in.cs; P.in_co = L.in.co;
     const int64_t span = (L.npix * L.in.cs - L.in.co) * 4;
@@ -229,8 +244,9 @@ hipError_t launch_pw32(const Pw32Launch &L, hipStream_t st) {
     P.npix = (int)L.npix; P.npiece = L.cin / 16; P.cout = L.cout; P.act = L.act; P.ncb = L.cout / 64;
     const size_t lds = (size_t)P.npiece * 4096;
     // K <= 320: 8-wave workgroups, two per CU; above: one 16-wave workgroup per CU (its weights alone are up to 128 KB)
-    if (lds <= 80 * 1024) return launch_pw<8>(P, lds, st);
-    return launch_pw<16>(P, lds, st);
+    if (L.raw) return lds <= 80 * 1024 ? launch_pw<8, true>(P, lds, st) : launch_pw<16, true>(P, lds, st);
+    if (lds <= 80 * 1024) return launch_pw<8, false>(P, lds, st);
+    return launch_pw<16, false>(P, lds, st);
 }
 
 }  // namespace obb
