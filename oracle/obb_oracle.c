@@ -64,11 +64,14 @@ static int seg_intersect(pt_t a, pt_t b, pt_t c, pt_t d) { /* closed segments sh
 }
 
 /* Shapely Polygon(...).is_valid restated for a 4-vertex ring: finite coords, non-zero area, the two pairs of
- * non-adjacent edges do not touch, and no zero-width spike at a vertex. */
+ * non-adjacent edges do not touch, and no zero-width spike at a vertex.  A vertex repeated consecutively is allowed (the ring is a
+ * triangle, and a triangle of non-zero area is valid): its two neighbouring edges meet there and are not "non-adjacent". */
 static int quad_valid(const pt_t *p) {
     for (int i = 0; i < 4; ++i)
         if (!isfinite(p[i].x) || !isfinite(p[i].y)) return 0;
     if (shoelace2(p, 4) == 0.0) return 0;
+    for (int i = 0; i < 4; ++i)
+        if (p[i].x == p[(i + 1) & 3].x && p[i].y == p[(i + 1) & 3].y) return 1; /* a triangle of non-zero area */
     if (seg_intersect(p[0], p[1], p[2], p[3])) return 0;
     if (seg_intersect(p[1], p[2], p[3], p[0])) return 0;
     for (int i = 0; i < 4; ++i) {

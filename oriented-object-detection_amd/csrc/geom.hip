@@ -840,13 +840,22 @@ __device__ __forceinline__ void merge_segment(const int seg, const double *__res
                 const BoxMeta mi = smeta[i];
                 if (!meta_overlap(mi, mj)) continue;
                 // the intersection lies inside both envelopes and inside either quad: IoU <= ub / (a_i + a_j - ub) with ub = min(area of
-                // the envelopes' overlap, a_i, a_j).  A pair whose bound is below the threshold by more than any rounding of the exact
-                // evaluation (relative 1e-9 against ~1e-15) cannot be a hit: it never reaches the clip -- the decisions are unchanged.
+                // the envelopes' overlap, a_i, a_j).  A pair whose bound is below the threshold by more than the rounding of the exact
+                // evaluation cannot be a hit: it never reaches the clip -- the decisions are unchanged.  That rounding is ABSOLUTE in the
+                // areas and grows with the coordinates: the shoelace sums round products of magnitude M^2 (M = largest |coordinate|), so
+                // at map coordinates of 6e4 a 100 px^2 area carries ~1e-8 relative, not 1e-15 (measured against exact rational areas:
+                // DESIGN.md, "polygon IoU").  slack bounds |computed - exact| of the clipped area plus that of a_i, a_j, with E >= the
+                // sum of the two envelope diagonals: u (28 M^2 + 256 M E + 672 E^2), u = 2^-53 (tests/geom_exact.py: iou_bound, summed
+                // over its worst path, the four triangle clips).  The clip's result is <= ub + slack, its union >= a_i + a_j - ub - slack.
                 {
                     const double ai = sarea[i];
                     const double ub = fmin(fmin(ai, aj), (fmin(mi.x1, mj.x1) - fmax(mi.x0, mj.x0)) * (fmin(mi.y1, mj.y1) - fmax(mi.y0, mj.y0)));
-                    const double den = ai + aj - ub;
-                    if (den > 0.0 && ub * (1.0 + 1e-9) < thr * den) continue;
+                    const double M = fmax(fmax(fmax(fabs(mi.x0), fabs(mi.x1)), fmax(fabs(mi.y0), fabs(mi.y1))),
+                                          fmax(fmax(fabs(mj.x0), fabs(mj.x1)), fmax(fabs(mj.y0), fabs(mj.y1))));
+                    const double E = (mi.x1 - mi.x0) + (mi.y1 - mi.y0) + (mj.x1 - mj.x0) + (mj.y1 - mj.y0);
+                    const double slack = 0x1p-53 * (28.0 * M * M + 256.0 * M * E + 672.0 * E * E);
+                    const double den = ai + aj - ub - slack;
+                    if (den > 0.0 && (ub + slack) * (1.0 + 0x1p-48) < thr * den) continue;
                 }
                 const unsigned int slot = atomicAdd(&npairs_s, 1u);
                 if (slot < (unsigned)kSegPairCap) spairs[slot] = ((unsigned)i << 16) | (unsigned)j;

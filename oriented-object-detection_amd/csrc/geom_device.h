@@ -44,6 +44,8 @@ __device__ __forceinline__ bool quad_valid(const P2 *p) {
     for (int i = 0; i < 4; ++i)
         if (!isfinite(p[i].x) || !isfinite(p[i].y)) return false;
     if (shoelace2<4>(p, 4) == 0.0) return false;
+    for (int i = 0; i < 4; ++i)  // a vertex repeated consecutively: the ring is a triangle, and a triangle of non-zero area is valid
+        if (p[i].x == p[(i + 1) & 3].x && p[i].y == p[(i + 1) & 3].y) return true;
     if (seg_intersect(p[0], p[1], p[2], p[3])) return false;
     if (seg_intersect(p[1], p[2], p[3], p[0])) return false;
     for (int i = 0; i < 4; ++i) {

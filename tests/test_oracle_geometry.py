@@ -7,12 +7,14 @@
 import json
 import math
 import os
+from fractions import Fraction
 
 import numpy as np
 import pytest
 
 from conftest import CLASS_IDS, GOLDEN, load_xlsx_csv
 from oracle import geom as og
+import geom_exact
 import synth
 
 
@@ -64,7 +66,9 @@ def test_iou_concave_quads():
     assert og.compute_polygon_iou(sq, arrow) == pytest.approx(1 / 4, abs=1e-14)
     arrow2 = [v + 0.5 for v in arrow]  # both concave -> triangle decomposition path
     i = og.compute_polygon_iou(arrow, arrow2)
-    assert 0.0 < i < 1.0 and i == pytest.approx(og.compute_polygon_iou(arrow2, arrow), abs=1e-14)
+    assert i == pytest.approx(25 / 167, abs=1e-15)  # geom_exact.iou: exactly 25/167 (worked out in test_geom_exact_cpu.py)
+    assert geom_exact.iou(arrow, arrow2)[0] == Fraction(25, 167) and abs(Fraction(i) - Fraction(25, 167)) <= geom_exact.iou_bound(arrow, arrow2)
+    assert i == pytest.approx(og.compute_polygon_iou(arrow2, arrow), abs=1e-14)
     assert og.compute_polygon_iou(arrow, arrow) == pytest.approx(1.0, abs=1e-14)
 
 
