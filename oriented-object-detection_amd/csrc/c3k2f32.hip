@@ -15,9 +15,9 @@
 // Traffic: 1.5 MB in + 2.8 MB out per tile.  MFMA floor (halo recompute and the 8-cout layer padded to a 16-row fragment included):
 // 1640 instructions per 208-pixel tile.
 #include "c3k2f32.h"
+#include "launchcfg.h"
 
 #include <algorithm>
-#include <mutex>
 
 namespace obb {
 
@@ -260,10 +260,8 @@ hipError_t launch_c3k2f32(const C3k2F32Launch &L, hipStream_t st) {
     if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
     constexpr int C = 16, CO = 64;
     constexpr size_t lds = (size_t)kC3MaxX * (C * 4 + 16) + (size_t)kC3MaxT * (C / 2 * 4 + 16) + 9 * 1024 + (4 * 1024 + 2 * 256) + (CO / 16) * 3 * 1024 + CO * 4;
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] { attr_err = hipFuncSetAttribute((const void *)k_c3k2_f32<16, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); });
-    if (attr_err != hipSuccess) return attr_err;
+    hipError_t e = allow_dyn_lds((const void *)k_c3k2_f32<16, 64>, 80 * 1024);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_c3k2_f32<16, 64>), dim3((unsigned)ntiles), dim3(512), lds, st, P);
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 // k_conv_igemm; 8 waves = 4 (three pixel fragments each) x 2 (halves of the 64 couts of a block).
 // Replaces ultralytics C3k (nn/modules/block.py) inside C3k2(c3k=True) for this shape; SURVEY Appendix A3.
 #include "c3kimg.h"
+#include "launchcfg.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -244,14 +245,8 @@ hipError_t launch_c3kimg(const C3kImgLaunch &L, hipStream_t st) {
     P.in = (const bf16_t *)L.in.p; P.in_bs = L.in.bs; P.in_cs = L.in.cs; P.in_co = L.in.co;
     P.out = (bf16_t *)L.out.p; P.out_bs = L.out.bs; P.out_cs = L.out.cs; P.out_co = L.out.co;
     P.wts = L.wts; P.bias = L.bias;
-    static bool attr[2] = {false, false};
-    const int k = L.f16 ? 0 : 1;
-    if (!attr[k]) {
-        hipError_t e = L.f16 ? hipFuncSetAttribute(reinterpret_cast<const void *>(&k_c3k_image<true>), hipFuncAttributeMaxDynamicSharedMemorySize, c3k::LDS_B)
-                             : hipFuncSetAttribute(reinterpret_cast<const void *>(&k_c3k_image<false>), hipFuncAttributeMaxDynamicSharedMemorySize, c3k::LDS_B);
-        if (e != hipSuccess) return e;
-        attr[k] = true;
-    }
+    hipError_t e = allow_dyn_lds(L.f16 ? reinterpret_cast<const void *>(&k_c3k_image<true>) : reinterpret_cast<const void *>(&k_c3k_image<false>), c3k::LDS_B);
+    if (e != hipSuccess) return e;
     if (L.f16) hipLaunchKernelGGL(k_c3k_image<true>, dim3((unsigned)L.B), dim3(512), c3k::LDS_B, st, P);
     else hipLaunchKernelGGL(k_c3k_image<false>, dim3((unsigned)L.B), dim3(512), c3k::LDS_B, st, P);
     return hipGetLastError();

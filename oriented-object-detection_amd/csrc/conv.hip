@@ -18,6 +18,7 @@
 //   * the network input layer reads the uint8 NHWC tile directly (BGR->RGB + /255 via a 256-entry LUT = exactly
 //     bf16(v/255)), i.e. the predictor's preprocess is fused into conv0.
 #include "conv.h"
+#include "launchcfg.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -1032,12 +1033,9 @@ bool conv_tail_supported(int ks, int MF, int NF, int cout1, int cout2, bool act1
 
 template <typename K>
 static hipError_t launch_big_lds(K kernel, const ConvParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    static bool attr_set = false;  // one flag per kernel instantiation
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);  // + the static arrays (bias, LUT) <= 160 KiB
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    // (every k_conv_igemm instantiation has the same function-pointer type, so K does not tell them apart: the cap is kept per device and kernel address)
+    hipError_t e = allow_dyn_lds((const void *)kernel, 152 * 1024);  // + the static arrays (bias, LUT) <= 160 KiB
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, P);
     return hipGetLastError();
 }
@@ -1249,12 +1247,8 @@ static hipError_t launch_conv_impl(const ConvLaunch &L, hipStream_t st, unsigned
         if (P.kst != 18 || P.nstage != 1 || lds > 158 * 1024) return hipErrorInvalidValue;
         const dim3 grid((unsigned)((P.gx + 7) / 8 * 8 * ncb));
         auto go = [&](auto kernel) -> hipError_t {
-            static std::vector<const void *> attr_set;  // (the four instantiations share one function-pointer type: keyed by address)
-            if (std::find(attr_set.begin(), attr_set.end(), (const void *)kernel) == attr_set.end()) {
-                hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);  // + static bias arrays <= 160 KiB
-                if (e != hipSuccess) return e;
-                attr_set.push_back((const void *)kernel);
-            }
+            hipError_t e = allow_dyn_lds((const void *)kernel, 158 * 1024);  // + static bias arrays <= 160 KiB
+            if (e != hipSuccess) return e;
             hipLaunchKernelGGL(kernel, grid, dim3(512), lds, st, P);
             return hipGetLastError();
         };

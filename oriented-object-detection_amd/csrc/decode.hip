@@ -8,11 +8,11 @@
 // SURVEY.md Appendix A2/A4/A6.  These are HBM/latency-bound kernels: one workgroup per tile, candidates kept in
 // anchor order by ballot/prefix-sum compaction so that ties sort exactly like a stable argsort.
 #include <algorithm>
-#include <mutex>
 #include <cmath>
 #include <cstdlib>
 
 #include "ctx.h"
+#include "launchcfg.h"
 #include "post_device.h"
 
 namespace obb {
@@ -1155,11 +1155,7 @@ int obb_decode_nms_gate(obb_ctx *ctx, const float *head, const float *cmax, int3
     // form stops each tile at its max_det-th survivor (3.87 -> 1.1 ms).  The threshold is the caller's conf, the only thing the host knows.
     if ((size_t)NPmax * 8 <= 128 * 1024 && conf_thres < 0.05f) {
         // round form: sort once, then rows in score order, kRoundRows at a time, until every tile has its max_det survivors
-        static bool attr_set = false;
-        if (!attr_set) {
-            OBB_HIP(ctx, hipFuncSetAttribute((const void *)k_heavy_bitonic, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            attr_set = true;
-        }
+        OBB_HIP(ctx, allow_dyn_lds((const void *)k_heavy_bitonic, 128 * 1024));
         hipLaunchKernelGGL(k_heavy_bitonic, dim3((unsigned)std::min<int>(B, 256)), dim3(1024), (size_t)NPmax * 8, st, A, max_det, S);
         OBB_LAUNCH_CHECK(ctx);
         // equal rounds of kRoundRows (a multiple of k_heavy_out's 256-row chunks), one workgroup column per tile: a saturated tile has its
@@ -1177,20 +1173,11 @@ int obb_decode_nms_gate(obb_ctx *ctx, const float *head, const float *cmax, int3
         const size_t AS = (size_t)((A + 3) & ~3);
         const size_t lds = ((AS * 37 + 15) & ~(size_t)15) + (kHeavyBins + 8) * 4;  // seven covariance terms + score + survivor list + class per candidate | score histogram
         if (lds <= 156 * 1024) {  // every candidate of a tile fits the LDS: two launches, the output included
-            static std::mutex mu;
-            static size_t attr_lds = 0;
-            {
-                std::lock_guard<std::mutex> lock(mu);
-                if (lds > attr_lds) {
-                    OBB_HIP(ctx, hipFuncSetAttribute((const void *)k_heavy_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    attr_lds = lds;
-                }
-            }
+            OBB_HIP(ctx, allow_dyn_lds((const void *)k_heavy_rows, lds));  // (grows with the largest A seen on this device)
             hipLaunchKernelGGL(k_heavy_prep, dim3((unsigned)slots, (unsigned)std::min<int64_t>(16, cdiv(A, 256))), dim3(256), 0, st, head, A, nc, h, w, S);
             OBB_LAUNCH_CHECK(ctx);
-            int ncu = 0, dev = 0;
-            OBB_HIP(ctx, hipGetDevice(&dev));
-            OBB_HIP(ctx, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            int ncu = 0;
+            OBB_HIP(ctx, cu_count(&ncu));
             const int resident = std::max(1, ncu) * (int)std::max<size_t>(1, (160 * 1024) / (lds + 128));
             hipLaunchKernelGGL(k_heavy_rows, dim3((unsigned)std::min<int64_t>(resident, (int64_t)B * kHeavyShareMax)), dim3(kHeavyRowsThreads), lds, st, A, conf_thres, iou_thres,
                                max_det, kq, bdmax, S, out, count);
@@ -1230,11 +1217,7 @@ int obb_decode_nms_full(obb_ctx *ctx, const float *head, int32_t B, int32_t h, i
     OBB_LAUNCH_CHECK(ctx);
     size_t lds = (size_t)A * (sizeof(RBox) + 12 + 3) + 96;
     if (lds <= 159 * 1024) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            OBB_HIP(ctx, hipFuncSetAttribute((const void *)k_nms_tile<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
-            attr_set = true;
-        }
+        OBB_HIP(ctx, allow_dyn_lds((const void *)k_nms_tile<true>, 159 * 1024));
         hipLaunchKernelGGL(k_nms_tile<true>, dim3((unsigned)B), dim3(1024), lds, st, (const float *)pred, A, nc, conf_thres, iou_thres, max_det,
                            30000, far_apart_factor(iou_thres), probiou_bdmax(iou_thres), S, out, count, 0);
     } else {

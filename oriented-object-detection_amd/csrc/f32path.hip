@@ -18,13 +18,12 @@
 //     (596 -> 771 us per 256 tiles).
 //   * epilogue: + bias, SiLU (v_exp_f32 + v_rcp_f32, 1 ulp each: silu32 below), + residual, fp32 store into a channel slice of the consumer's buffer.
 #include "f32path.h"
+#include "launchcfg.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 
 namespace obb {
 
@@ -783,12 +782,8 @@ size_t conv32_lds_bytes(const Conv32Launch &L) {
 template <int KS, int MFM, int WC, bool IN_U8, bool VCAT, int TAIL, bool DW = false, int NC = 1, bool BLK = false, bool AINIT = false>
 static hipError_t launch32_k(const C32Params &P0, dim3 grid, size_t lds, hipStream_t st) {
     const void *fn = (const void *)k_conv_f32<KS, MFM, WC, kNW, IN_U8, VCAT, TAIL, DW, NC, BLK, AINIT>;
-    static bool attr_set = false;  // (per instantiation) up to 80 KiB of dynamic LDS: two workgroups per CU
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = allow_dyn_lds(fn, 80 * 1024);  // (per device and instantiation) up to 80 KiB of dynamic LDS: two workgroups per CU
+    if (e != hipSuccess) return e;
     C32Params P = P0;
     P.tstep = 0;
     // (measured per layer, 512 tiles: layers of 1-3 stages per tile gain 3-18 % -- model.2.cv2 867 -> 707 us -- longer tiles hide their
@@ -798,22 +793,10 @@ static hipError_t launch32_k(const C32Params &P0, dim3 grid, size_t lds, hipStre
 #endif
     if (TAIL == 0 && !DW && !IN_U8 && P0.tstep != 0 && P0.nstage <= OBB_XT_MAX_STAGES) {  // (launch_conv32 passes Conv32Launch::xtile in tstep)
         // cross-tile pipeline: a grid of resident workgroups, each walking ~equally many tiles (see XT in the kernel)
-        static std::map<size_t, int> occ;  // resident workgroups per CU of this instantiation, by dynamic LDS size
-        static int ncu = 0;
-        static std::mutex mu;  // (contexts of different host threads launch through the same cache)
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = occ.find(lds);
-        if (it == occ.end()) {
-            int n = 0, dev = 0;
-            hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kNW * 64, lds);
-            if (e != hipSuccess) return e;
-            if (!ncu) {
-                if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-            }
-            it = occ.emplace(lds, std::max(1, n)).first;
-        }
+        int n = 0, ncu = 0;  // resident workgroups per CU of this instantiation at this dynamic LDS size, CUs of this device
+        if ((e = resident_blocks(fn, kNW * 64, lds, &n)) != hipSuccess || (e = cu_count(&ncu)) != hipSuccess) return e;
         const int64_t tiles8 = ((int64_t)P.ntiles + 7) / 8;
-        const int64_t slots_max = std::max<int64_t>(1, (int64_t)it->second * ncu / (8 * P.ncb));
+        const int64_t slots_max = std::max<int64_t>(1, (int64_t)std::max(1, n) * ncu / (8 * P.ncb));
         const int64_t rounds = (tiles8 + slots_max - 1) / slots_max;
         if (rounds > 1) {
             const int64_t slots = (tiles8 + rounds - 1) / rounds;
@@ -1501,13 +1484,9 @@ hipError_t launch_attention_f32(const TensorRef &qkv, const TensorRef &out, int 
     if (use_mfma && N <= 192) {
         const int NP = (N + 15) & ~15;
         const size_t lds_m = sizeof(float) * ((size_t)NP * 36 + (size_t)NP * 64);  // <= 75 KiB
-        static bool attr_m = false;
-        if (!attr_m) {
-            hipError_t e = hipFuncSetAttribute((const void *)k_attention_mfma_f32<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_attention_mfma_f32<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess) return e;
-            attr_m = true;
-        }
+        hipError_t e = allow_dyn_lds((const void *)k_attention_mfma_f32<12>, 96 * 1024);
+        if (e == hipSuccess) e = allow_dyn_lds((const void *)k_attention_mfma_f32<4>, 96 * 1024);
+        if (e != hipSuccess) return e;
         const float scale_m = (float)(1.0 / sqrt((double)kd));
         if (NP <= 64) hipLaunchKernelGGL((k_attention_mfma_f32<4>), dim3((unsigned)(B * nh)), dim3(256), lds_m, st, qkv, out, N, nh, scale_m);
         else hipLaunchKernelGGL((k_attention_mfma_f32<12>), dim3((unsigned)(B * nh)), dim3(256), lds_m, st, qkv, out, N, nh, scale_m);
@@ -1515,12 +1494,8 @@ hipError_t launch_attention_f32(const TensorRef &qkv, const TensorRef &out, int 
     }
     const size_t lds = sizeof(float) * ((size_t)N * 32 + (size_t)N * 64);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_attention_f32<32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = allow_dyn_lds((const void *)k_attention_f32<32, 64>, 160 * 1024);
+    if (e != hipSuccess) return e;
     const int nsplit = (N + 63) / 64;  // one wave of queries per workgroup
     const float scale = (float)(1.0 / sqrt((double)kd));
     hipLaunchKernelGGL((k_attention_f32<32, 64>), dim3((unsigned)(B * nh * nsplit)), dim3(64), lds, st, qkv, out, N, nh, nsplit, scale);

@@ -17,6 +17,7 @@
 //   tail     a lane's 8 outputs of a pixel are one B-operand fragment of the 1x1 (k = channel g*8 + j): straight from registers;
 //            its 8 results are 16 contiguous bytes, the four lanes of a pixel 64: stored from registers
 #include "front.h"
+#include "launchcfg.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -310,12 +311,8 @@ hipError_t launch_front(const FrontLaunch &L, hipStream_t st) {
     const dim3 grid((unsigned)((nt + P.tpw - 1) / P.tpw));
     const size_t lds = (size_t)kFrontActBytes + (size_t)kIW * kCvtPitch;
     auto go = [&](auto kernel) -> hipError_t {
-        static std::vector<const void *> attr_set;  // (the instantiations share one function-pointer type: keyed by address)
-        if (std::find(attr_set.begin(), attr_set.end(), (const void *)kernel) == attr_set.end()) {
-            hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-            if (e != hipSuccess) return e;
-            attr_set.push_back((const void *)kernel);
-        }
+        hipError_t e = allow_dyn_lds((const void *)kernel, 64 * 1024);
+        if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, P);
         return hipGetLastError();
     };

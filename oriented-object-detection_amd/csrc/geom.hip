@@ -10,9 +10,9 @@
 // All of this is byte/compare work on KB..MB inputs: the kernels are HBM/latency bound, so the design rules are
 // coalesced SoA streams, LDS-resident segments, wave64 ballots/shuffles for the serial scans, and no GEMM shaping.
 #include <algorithm>
-#include <mutex>
 
 #include "ctx.h"
+#include "launchcfg.h"
 #include "geom_device.h"
 #include "post_device.h"
 
@@ -1613,13 +1613,6 @@ int obb_nms_reduce(obb_ctx *ctx, const uint64_t *mask, int64_t n, uint8_t *keep,
 int obb_merge_detections(obb_ctx *ctx, const double *boxes, const int32_t *cls, const double *conf, int64_t n, double thr,
                          int32_t *order, uint8_t *keep, int32_t *n_keep, obb_stream_t s);
 
-// workgroups of the 512-row form the chip holds at once (its LDS: one per CU)
-static int merge_resident(obb_ctx *) {
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1) ncu = 64;
-    return ncu;
-}
-
 int obb_merge_segments(obb_ctx *ctx, const double *boxes, const int32_t *cls, const double *conf, const int32_t *seg_off,
                        int32_t nseg, int64_t n, double thr, int32_t *order, uint8_t *keep, obb_stream_t s) {
     OBB_REQUIRE(ctx, ctx && nseg >= 0 && n >= 0, "obb_merge_segments: bad arguments");
@@ -1632,9 +1625,12 @@ int obb_merge_segments(obb_ctx *ctx, const double *boxes, const int32_t *cls, co
     OBB_HIP(ctx, hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st));
     hipLaunchKernelGGL(k_merge_segments_wave, dim3((unsigned)nseg), dim3(64), 0, st, boxes, cls, conf, seg_off, seg_off + 1, thr, order, keep, (int32_t *)nullptr,
                        status + 64, status + 1);
-    if (n > kSegWave)  // (some segment may be longer than a wave takes)
-        hipLaunchKernelGGL((k_merge_segments<kSegMax, 1024, kSegPairCap>), dim3((unsigned)std::min<int>(nseg, merge_resident(ctx))), dim3(1024), 0, st, boxes, cls, conf,
+    if (n > kSegWave) {  // (some segment may be longer than a wave takes)
+        int ncu = 0;  // workgroups of the 512-row form the chip holds at once (its LDS: one per CU)
+        OBB_HIP(ctx, cu_count(&ncu));
+        hipLaunchKernelGGL((k_merge_segments<kSegMax, 1024, kSegPairCap>), dim3((unsigned)std::min<int>(nseg, ncu)), dim3(1024), 0, st, boxes, cls, conf,
                            seg_off, seg_off + 1, thr, order, keep, (int32_t *)nullptr, status, kSegWave, 0, status + 64, status + 1);
+    }
     OBB_LAUNCH_CHECK(ctx);
     if (n <= kSegMax) return OBB_OK;  // no segment can be longer than the LDS-resident kernel takes
     // Segments above kSegMax rows were flagged and left untouched by the kernel (a tile with more than 512 detections: max_det > 512, or
@@ -1700,13 +1696,8 @@ int obb_merge_detections(obb_ctx *ctx, const double *boxes, const int32_t *cls, 
     const size_t lds_states = (size_t)cdiv(n, 4) * 4;
     const size_t lds_lazy = (size_t)W * 8 + 64;
     OBB_REQUIRE(ctx, lds_lazy <= 150 * 1024, "obb_merge_detections: n=%lld exceeds the 1.2M rows the LDS-resident scans hold", (long long)n);
-    static std::once_flag attr_once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(attr_once, [] {
-        attr_err = hipFuncSetAttribute((const void *)k_nms_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (attr_err == hipSuccess) attr_err = hipFuncSetAttribute((const void *)k_nms_lazy, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    });
-    OBB_HIP(ctx, attr_err);
+    OBB_HIP(ctx, allow_dyn_lds((const void *)k_nms_resolve, 150 * 1024));
+    OBB_HIP(ctx, allow_dyn_lds((const void *)k_nms_lazy, 150 * 1024));
     unsigned int *ecount = (unsigned int *)ctx->workspace(WS_NMS_D, 256);
     if (!ecount) return set_error(ctx, OBB_ERR_HIP, "obb_merge_detections: workspace allocation failed");
     OBB_HIP(ctx, hipMemsetAsync(ecount, 0, sizeof(unsigned int), st));
@@ -1848,9 +1839,12 @@ int obb_tile_survivors(obb_ctx *ctx, const float *det, const int32_t *count, int
     OBB_HIP(ctx, hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st));
     hipLaunchKernelGGL(k_tile_stage, dim3((unsigned)B), dim3(256), 0, st, det, count, (int)max_det, lb, tile_ids, rects, (int)margin, (int)strike_cls, S);
     hipLaunchKernelGGL(k_merge_segments_wave, dim3((unsigned)B), dim3(64), 0, st, S.gb, S.cls, S.conf, S.lo, S.hi, iou_thr, order, keep, nkeep, status + 64, status + 1);
-    if (max_det > kSegWave)  // (tiles with more than 64 survivors: resident workgroups walk the list the wave kernel left)
-        hipLaunchKernelGGL((k_merge_segments<kSegMax, 1024, kSegPairCap>), dim3((unsigned)std::min<int>(B, merge_resident(ctx))), dim3(1024), 0, st, S.gb, S.cls, S.conf, S.lo,
+    if (max_det > kSegWave) {  // (tiles with more than 64 survivors: resident workgroups walk the list the wave kernel left)
+        int ncu = 0;  // the 512-row form's LDS: one workgroup per CU
+        OBB_HIP(ctx, cu_count(&ncu));
+        hipLaunchKernelGGL((k_merge_segments<kSegMax, 1024, kSegPairCap>), dim3((unsigned)std::min<int>(B, ncu)), dim3(1024), 0, st, S.gb, S.cls, S.conf, S.lo,
                            S.hi, iou_thr, order, keep, nkeep, status, kSegWave, 0, status + 64, status + 1);
+    }
     hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, nkeep, (int)B, tile_off, n_records);
     hipLaunchKernelGGL(k_tile_emit, dim3((unsigned)B), dim3(64), 0, st, S, order, keep, tile_off, tile_ids, records);
     OBB_LAUNCH_CHECK(ctx);

@@ -3,6 +3,7 @@
 // 2-head C2PSA attention.  All are HBM/LDS-bound VALU kernels on NHWC bf16 with 16 B (8-channel) accesses; each
 // writes straight into the channel slice of its consumer's concat buffer.
 #include "nnops.h"
+#include "launchcfg.h"
 
 #include <cstdlib>
 
@@ -394,12 +395,8 @@ hipError_t launch_upsample2(const TensorRef &in, const TensorRef &out, int B, in
 
 template <bool F16>
 static hipError_t launch_attention_t(const TensorRef &qkv, const TensorRef &out, int B, int N, int nh, int kd, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_attention<32, 64, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    hipError_t e = allow_dyn_lds((const void *)k_attention<32, 64, F16>, 160 * 1024);
+    if (e != hipSuccess) return e;
     float scale = (float)(1.0 / sqrt((double)kd));  // python: key_dim ** -0.5 evaluated in double, applied to an fp32 tensor
     hipLaunchKernelGGL((k_attention<32, 64, F16>), dim3((unsigned)(B * nh)), dim3(256), lds, st, qkv, out, N, nh, scale);
     return hipGetLastError();

@@ -21,10 +21,9 @@
 // Row order of the weights (pack_pw32_weights): a lane ends with 16 consecutive output channels of its pixel (64 contiguous bytes / two
 // 8-channel blocks).
 #include "pw32.h"
+#include "launchcfg.h"
 
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 namespace obb {
 
@@ -199,24 +198,12 @@ std::vector<float> pack_pw32_weights(const float *w, int cout, int cin, const in
 template <int NW, bool RAW>
 static hipError_t launch_pw(const Pw32Params &P0, size_t lds, hipStream_t st) {
     const void *fn = (const void *)k_pw_f32<NW, RAW>;
-    static std::mutex mu;
-    static std::map<std::pair<int, size_t>, int> occ;  // (device, LDS bytes) -> resident workgroups on the chip
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    int resident = 0;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        auto it = occ.find({dev, lds});
-        if (it == occ.end()) {
-            int n = 0, ncu = 0;
-            if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)) != hipSuccess) return e;
-            if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, NW * 64, lds)) != hipSuccess) return e;
-            if ((e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-            it = occ.emplace(std::make_pair(dev, lds), std::max(1, n) * std::max(1, ncu)).first;
-        }
-        resident = it->second;
-    }
+    int n = 0, ncu = 0;
+    hipError_t e;
+    if ((e = allow_dyn_lds(fn, 128 * 1024)) != hipSuccess) return e;
+    if ((e = resident_blocks(fn, NW * 64, lds, &n)) != hipSuccess) return e;
+    if ((e = cu_count(&ncu)) != hipSuccess) return e;
+    const int resident = std::max(1, n) * std::max(1, ncu);  // resident workgroups on the chip
     Pw32Params P = P0;
     P.nfrag = (int)(((int64_t)P.npix + 15) / 16);
     // walkers (workgroups per cout block): at most the resident workgroups, at least three fragments per wave, in units of 8 (the XCD order)

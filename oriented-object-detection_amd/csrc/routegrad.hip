@@ -17,10 +17,9 @@
 //   upcat           out = cat(nearest_upsample_up(a), b) along C, up in {1, 2}; backward da[p] = fp32 sum of the up^2 copies (dy then dx),
 //                   db = the b slice; accum: the existing bf16 value is the first term of the fp32 sum.  One rounding per result.
 #include <algorithm>
-#include <mutex>
-#include <set>
 
 #include "ctx.h"
+#include "launchcfg.h"
 
 namespace obb {
 namespace {
@@ -272,17 +271,7 @@ int obb_sppf_pools_fwd_bf16(obb_ctx *ctx, const uint16_t *x, int32_t B, int32_t 
 int obb_sppf_pools_bwd_bf16(obb_ctx *ctx, const uint16_t *cat, const uint16_t *dcat, int32_t B, int32_t H, int32_t W, int32_t C, uint16_t *dx, obb_stream_t s) {
     if (int rc = pools_check(ctx, "obb_sppf_pools_bwd_bf16", B, H, W, C)) return rc;
     OBB_REQUIRE(ctx, cat && dcat && dx, "obb_sppf_pools_bwd_bf16: NULL buffer");
-    {  // more than 64 KiB of dynamic LDS has to be allowed once on every device the kernel runs on (the current one: pw32.hip's rule)
-        static std::mutex mu;
-        static std::set<int> allowed;
-        int dev = 0;
-        OBB_HIP(ctx, hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(mu);
-        if (!allowed.count(dev)) {
-            OBB_HIP(ctx, hipFuncSetAttribute((const void *)k_sppf_pools_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, kPoolMaxElems * kPoolBwdBytes));
-            allowed.insert(dev);
-        }
-    }
+    OBB_HIP(ctx, allow_dyn_lds((const void *)k_sppf_pools_bwd, kPoolMaxElems * kPoolBwdBytes));  // more than 64 KiB of dynamic LDS
     const int share = pool_share(H, W), ngrp = (int)cdiv(C / 8, share);
     const size_t lds = (size_t)H * W * share * kPoolBwdBytes;
     hipLaunchKernelGGL(k_sppf_pools_bwd, dim3((unsigned)((int64_t)B * ngrp)), dim3(256), lds, (hipStream_t)s, cat, dcat, (int)H, (int)W, (int)C, share, ngrp, dx);
