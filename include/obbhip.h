@@ -254,6 +254,31 @@ int obb_upcat_fwd_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int32
                        uint16_t *out, obb_stream_t s);
 int obb_upcat_bwd_bf16(obb_ctx *ctx, const uint16_t *dout, int32_t B, int32_t H, int32_t W, int32_t Ca, int32_t Cb, int32_t up, uint16_t *da,
                        uint16_t *db, int32_t accum_a, int32_t accum_b, obb_stream_t s);
+/* Depthwise 3x3 Conv blocks in training mode (`model.train(...)`, Train_OBB.py:796-841 -> ultralytics DWConv / Conv(g = c): the head's class
+ * branch model.23.cv3.i.{0,1}.0 and C2PSA's attn.pe): stride 1, pad 1 (zeros), groups = C, no bias, no activation.  x, z, dz, dx bf16 NHWC
+ * [B][H][W][C] on the device, C % 8 == 0 (>= 8), B, H, W >= 1, no map-size limit.  w: the fp32 MASTER weights [C][1][3][3] on the device; every
+ * kernel rounds them to bf16 (nearest even) as it loads them (w~ below: what bf16 autocast hands F.conv2d) -- there is no pack step.  Products and
+ * sums are fp32, taps are added in (ky, kx) ascending order starting from 0, one bf16 rounding at each bf16 store; dw is fp32 [C][1][3][3].
+ * obb_dwconv3_fwd_bf16: z[b,i,j,c] = sum_{ky,kx} w~[c,ky,kx] x[b, i+ky-1, j+kx-1, c].
+ * obb_dwconv3_bwd_bf16: BOTH gradients from one pass over x and dz:
+ *   dx[b,i,j,c] = sum_{ky,kx} w~[c,ky,kx] dz[b, i-ky+1, j-kx+1, c];   dw[c,ky,kx] = sum_{b,i,j} dz[b,i,j,c] x[b, i+ky-1, j+kx-1, c].
+ *   dx or dw NULL: that half is skipped and nothing of it is written (x may then be NULL for dx alone, w for dw alone); the half that is
+ *   computed is bit-equal to the fused call's.  Both NULL: OBB_ERR_INVALID.  dw: per-lane fp32 sums, a fixed LDS tree over the lanes of a channel
+ *   chunk, one fp32 slab per workgroup in a ctx workspace slot, a second launch that adds the slabs in index order.  No atomics: results are
+ *   bit-reproducible, also after the workspace slot has grown.
+ * obb_dwconv3_bwd_geometry: host only, no context.  out = {rows per stripe, pixels per lane run, number of slabs, L} -- the split the launcher
+ *   itself uses for that shape (it calls the same function); L = the longest chain of fp32 additions a dw element passes through (lane run +
+ *   LDS tree depth + slab combine).  OBB_ERR_INVALID on a bad shape.
+ * obb_bn_fwd_bf16 / obb_bn_bwd_bf16: obb_bn_silu_fwd_bf16 / obb_bn_silu_bwd_bf16 with `act`: 1 = SiLU (bit-identical to those), 0 = identity
+ *   (a = gamma xhat + beta; g = da) for Conv(act=False). */
+int obb_dwconv3_fwd_bf16(obb_ctx *ctx, const uint16_t *x, const float *w, int32_t B, int32_t H, int32_t W, int32_t C, uint16_t *z, obb_stream_t s);
+int obb_dwconv3_bwd_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dz, const float *w, int32_t B, int32_t H, int32_t W, int32_t C, uint16_t *dx,
+                         float *dw, obb_stream_t s);
+int obb_dwconv3_bwd_geometry(int32_t B, int32_t H, int32_t W, int32_t C, int32_t out[4]);
+int obb_bn_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps, float momentum,
+                    float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, int32_t act, obb_stream_t s);
+int obb_bn_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
+                    const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, int32_t act, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S1: model(...) -> results[0].obb  (Detect_OBB.py:26,81-83,228-231) */
 /* Weight blob ("OBBW" format, produced by the Python side from BN-folded conv weights) for a

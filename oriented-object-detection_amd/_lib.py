@@ -58,6 +58,11 @@ SIGNATURES = {
     "obb_sppf_pools_bwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_upcat_fwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_upcat_bwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, C.c_int32, C.c_int32, _V],
+    "obb_dwconv3_fwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_dwconv3_bwd_bf16": [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],
+    "obb_dwconv3_bwd_geometry": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip],
+    "obb_bn_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, C.c_int32, _V],
+    "obb_bn_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, C.c_int32, _V],
     "obb_gather_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V, _V],
     "obb_letterbox": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V,
                       C.c_int32, C.c_int32, _V],

@@ -3,7 +3,7 @@
 //
 //   forward   mean_c, var_c = batch mean / biased variance of z[:, c];  invstd_c = 1 / sqrt(var_c + eps)
 //             running_mean = (1 - m) running_mean + m mean;  running_var = (1 - m) running_var + m var N / (N - 1)   (unbiased, as torch)
-//             a = silu(gamma (z - mean) invstd + beta), rounded to bf16 once
+//             a = silu(gamma (z - mean) invstd + beta), rounded to bf16 once   (act = 0, obb_bn_fwd_bf16 / obb_bn_bwd_bf16: no SiLU, g = da)
 //   backward  xhat = (z - mean) invstd, y = gamma xhat + beta recomputed from z (no normalised tensor is stored);  g = da silu'(y)
 //             dbeta = sum g,  dgamma = sum g xhat,  dz = gamma invstd (g - dbeta / N - xhat dgamma / N), rounded to bf16 once
 //
@@ -161,7 +161,8 @@ __global__ __launch_bounds__(256) void k_bn_stats_final(const unsigned short *__
     running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (m2 / (N - 1.0f));
 }
 
-// forward, pass 3: a = silu(gamma (z - mean) invstd + beta), one 16-byte chunk per thread and step
+// forward, pass 3: a = silu(gamma (z - mean) invstd + beta) (ACT; else the BatchNorm output itself), one 16-byte chunk per thread and step
+template <bool ACT>
 __global__ __launch_bounds__(256) void k_bn_silu_apply(const unsigned short *__restrict__ z, int64_t nchunk, int C8, const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, const float *__restrict__ mean, const float *__restrict__ invstd,
                                                        unsigned short *__restrict__ a) {
@@ -170,12 +171,16 @@ __global__ __launch_bounds__(256) void k_bn_silu_apply(const unsigned short *__r
         float v[8];
         unpack8(reinterpret_cast<const uint4 *>(z)[i], v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = silu_f(gamma[c0 + j] * ((v[j] - mean[c0 + j]) * invstd[c0 + j]) + beta[c0 + j]);
+        for (int j = 0; j < 8; ++j) {
+            const float y = gamma[c0 + j] * ((v[j] - mean[c0 + j]) * invstd[c0 + j]) + beta[c0 + j];
+            v[j] = ACT ? silu_f(y) : y;
+        }
         reinterpret_cast<uint4 *>(a)[i] = pack8(v);
     }
 }
 
-// g = da silu'(y) and xhat of the 8 channels of one chunk
+// g = da silu'(y) (ACT; else g = da) and xhat of the 8 channels of one chunk
+template <bool ACT>
 __device__ __forceinline__ void bn_bwd_terms(const uint4 zv, const uint4 dav, const float ga[8], const float be[8], const float mu[8], const float is[8],
                                              float g[8], float xh[8]) {
     float zf[8], df[8];
@@ -184,12 +189,17 @@ __device__ __forceinline__ void bn_bwd_terms(const uint4 zv, const uint4 dav, co
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         xh[j] = (zf[j] - mu[j]) * is[j];
-        const float y = ga[j] * xh[j] + be[j], sg = 1.0f / (1.0f + expf(-y));
-        g[j] = df[j] * (sg * (1.0f + y * (1.0f - sg)));
+        if (ACT) {
+            const float y = ga[j] * xh[j] + be[j], sg = 1.0f / (1.0f + expf(-y));
+            g[j] = df[j] * (sg * (1.0f + y * (1.0f - sg)));
+        } else {
+            g[j] = df[j];
+        }
     }
 }
 
 // backward, pass 1: per pixel block sum g and sum g xhat into the slab
+template <bool ACT>
 __global__ __launch_bounds__(256) void k_bn_bwd_part(const unsigned short *__restrict__ z, const unsigned short *__restrict__ da, int64_t npix, int C, int64_t PB,
                                                      int CW, int RP, const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ mean,
                                                      const float *__restrict__ invstd, float *__restrict__ slab_g, float *__restrict__ slab_gx) {
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_part(const unsigned short *__res
     }
     if (act)
         for (int64_t p = p0 + row; p < p1; p += RP) {
-            bn_bwd_terms(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), *reinterpret_cast<const uint4 *>(da + p * C + c8 * 8), ga, be, mu, is, g, xh);
+            bn_bwd_terms<ACT>(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), *reinterpret_cast<const uint4 *>(da + p * C + c8 * 8), ga, be, mu, is, g, xh);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { sg[j] += g[j]; sgx[j] += g[j] * xh[j]; }
         }
@@ -236,6 +246,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_final(const float *__restrict__ 
 }
 
 // backward, pass 3: dz = gamma invstd (g - dbeta / N - xhat dgamma / N)
+template <bool ACT>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const unsigned short *__restrict__ z, const unsigned short *__restrict__ da, int64_t nchunk, int C8, float inv_n,
                                                       const float *__restrict__ gamma, const float *__restrict__ beta, const float *__restrict__ mean,
                                                       const float *__restrict__ invstd, const float *__restrict__ dgamma, const float *__restrict__ dbeta,
@@ -245,7 +256,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const unsigned short *__re
         float ga[8], be[8], mu[8], is[8], g[8], xh[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) { ga[j] = gamma[c0 + j]; be[j] = beta[c0 + j]; mu[j] = mean[c0 + j]; is[j] = invstd[c0 + j]; }
-        bn_bwd_terms(reinterpret_cast<const uint4 *>(z)[i], reinterpret_cast<const uint4 *>(da)[i], ga, be, mu, is, g, xh);
+        bn_bwd_terms<ACT>(reinterpret_cast<const uint4 *>(z)[i], reinterpret_cast<const uint4 *>(da)[i], ga, be, mu, is, g, xh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) g[j] = ga[j] * is[j] * (g[j] - dbeta[c0 + j] * inv_n - xh[j] * (dgamma[c0 + j] * inv_n));
         reinterpret_cast<uint4 *>(dz)[i] = pack8(g);
@@ -258,46 +269,79 @@ static unsigned elementwise_grid(int64_t nchunk) { return (unsigned)std::max<int
 
 using namespace obb;
 
-extern "C" {
-
-int obb_bn_silu_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps, float momentum,
-                         float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, obb_stream_t s) {
-    OBB_REQUIRE(ctx, ctx && C > 0 && C % 8 == 0, "obb_bn_silu_fwd_bf16: C = %d must be a positive multiple of 8", (int)C);
-    OBB_REQUIRE(ctx, npix >= 2 && npix < (1ll << 31), "obb_bn_silu_fwd_bf16: npix = %lld: training statistics need 2 <= npix < 2^31", (long long)npix);
-    OBB_REQUIRE(ctx, eps > 0.f && momentum >= 0.f && momentum <= 1.f, "obb_bn_silu_fwd_bf16: bad eps / momentum");
-    OBB_REQUIRE(ctx, z && gamma && beta && running_mean && running_var && mean && invstd && a, "obb_bn_silu_fwd_bf16: NULL buffer");
+// the bodies of the entry points; act: SiLU after the BatchNorm (the Conv block) or none (Conv(act=False)), a template flag of the kernels
+static int bn_fwd_impl(obb_ctx *ctx, const char *fn, bool act, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps,
+                       float momentum, float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && C > 0 && C % 8 == 0, "%s: C = %d must be a positive multiple of 8", fn, (int)C);
+    OBB_REQUIRE(ctx, npix >= 2 && npix < (1ll << 31), "%s: npix = %lld: training statistics need 2 <= npix < 2^31", fn, (long long)npix);
+    OBB_REQUIRE(ctx, eps > 0.f && momentum >= 0.f && momentum <= 1.f, "%s: bad eps / momentum", fn);
+    OBB_REQUIRE(ctx, z && gamma && beta && running_mean && running_var && mean && invstd && a, "%s: NULL buffer", fn);
     hipStream_t st = (hipStream_t)s;
     const BnGeo g = bn_geo(npix, C);
     float *slab = (float *)ctx->workspace(WS_TRAIN_E, (size_t)2 * g.nbx * C * 4);
-    if (!slab) return set_error(ctx, OBB_ERR_HIP, "obb_bn_silu_fwd_bf16: workspace allocation failed");
+    if (!slab) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
     float *slab_m2 = slab + (size_t)g.nbx * C;
     hipLaunchKernelGGL(k_bn_stats_part, dim3((unsigned)g.nbx, (unsigned)g.ny), dim3(256), 0, st, z, npix, (int)C, g.PB, g.CW, g.RP, slab, slab_m2);
     hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, z, slab, slab_m2, g.nbx, g.PB, npix, (int)C, eps, momentum, running_mean,
                        running_var, mean, invstd);
     const int64_t nchunk = npix * g.C8;
-    hipLaunchKernelGGL(k_bn_silu_apply, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, nchunk, g.C8, gamma, beta, mean, invstd, a);
+    if (act)
+        hipLaunchKernelGGL(k_bn_silu_apply<true>, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, nchunk, g.C8, gamma, beta, mean, invstd, a);
+    else
+        hipLaunchKernelGGL(k_bn_silu_apply<false>, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, nchunk, g.C8, gamma, beta, mean, invstd, a);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }
 
-int obb_bn_silu_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta, const float *mean,
-                         const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, obb_stream_t s) {
-    OBB_REQUIRE(ctx, ctx && C > 0 && C % 8 == 0, "obb_bn_silu_bwd_bf16: C = %d must be a positive multiple of 8", (int)C);
-    OBB_REQUIRE(ctx, npix >= 2 && npix < (1ll << 31), "obb_bn_silu_bwd_bf16: npix = %lld: training statistics need 2 <= npix < 2^31", (long long)npix);
-    OBB_REQUIRE(ctx, z && da && gamma && beta && mean && invstd && dgamma && dbeta && dz, "obb_bn_silu_bwd_bf16: NULL buffer");
+static int bn_bwd_impl(obb_ctx *ctx, const char *fn, bool act, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
+                       const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && C > 0 && C % 8 == 0, "%s: C = %d must be a positive multiple of 8", fn, (int)C);
+    OBB_REQUIRE(ctx, npix >= 2 && npix < (1ll << 31), "%s: npix = %lld: training statistics need 2 <= npix < 2^31", fn, (long long)npix);
+    OBB_REQUIRE(ctx, z && da && gamma && beta && mean && invstd && dgamma && dbeta && dz, "%s: NULL buffer", fn);
     hipStream_t st = (hipStream_t)s;
     const BnGeo g = bn_geo(npix, C);
     float *slab = (float *)ctx->workspace(WS_TRAIN_E, (size_t)2 * g.nbx * C * 4);
-    if (!slab) return set_error(ctx, OBB_ERR_HIP, "obb_bn_silu_bwd_bf16: workspace allocation failed");
+    if (!slab) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
     float *slab_gx = slab + (size_t)g.nbx * C;
-    hipLaunchKernelGGL(k_bn_bwd_part, dim3((unsigned)g.nbx, (unsigned)g.ny), dim3(256), 0, st, z, da, npix, (int)C, g.PB, g.CW, g.RP, gamma, beta, mean, invstd,
-                       slab, slab_gx);
+    const dim3 pgrid((unsigned)g.nbx, (unsigned)g.ny);
+    if (act)
+        hipLaunchKernelGGL(k_bn_bwd_part<true>, pgrid, dim3(256), 0, st, z, da, npix, (int)C, g.PB, g.CW, g.RP, gamma, beta, mean, invstd, slab, slab_gx);
+    else
+        hipLaunchKernelGGL(k_bn_bwd_part<false>, pgrid, dim3(256), 0, st, z, da, npix, (int)C, g.PB, g.CW, g.RP, gamma, beta, mean, invstd, slab, slab_gx);
     hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, slab, slab_gx, g.nbx, (int)C, dgamma, dbeta);
     const int64_t nchunk = npix * g.C8;
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, da, nchunk, g.C8, 1.0f / (float)npix, gamma, beta, mean, invstd,
-                       dgamma, dbeta, dz);
+    const float inv_n = 1.0f / (float)npix;
+    if (act)
+        hipLaunchKernelGGL(k_bn_bwd_apply<true>, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, da, nchunk, g.C8, inv_n, gamma, beta, mean, invstd, dgamma, dbeta, dz);
+    else
+        hipLaunchKernelGGL(k_bn_bwd_apply<false>, dim3(elementwise_grid(nchunk)), dim3(256), 0, st, z, da, nchunk, g.C8, inv_n, gamma, beta, mean, invstd, dgamma, dbeta, dz);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
+}
+
+extern "C" {
+
+int obb_bn_silu_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps, float momentum,
+                         float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, obb_stream_t s) {
+    return bn_fwd_impl(ctx, "obb_bn_silu_fwd_bf16", true, z, npix, C, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, a, s);
+}
+
+int obb_bn_silu_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta, const float *mean,
+                         const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, obb_stream_t s) {
+    return bn_bwd_impl(ctx, "obb_bn_silu_bwd_bf16", true, z, da, npix, C, gamma, beta, mean, invstd, dgamma, dbeta, dz, s);
+}
+
+// act = 1: the two entry points above; act = 0: BatchNorm alone (Conv(act=False): C2PSA's attn.pe)
+int obb_bn_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, const float *gamma, const float *beta, float eps, float momentum, float *running_mean,
+                    float *running_var, float *mean, float *invstd, uint16_t *a, int32_t act, obb_stream_t s) {
+    OBB_REQUIRE(ctx, act == 0 || act == 1, "obb_bn_fwd_bf16: act = %d must be 0 (identity) or 1 (SiLU)", (int)act);
+    return bn_fwd_impl(ctx, "obb_bn_fwd_bf16", act == 1, z, npix, C, gamma, beta, eps, momentum, running_mean, running_var, mean, invstd, a, s);
+}
+
+int obb_bn_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta, const float *mean,
+                    const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, int32_t act, obb_stream_t s) {
+    OBB_REQUIRE(ctx, act == 0 || act == 1, "obb_bn_bwd_bf16: act = %d must be 0 (identity) or 1 (SiLU)", (int)act);
+    return bn_bwd_impl(ctx, "obb_bn_bwd_bf16", act == 1, z, da, npix, C, gamma, beta, mean, invstd, dgamma, dbeta, dz, s);
 }
 
 }  // extern "C"

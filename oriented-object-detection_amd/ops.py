@@ -10,6 +10,7 @@ The plain functions below (`forward`, `decode_nms`, `merge_detections`, ...) are
 uses: they allocate the outputs and call `torch.ops.obbhip.*`.
 """
 import ctypes as C
+import ctypes as _ct  # (for functions whose own argument is named C)
 import os
 from typing import List, Optional
 
@@ -280,6 +281,32 @@ def _upcat_fwd(a: T, b: T, up: int, out: T) -> None:
 def _upcat_bwd(dout: T, H: int, W: int, Ca: int, up: int, da: Optional[T], db: Optional[T], accum_a: bool, accum_b: bool) -> None:
     _call("obb_upcat_bwd_bf16", ctx(dout.device), _p(dout), dout.shape[0], int(H), int(W), int(Ca), dout.shape[-1] - int(Ca), int(up), _p(da), _p(db),
           int(accum_a), int(accum_b), _stream())
+
+
+@_op("dwconv3_fwd", ("z",))
+def _dwconv3_fwd(x: T, w: T, z: T) -> None:
+    B, H, W, C = x.shape
+    _call("obb_dwconv3_fwd_bf16", ctx(x.device), _p(x), _p(w), B, H, W, C, _p(z), _stream())
+
+
+@_op("dwconv3_bwd", ("dx", "dw"))
+def _dwconv3_bwd(x: T, dz: T, w: T, dx: Optional[T], dw: Optional[T]) -> None:
+    B, H, W, C = dz.shape
+    _call("obb_dwconv3_bwd_bf16", ctx(dz.device), _p(x), _p(dz), _p(w), B, H, W, C, _p(dx), _p(dw), _stream())
+
+
+@_op("bn_fwd", ("running_mean", "running_var", "mean", "invstd", "a"))
+def _bn_fwd(z: T, gamma: T, beta: T, eps: float, momentum: float, running_mean: T, running_var: T, mean: T, invstd: T, a: T, act: bool) -> None:
+    C = z.shape[-1]
+    _call("obb_bn_fwd_bf16", ctx(z.device), _p(z), z.numel() // C, C, _p(gamma), _p(beta), float(eps), float(momentum), _p(running_mean), _p(running_var),
+          _p(mean), _p(invstd), _p(a), int(bool(act)), _stream())
+
+
+@_op("bn_bwd", ("dgamma", "dbeta", "dz"))
+def _bn_bwd(z: T, da: T, gamma: T, beta: T, mean: T, invstd: T, dgamma: T, dbeta: T, dz: T, act: bool) -> None:
+    C = z.shape[-1]
+    _call("obb_bn_bwd_bf16", ctx(z.device), _p(z), _p(da), z.numel() // C, C, _p(gamma), _p(beta), _p(mean), _p(invstd), _p(dgamma), _p(dbeta), _p(dz),
+          int(bool(act)), _stream())
 
 
 @_op("debug_activation", ("out",))
@@ -564,6 +591,21 @@ def bn_silu_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, moment
     return a, mean, invstd
 
 
+def bn_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, momentum=0.03, act=True):
+    """bn_silu_fwd_bf16 with the activation as an argument: act=True is that function (bit-identical), act=False the training-mode BatchNorm2d
+    alone (Conv(act=False)) -> (a bf16 like z, batch mean fp32 [C], invstd fp32 [C])."""
+    zz = _chk(z, torch.bfloat16, "z")
+    Cn = zz.shape[-1]
+    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var"))]
+    if any(t.numel() != Cn for t in vecs):
+        raise ValueError("bn_fwd_bf16: per-channel vectors must have C entries")
+    a = torch.empty_like(zz)
+    mean = torch.empty(Cn, dtype=torch.float32, device=zz.device)
+    invstd = torch.empty_like(mean)
+    _O.bn_fwd(zz, vecs[0], vecs[1], float(eps), float(momentum), vecs[2], vecs[3], mean, invstd, a, bool(act))
+    return a, mean, invstd
+
+
 def bn_silu_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None):
     """Backward of bn_silu_fwd_bf16 (batch statistics): z, da bf16 [..., C] -> (dz bf16 like z, dgamma fp32 [C], dbeta fp32 [C]); dgamma / dbeta
     go into the given tensors (e.g. views of an optimiser group's gradient buffer) when passed."""
@@ -579,6 +621,67 @@ def bn_silu_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None):
     dz = torch.empty_like(zz)
     _O.bn_silu_bwd(zz, d, *vecs, dg, db, dz)
     return dz, dg, db
+
+
+def bn_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None, act=True):
+    """Backward of bn_fwd_bf16 with the same `act` -> (dz bf16 like z, dgamma fp32 [C], dbeta fp32 [C]); dgamma / dbeta go into the given tensors
+    when passed."""
+    zz, d = _chk(z, torch.bfloat16, "z"), _chk(da, torch.bfloat16, "da")
+    if d.shape != zz.shape:
+        raise ValueError("bn_bwd_bf16: da must have the shape of z")
+    Cn = zz.shape[-1]
+    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
+    dg = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dgamma is None else _chk(dgamma, torch.float32, "dgamma")
+    db = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dbeta is None else _chk(dbeta, torch.float32, "dbeta")
+    if any(t.numel() != Cn for t in vecs + [dg, db]):
+        raise ValueError("bn_bwd_bf16: per-channel vectors must have C entries")
+    dz = torch.empty_like(zz)
+    _O.bn_bwd(zz, d, *vecs, dg, db, dz, bool(act))
+    return dz, dg, db
+
+
+def _dw_weights(w, Cn, fn):
+    ww = _chk(w, torch.float32, "w")
+    if tuple(ww.shape) != (Cn, 1, 3, 3):
+        raise ValueError(f"{fn}: w must be the depthwise 3x3 weights [C,1,3,3] = [{Cn},1,3,3], got {tuple(ww.shape)}")
+    return ww
+
+
+def dwconv3_fwd_bf16(x, w):
+    """Depthwise 3x3 convolution (stride 1, pad 1, groups = C, no bias, no activation): x bf16 [B,H,W,C] NHWC, w fp32 MASTER weights [C,1,3,3]
+    (rounded to bf16 as the kernel loads them: no pack step) -> z bf16 [B,H,W,C]; fp32 sums, taps in (ky, kx) order, one bf16 rounding."""
+    xx = _chk(x, torch.bfloat16, "x")
+    if xx.dim() != 4:
+        raise ValueError("dwconv3_fwd_bf16: x must be [B,H,W,C]")
+    ww = _dw_weights(w, xx.shape[-1], "dwconv3_fwd_bf16")
+    z = torch.empty_like(xx)
+    _O.dwconv3_fwd(xx, ww, z)
+    return z
+
+
+def dwconv3_bwd_bf16(x, dz, w, dw_out=None, need_dx=True):
+    """Fused backward of dwconv3_fwd_bf16, both gradients from one pass over x and dz (bf16 [B,H,W,C]) -> (dx bf16 [B,H,W,C] or None when
+    need_dx is False, dw fp32 [C,1,3,3]); dw goes into `dw_out` when given (e.g. a view of an optimiser group's gradient buffer).
+    Deterministic (no atomics)."""
+    xx, d = _chk(x, torch.bfloat16, "x"), _chk(dz, torch.bfloat16, "dz")
+    if xx.dim() != 4 or d.shape != xx.shape:
+        raise ValueError("dwconv3_bwd_bf16: x and dz must both be [B,H,W,C]")
+    Cn = xx.shape[-1]
+    ww = _dw_weights(w, Cn, "dwconv3_bwd_bf16")
+    dw = torch.empty((Cn, 1, 3, 3), dtype=torch.float32, device=xx.device) if dw_out is None else _chk(dw_out, torch.float32, "dw_out")
+    if tuple(dw.shape) != (Cn, 1, 3, 3):
+        raise ValueError("dwconv3_bwd_bf16: dw_out must be [C,1,3,3]")
+    dx = torch.empty_like(xx) if need_dx else None
+    _O.dwconv3_bwd(xx, d, ww, dx, dw)
+    return dx, dw
+
+
+def dwconv3_bwd_geometry(B, H, W, C):
+    """Host helper -> (rows per stripe, pixels per lane run, number of slabs, L): the split obb_dwconv3_bwd_bf16 uses at this shape; L is the
+    longest chain of fp32 additions one dw element passes through."""
+    out = (_ct.c_int32 * 4)()
+    _lib.check(_lib.lib().obb_dwconv3_bwd_geometry(int(B), int(H), int(W), int(C), out))
+    return tuple(int(v) for v in out)
 
 
 def sppf_pools_fwd_bf16(x):

@@ -14,7 +14,9 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
   * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
     training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded;
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
-    the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip)."""
+    the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
+  * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
+    one `DWConv 3x3 -> Conv 1x1` pair of the head's class branch built from it and ConvBN."""
 import math
 
 import torch
@@ -247,6 +249,77 @@ class ConvBN:
         """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32."""
         f = self.gamma / torch.sqrt(self.running_var + self.eps)
         return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+
+class DWConvBN:
+    """ONE depthwise Ultralytics block in training mode -- `DWConv(c, c, 3)` = Conv2d(c, c, 3, 1, 1, groups=c, bias=False) -> BatchNorm2d -> SiLU
+    (act=True: the head's class branch, model.23.cv3.i.{0,1}.0) or without the SiLU (act=False: `Conv(c, c, 3, g=c, act=False)`, C2PSA's
+    attn.pe) -- under ConvBN's contract: bf16 NHWC activations, fp32 master parameters in `groups` (w [C,1,3,3] in group 0, gamma in 1, beta in
+    2), `forward` / `backward` / `fold`.  The kernels read the master weights directly (rounded to bf16 as they are loaded: no pack step); the
+    backward takes dx and dW from one pass over x and dz, dW written straight into the group's gradient view."""
+
+    def __init__(self, groups, w, gamma=None, beta=None, act=True, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
+        if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
+            raise ValueError(f"DWConvBN: w must be the depthwise 3x3 weights [C,1,3,3], got {tuple(w.shape)}")
+        c = w.shape[0]
+        self.c1 = self.c2 = c
+        self.k, self.s, self.act, self.eps, self.momentum = 3, 1, bool(act), eps, momentum
+        dev = w.device
+        self.groups = groups
+        self._iw = groups.add(0, w)
+        self._ig = groups.add(1, gamma if gamma is not None else torch.ones(c, device=dev))
+        self._ib = groups.add(2, beta if beta is not None else torch.zeros(c, device=dev))
+        self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c, device=dev)).float().contiguous()
+        self.running_var = (running_var.clone() if running_var is not None else torch.ones(c, device=dev)).float().contiguous()
+        self.saved = None
+
+    w = property(lambda self: self.groups.param[self._iw])
+    gamma = property(lambda self: self.groups.param[self._ig])
+    beta = property(lambda self: self.groups.param[self._ib])
+    dw = property(lambda self: self.groups.grad[self._iw])
+    dgamma = property(lambda self: self.groups.grad[self._ig])
+    dbeta = property(lambda self: self.groups.grad[self._ib])
+
+    def forward(self, x):
+        """x bf16 [B,H,W,C] -> a bf16 [B,H,W,C]; keeps (x, z, mean, invstd) for the backward."""
+        z = ops.dwconv3_fwd_bf16(x, self.w)
+        a, mean, invstd = ops.bn_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum, act=self.act)
+        self.saved = (x, z, mean, invstd)
+        return a
+
+    def backward(self, da, need_dx=True):
+        """da bf16 like the forward's output -> dx bf16 like its input (None when need_dx is False); dW, dgamma, dbeta are written into the
+        groups' gradient buffers."""
+        x, z, mean, invstd = self.saved
+        dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=self.act)
+        dx, _ = ops.dwconv3_bwd_bf16(x, dz, self.w, dw_out=self.dw, need_dx=need_dx)
+        return dx
+
+    def fold(self):
+        """-> (w [C,1,3,3], b [C]): the eval-mode BN folded into the depthwise conv, fp32."""
+        f = self.gamma / torch.sqrt(self.running_var + self.eps)
+        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+
+class ClassBranchPair:
+    """One `Sequential(DWConv(c1, c1, 3), Conv(c1, c2, 1))` of the head's class branch (ultralytics Detect.cv3[i][0] and [1]; the branch is two
+    such pairs and the nc-channel logit Conv2d) in training mode: DWConvBN -> ConvBN(1x1), both with SiLU.  dw / pw: (w, gamma, beta[,
+    running_mean, running_var]) of the two blocks, registered in `groups` in that order.  `backward` chains the two blocks' backwards."""
+
+    def __init__(self, groups, dw, pw, eps=1e-3, momentum=0.03):
+        opt = lambda t, i: t[i] if len(t) > i else None
+        self.dw = DWConvBN(groups, dw[0], opt(dw, 1), opt(dw, 2), True, opt(dw, 3), opt(dw, 4), eps, momentum)
+        self.pw = ConvBN(groups, pw[0], opt(pw, 1), opt(pw, 2), 1, opt(pw, 3), opt(pw, 4), eps, momentum)
+        if self.pw.k != 1 or self.pw.c1 != self.dw.c2:
+            raise ValueError(f"ClassBranchPair: pw is a 1x1 conv reading dw's {self.dw.c2} channels, got k = {self.pw.k}, c1 = {self.pw.c1}")
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
+        return self.pw.forward(self.dw.forward(x))
+
+    def backward(self, da):
+        """da bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
+        return self.dw.backward(self.pw.backward(da))
 
 
 class SPPF:
