@@ -279,6 +279,29 @@ int obb_bn_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, co
                     float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, int32_t act, obb_stream_t s);
 int obb_bn_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
                     const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, int32_t act, obb_stream_t s);
+/* Softmax attention core of C2PSA in training mode (`model.train(...)`, Train_OBB.py:796-841 -> ultralytics Attention(dim, num_heads,
+ * attn_ratio = 0.5), model.10.m.*.attn), key_dim 32, head_dim 64, all tensors on the device.  Layout, the inference core's: qkv and dqkv bf16
+ * [B][N][nh * 128], per token [q: nh * 32 | k: nh * 32 | v: nh * 64] (the qkv conv's output channels in DEVICE order, heads grouped); out, dout
+ * and dv_add bf16 [B][N][nh * 64]; lse fp32 [B][nh][N].  scale = (float)(1 / sqrt(32.0)).  Limits: 1 <= N <= 192 (the keys of a head are
+ * resident in LDS; a longer sequence is OBB_ERR_INVALID, not a slower path), nh >= 1, B >= 1; a NULL buffer other than dv_add is
+ * OBB_ERR_INVALID; the bf16 buffers are 16-byte aligned.
+ * obb_attn_fwd_bf16: S = scale q k^T, P = softmax over the keys of S, out = P v; lse[q] = max_k S[q][k] + log(sum_k exp(S[q][k] - max)) is the
+ *   only thing kept for the backward.
+ * obb_attn_bwd_bf16: P = exp(S - lse) recomputed from qkv and lse; dV = P^T dO (+ dv_add), dP = dO V^T, D[q] = sum_d dO[q][d] out[q][d],
+ *   dS = P o (dP - D), dQ = scale dS K, dK = scale dS^T Q; EVERY element of dqkv is written.  dv_add may be NULL; given, it is added to dV in
+ *   fp32 before dV's single bf16 rounding (the gradient of v's second consumer, attn.pe: the accumulate form of obb_upcat_bwd_bf16).
+ * Rounding points: bf16 x bf16 products are exact in fp32; sums are fp32 (matrix-core accumulators; D: 16 products in index order per quarter,
+ *   then (p0 + p1) + (p2 + p3)); exp / log are the hardware's base-2 instructions on arguments scaled by fp32 log2(e) / ln(2); P and dS enter
+ *   their matrix products SPLIT into hi + lo bf16 parts (2^-16 relative is lost, they are not rounded to bf16); one bf16 rounding at each
+ *   bf16 store, scale applied to the fp32 sum of dQ / dK just before it.
+ * Determinism: every output row has one owner wave (a dQ row: the wave of its 16-query block, walking all keys; a dK / dV row: the wave of
+ *   its 16-key block, walking all queries); no atomics, no cross-wave sum, no workspace: results are bit-reproducible.
+ * obb_add_bf16: out[i] = bf16(fp32(a[i]) + fp32(b[i])), i < n, n % 8 == 0 (>= 8), 16-byte aligned; out may alias a.  The residual adds of a
+ *   PSA block and the gradient sums at their fan-outs. */
+int obb_attn_fwd_bf16(obb_ctx *ctx, const uint16_t *qkv, int32_t B, int32_t N, int32_t nh, uint16_t *out, float *lse, obb_stream_t s);
+int obb_attn_bwd_bf16(obb_ctx *ctx, const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout, const uint16_t *dv_add,
+                      int32_t B, int32_t N, int32_t nh, uint16_t *dqkv, obb_stream_t s);
+int obb_add_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int64_t n, uint16_t *out, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S1: model(...) -> results[0].obb  (Detect_OBB.py:26,81-83,228-231) */
 /* Weight blob ("OBBW" format, produced by the Python side from BN-folded conv weights) for a

@@ -63,6 +63,9 @@ SIGNATURES = {
     "obb_dwconv3_bwd_geometry": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip],
     "obb_bn_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, C.c_int32, _V],
     "obb_bn_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, C.c_int32, _V],
+    "obb_attn_fwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],
+    "obb_attn_bwd_bf16": [_V, _V, _V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_add_bf16": [_V, _V, _V, C.c_int64, _V, _V],
     "obb_gather_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V, _V],
     "obb_letterbox": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V,
                       C.c_int32, C.c_int32, _V],

@@ -16,6 +16,8 @@
 //   share           2 chunks per workgroup while H * W <= 512, 1 above (H, W <= 32 each): the rule depends on the map alone.
 //   upcat           out = cat(nearest_upsample_up(a), b) along C, up in {1, 2}; backward da[p] = fp32 sum of the up^2 copies (dy then dx),
 //                   db = the b slice; accum: the existing bf16 value is the first term of the fp32 sum.  One rounding per result.
+//   add             out = bf16(fp32(a) + fp32(b)) over n elements, n % 8 == 0; out may alias a (a chunk is read before it is written, by the
+//                   same lane): the residual adds of a PSA block and the gradient sum at their fan-outs.
 #include <algorithm>
 
 #include "ctx.h"
@@ -230,6 +232,18 @@ __global__ __launch_bounds__(256) void k_upcat_bwd(const unsigned short *__restr
     }
 }
 
+// one 16-byte chunk per thread and step
+__global__ __launch_bounds__(256) void k_add_bf16(const unsigned short *a, const unsigned short *__restrict__ b, int64_t nchunk, unsigned short *out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * 256) {
+        float x[8], y[8];
+        rg_unpack8(reinterpret_cast<const uint4 *>(a)[i], x);
+        rg_unpack8(reinterpret_cast<const uint4 *>(b)[i], y);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] += y[j];
+        reinterpret_cast<uint4 *>(out)[i] = rg_pack8(x);
+    }
+}
+
 namespace {
 unsigned route_grid(int64_t nchunk) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nchunk, 256), 4096)); }
 
@@ -298,6 +312,16 @@ int obb_upcat_bwd_bf16(obb_ctx *ctx, const uint16_t *dout, int32_t B, int32_t H,
     if (nA + nB == 0) return OBB_OK;
     hipLaunchKernelGGL(k_upcat_bwd, dim3(route_grid(nA + nB)), dim3(256), 0, (hipStream_t)s, dout, nA, nB, (int)H, (int)W, (int)(Ca / 8), (int)(Cb / 8), (int)up, da,
                        db, (int)(accum_a != 0), (int)(accum_b != 0));
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
+}
+
+int obb_add_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int64_t n, uint16_t *out, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && n >= 8 && n % 8 == 0, "obb_add_bf16: n = %lld must be a positive multiple of 8", (long long)n);
+    OBB_REQUIRE(ctx, a && b && out, "obb_add_bf16: NULL buffer");
+    OBB_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0,
+                "obb_add_bf16: a, b and out must be 16-byte aligned");
+    hipLaunchKernelGGL(k_add_bf16, dim3(route_grid(n / 8)), dim3(256), 0, (hipStream_t)s, a, b, n / 8, out);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }

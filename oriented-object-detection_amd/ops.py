@@ -309,6 +309,23 @@ def _bn_bwd(z: T, da: T, gamma: T, beta: T, mean: T, invstd: T, dgamma: T, dbeta
           int(bool(act)), _stream())
 
 
+@_op("attn_fwd", ("out", "lse"))
+def _attn_fwd(qkv: T, nh: int, out: T, lse: T) -> None:
+    B, N = qkv.shape[0], qkv.numel() // (qkv.shape[0] * qkv.shape[-1])
+    _call("obb_attn_fwd_bf16", ctx(qkv.device), _p(qkv), B, N, int(nh), _p(out), _p(lse), _stream())
+
+
+@_op("attn_bwd", ("dqkv",))
+def _attn_bwd(qkv: T, out: T, lse: T, dout: T, dv_add: Optional[T], nh: int, dqkv: T) -> None:
+    B, N = qkv.shape[0], qkv.numel() // (qkv.shape[0] * qkv.shape[-1])
+    _call("obb_attn_bwd_bf16", ctx(qkv.device), _p(qkv), _p(out), _p(lse), _p(dout), _p(dv_add), B, N, int(nh), _p(dqkv), _stream())
+
+
+@_op("add_bf16", ("out",))
+def _add_bf16(a: T, b: T, out: T) -> None:
+    _call("obb_add_bf16", ctx(a.device), _p(a), _p(b), a.numel(), _p(out), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -743,6 +760,54 @@ def upcat_bwd_bf16(dout, Ca, up=1, da=None, db=None, need_da=True, need_db=True)
         db = None
     _O.upcat_bwd(d, H, W, int(Ca), int(up), da, db, acc_a, acc_b)
     return da, db
+
+
+def _attn_tokens(t, nh, per_head, fn, name):
+    """t bf16 [B, ..., nh * per_head] with at least one token axis -> (checked tensor, B, N)"""
+    tt = _chk(t, torch.bfloat16, name)
+    if int(nh) < 1 or tt.dim() < 3 or tt.shape[-1] != int(nh) * per_head:
+        raise ValueError(f"{fn}: {name} must be [B, ..., nh * {per_head}] = [B, ..., {int(nh) * per_head}] for nh = {nh}, got {tuple(tt.shape)}")
+    return tt, tt.shape[0], tt.numel() // (tt.shape[0] * tt.shape[-1])
+
+
+def attn_fwd_bf16(qkv, nh):
+    """Softmax attention core with key_dim 32, head_dim 64: qkv bf16 [B, N, nh * 128] (or [B, H, W, nh * 128], N = H W), per token
+    [q: nh * 32 | k: nh * 32 | v: nh * 64] -> (out bf16 [B, ..., nh * 64], lse fp32 [B, nh, N]); 1 <= N <= 192.  lse is all the backward needs."""
+    qq, B, N = _attn_tokens(qkv, nh, 128, "attn_fwd_bf16", "qkv")
+    out = torch.empty((*qq.shape[:-1], int(nh) * 64), dtype=torch.bfloat16, device=qq.device)
+    lse = torch.empty((B, int(nh), N), dtype=torch.float32, device=qq.device)
+    _O.attn_fwd(qq, int(nh), out, lse)
+    return out, lse
+
+
+def attn_bwd_bf16(qkv, out, lse, dout, nh, dv_add=None):
+    """Backward of attn_fwd_bf16 -> dqkv bf16 like qkv, every element written.  dv_add (bf16 like out) is added to dV in fp32 before its one
+    rounding: the gradient of v's other consumer.  Deterministic (no atomics)."""
+    qq, B, N = _attn_tokens(qkv, nh, 128, "attn_bwd_bf16", "qkv")
+    oo, _, _ = _attn_tokens(out, nh, 64, "attn_bwd_bf16", "out")
+    dd, _, _ = _attn_tokens(dout, nh, 64, "attn_bwd_bf16", "dout")
+    ll = _chk(lse, torch.float32, "lse")
+    if oo.shape[:-1] != qq.shape[:-1] or dd.shape != oo.shape or tuple(ll.shape) != (B, int(nh), N):
+        raise ValueError(f"attn_bwd_bf16: out {tuple(oo.shape)}, dout {tuple(dd.shape)}, lse {tuple(ll.shape)} do not belong to qkv {tuple(qq.shape)}")
+    if dv_add is not None:
+        dv_add, _, _ = _attn_tokens(dv_add, nh, 64, "attn_bwd_bf16", "dv_add")
+        if dv_add.shape != oo.shape:
+            raise ValueError("attn_bwd_bf16: dv_add must have the shape of out")
+    dqkv = torch.empty_like(qq)
+    _O.attn_bwd(qq, oo, ll, dd, dv_add, int(nh), dqkv)
+    return dqkv
+
+
+def add_bf16(a, b, out=None):
+    """bf16(fp32(a) + fp32(b)) element-wise, numel % 8 == 0; `out` may be `a` (in place)."""
+    aa, bb = _chk(a, torch.bfloat16, "a"), _chk(b, torch.bfloat16, "b")
+    if aa.shape != bb.shape:
+        raise ValueError(f"add_bf16: a {tuple(aa.shape)} and b {tuple(bb.shape)} differ in shape")
+    out = torch.empty_like(aa) if out is None else _chk(out, torch.bfloat16, "out")
+    if out.shape != aa.shape:
+        raise ValueError("add_bf16: out must have the shape of a")
+    _O.add_bf16(aa, bb, out)
+    return out
 
 
 def silu_bf16(z):

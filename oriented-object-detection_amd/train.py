@@ -16,7 +16,10 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
     the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
   * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
-    one `DWConv 3x3 -> Conv 1x1` pair of the head's class branch built from it and ConvBN."""
+    one `DWConv 3x3 -> Conv 1x1` pair of the head's class branch built from it and ConvBN;
+  * `Attention` / `PSABlock`: C2PSA's attention (csrc/attngrad.hip: the softmax core with its backward) and one PSA block of model 10 around it --
+    qkv / proj / ffn as ConvBN (with `act=False` where the reference has none), pe as DWConvBN, the residual adds and the gradient sums at their
+    fan-outs as ops.add_bf16."""
 import math
 
 import torch
@@ -200,16 +203,16 @@ class ParamGroups:
 
 class ConvBN:
     """ONE Ultralytics `Conv(c1, c2, k, s)` block in training mode -- Conv2d(bias=False) -> BatchNorm2d (batch statistics, running statistics
-    updated) -> SiLU -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
+    updated) -> SiLU (act=False: no SiLU, Ultralytics' `Conv(..., act=False)`) -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
     k = 1 or 3; s = 2 with k = 3 only (the downsampling convs).  Ultralytics' initialize_weights sets eps = 1e-3, momentum = 0.03 (recalled:
     the package is not installed here, so these defaults are unpinned like optimizer_config; both are arguments).  Every arithmetic step on
     the device is a libobbhip kernel; running statistics are buffers of the block, not parameters."""
 
-    def __init__(self, groups, w, gamma=None, beta=None, s=1, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
+    def __init__(self, groups, w, gamma=None, beta=None, s=1, running_mean=None, running_var=None, eps=1e-3, momentum=0.03, act=True):
         c2, c1, k, k2 = w.shape
         if k != k2 or k not in (1, 3) or s not in (1, 2) or (s == 2 and k != 3):
             raise ValueError(f"ConvBN: k = {k}, s = {s}: k 1 or 3 at stride 1, k 3 at stride 2")
-        self.c1, self.c2, self.k, self.s, self.eps, self.momentum = c1, c2, k, s, eps, momentum
+        self.c1, self.c2, self.k, self.s, self.eps, self.momentum, self.act = c1, c2, k, s, eps, momentum, bool(act)
         dev = w.device
         self.groups = groups
         self._iw = groups.add(0, w)
@@ -230,7 +233,10 @@ class ConvBN:
         """x bf16 [B,H,W,c1] -> a bf16 [B,Ho,Wo,c2]; keeps (x, z, mean, invstd) for the backward."""
         H, W = x.shape[1], x.shape[2]
         z = ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, H, W, stride=self.s), None, self.c2, self.k, stride=self.s)
-        a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
+        if self.act:
+            a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
+        else:  # Conv(act=False): BatchNorm alone
+            a, mean, invstd = ops.bn_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum, act=False)
         self.saved = (x, z, mean, invstd)
         return a
 
@@ -238,7 +244,10 @@ class ConvBN:
         """da bf16 like the forward's output -> dx bf16 like its input; dW, dgamma, dbeta are written into the groups' gradient buffers."""
         x, z, mean, invstd = self.saved
         H, W = x.shape[1], x.shape[2]
-        dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
+        if self.act:
+            dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
+        else:
+            dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=False)
         ops.conv_wgrad_bf16(x, dz, self.k, stride=self.s, out=self.dw)
         bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
         if self.s == 2:
@@ -320,6 +329,93 @@ class ClassBranchPair:
     def backward(self, da):
         """da bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
         return self.dw.backward(self.pw.backward(da))
+
+
+def qkv_device_order(nh, kd=32, hd=64):
+    """-> LongTensor perm: device channel i of the qkv conv is checkpoint channel perm[i].  The checkpoint groups the output channels per head,
+    [q | k | v] of head 0, then head 1, ...; the attention kernels read [q of all heads | k of all heads | v of all heads], so that v is one
+    contiguous slice (the permutation the forward engine applies to the same layer at load)."""
+    perm = []
+    for off, n in ((0, kd), (kd, kd), (2 * kd, hd)):
+        for h in range(nh):
+            perm.extend(range(h * (2 * kd + hd) + off, h * (2 * kd + hd) + off + n))
+    return torch.tensor(perm, dtype=torch.long)
+
+
+class Attention:
+    """Ultralytics `Attention(dim, num_heads, attn_ratio=0.5)` (model.10.m.i.attn; key_dim 32, head_dim 64, nh = dim / 64) in training mode:
+        qkv = Conv 1x1 (dim -> 2 dim, no act);  out = softmax(scale q^T k) applied to v per head;  y = proj(out + pe(v)),
+    pe = depthwise Conv 3x3 (no act), proj = Conv 1x1 (no act).  qkv / proj / pe: (w, gamma, beta[, running_mean, running_var]) of the three
+    blocks in CHECKPOINT channel order, registered in `groups` in that order.  The qkv block is HELD in device order (`qkv_device_order`: its
+    rows of w, gamma, beta and the running statistics are permuted once, here), so its parameters, gradients and running statistics in `groups`
+    are in device order; `fold()` hands every block back in checkpoint order.  The v slice of qkv that pe reads is a torch copy (index
+    bookkeeping).  bf16 [B,H,W,dim] in and out, H W <= 192."""
+
+    def __init__(self, groups, qkv, proj, pe, nh, eps=1e-3, momentum=0.03):
+        opt = lambda t, i: t[i] if len(t) > i else None
+        self.nh = int(nh)
+        dim = self.nh * 64
+        if tuple(qkv[0].shape) != (2 * dim, dim, 1, 1) or tuple(proj[0].shape) != (dim, dim, 1, 1) or tuple(pe[0].shape) != (dim, 1, 3, 3):
+            raise ValueError(f"Attention: nh = {nh} heads of 64 channels: qkv [{2 * dim},{dim},1,1], proj [{dim},{dim},1,1], pe [{dim},1,3,3], got "
+                             f"{tuple(qkv[0].shape)}, {tuple(proj[0].shape)}, {tuple(pe[0].shape)}")
+        self.perm = qkv_device_order(self.nh).to(qkv[0].device)
+        self.inv = torch.argsort(self.perm)
+        pq = [None if t is None else t[self.perm].contiguous() for t in (opt(qkv, i) for i in range(5))]
+        self.qkv = ConvBN(groups, pq[0], pq[1], pq[2], 1, pq[3], pq[4], eps, momentum, act=False)
+        self.proj = ConvBN(groups, proj[0], opt(proj, 1), opt(proj, 2), 1, opt(proj, 3), opt(proj, 4), eps, momentum, act=False)
+        self.pe = DWConvBN(groups, pe[0], opt(pe, 1), opt(pe, 2), False, opt(pe, 3), opt(pe, 4), eps, momentum)
+        self.saved = None
+
+    def forward(self, x):
+        """x bf16 [B,H,W,dim] -> bf16 [B,H,W,dim]; keeps (qkv, out, lse) for the backward."""
+        qkv = self.qkv.forward(x)
+        out, lse = ops.attn_fwd_bf16(qkv, self.nh)
+        v = qkv[..., self.nh * 64:].contiguous()
+        self.saved = (qkv, out, lse)
+        return self.proj.forward(ops.add_bf16(out, self.pe.forward(v)))
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; the nine parameter gradients go into the groups' gradient buffers.  The
+        gradient of `out + pe(v)` goes to both the core and pe; pe's dx arrives in dV inside the core's backward (dv_add)."""
+        qkv, out, lse = self.saved
+        ds = self.proj.backward(dy)
+        dqkv = ops.attn_bwd_bf16(qkv, out, lse, ds, self.nh, dv_add=self.pe.backward(ds))
+        return self.qkv.backward(dqkv)
+
+    def fold(self):
+        """-> {"qkv": (w, b), "proj": (w, b), "pe": (w, b)}: eval-mode BN folded into each conv, fp32, checkpoint channel order."""
+        wq, bq = self.qkv.fold()
+        return {"qkv": (wq[self.inv], bq[self.inv]), "proj": self.proj.fold(), "pe": self.pe.fold()}
+
+
+class PSABlock:
+    """Ultralytics `PSABlock(c, attn_ratio=0.5, num_heads=c // 64)` (model.10.m.i) in training mode:
+        x = x + attn(x);  x = x + ffn1(ffn0(x)),   ffn0 = Conv 1x1 (c -> 2 c, SiLU), ffn1 = Conv 1x1 (2 c -> c, no act).
+    qkv / proj / pe as for `Attention`, ffn0 / ffn1: (w, gamma, beta[, running_mean, running_var]); registered in `groups` in the order qkv,
+    proj, pe, ffn0, ffn1.  The two residual adds and the two gradient sums at their fan-outs are ops.add_bf16 (fp32 add, one rounding)."""
+
+    def __init__(self, groups, qkv, proj, pe, ffn0, ffn1, nh, eps=1e-3, momentum=0.03):
+        opt = lambda t, i: t[i] if len(t) > i else None
+        self.attn = Attention(groups, qkv, proj, pe, nh, eps, momentum)
+        self.ffn0 = ConvBN(groups, ffn0[0], opt(ffn0, 1), opt(ffn0, 2), 1, opt(ffn0, 3), opt(ffn0, 4), eps, momentum)
+        self.ffn1 = ConvBN(groups, ffn1[0], opt(ffn1, 1), opt(ffn1, 2), 1, opt(ffn1, 3), opt(ffn1, 4), eps, momentum, act=False)
+        c = self.attn.nh * 64
+        if (self.ffn0.k, self.ffn0.c1, self.ffn1.k, self.ffn1.c1, self.ffn1.c2) != (1, c, 1, self.ffn0.c2, c):
+            raise ValueError(f"PSABlock: ffn0 and ffn1 are 1x1 convs {c} -> m -> {c}, got {tuple(ffn0[0].shape)}, {tuple(ffn1[0].shape)}")
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c] -> bf16 [B,H,W,c]."""
+        x1 = ops.add_bf16(x, self.attn.forward(x))
+        return ops.add_bf16(x1, self.ffn1.forward(self.ffn0.forward(x1)))
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; the fifteen parameter gradients go into the groups' gradient buffers."""
+        d1 = ops.add_bf16(dy, self.ffn0.backward(self.ffn1.backward(dy)))
+        return ops.add_bf16(d1, self.attn.backward(d1))
+
+    def fold(self):
+        """-> Attention.fold() plus {"ffn0": (w, b), "ffn1": (w, b)}."""
+        return {**self.attn.fold(), "ffn0": self.ffn0.fold(), "ffn1": self.ffn1.fold()}
 
 
 class SPPF:
