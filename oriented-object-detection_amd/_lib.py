@@ -52,6 +52,7 @@ SIGNATURES = {
     "obb_conv_fwd_s2_bf16": [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_conv_dgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_conv_wgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_conv_wgrad_c8_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_bn_silu_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, _V],
     "obb_bn_silu_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V],
     "obb_sppf_pools_fwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],

@@ -19,11 +19,18 @@
 //            zero-inserted dY on the dgrad-form weights.  dY_up only needs the H x W extent (positions H and -1 are zeros / padding either
 //            way), so the conv writes dX directly, no crop.  It spends 4x the useful MACs (three taps of four see an inserted zero).
 //   wgrad    k_conv_wgrad<3, 2>: R output rows stage 2R + 1 input rows of width 2 Wp + 1 (one 208-pixel row of model.3 at 416 px: R = 1).
+//
+// Channel counts that are multiples of 8 but not of 64 (obb_conv_wgrad_c8_bf16: model.1, the Bottlenecks of the C3k2 blocks down to 16 -> 8, the
+// 1x1s behind a 48- / 96-channel concat, the head's angle branch): k_conv_wgrad_c8, the same arithmetic on blocks of ceil(live / 16) fragments
+// per side -- the LDS tile at the live width, only the block's cout fragments issued, and the waves that have no cin fragment of their own
+// taking every nshare-th k step of another wave's fragment (added in fixed wave order through LDS before the slab write).  Its slabs hold
+// dW's elements only ([tap][cout][cin] per walker, summed in walker order by k_wgrad_reduce_c8).  The split is described at the kernel.
 #include <algorithm>
 #include <vector>
 
 #include "conv.h"
 #include "ctx.h"
+#include "launchcfg.h"
 
 namespace obb {
 
@@ -105,6 +112,120 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ 
     const int cib = blk % ncib, cob = blk / ncib;
     const int co = cob * 64 + co_l, ci = cib * 64 + ci_l;
     if (co < cout && ci < cin) dw[((size_t)co * cin + ci) * taps + t] = s;
+}
+
+// ---- wgrad at any channel counts that are multiples of 8 (k_conv_wgrad_c8): the same tiles, the same walk and the same arithmetic as
+// k_conv_wgrad, for blocks of dW that are narrower than 64 x 64.  Channel blocks are ceil(c / 64) per side; the last block of a side holds
+// c % 64 live channels (8 .. 56).  The launcher issues one launch per CLASS of blocks -- (full | partial cout block) x (full | partial cin
+// block), at most four -- so that within a launch every workgroup has the same shape:
+//   NCF   (template) cout fragments of the block = ceil(live cout / 16): acc[NCF][TAPS]; a 16 -> 8 layer issues 1 x TAPS MFMAs per k step
+//   ncif  cin fragments of the block = ceil(live cin / 16)
+// LDS tile at the LIVE width: X pixels are ncif * 16 channels apart, dY pixels NCF * 16 (not 64), staged in 16-byte chunks; a chunk whose
+// first channel is >= the live count (the upper half of a fragment with 8 live channels) is zero-filled and never read from memory.
+// Wave split: a wave owns ONE cin fragment, as in k_conv_wgrad.  With ncif < 4 the other waves take a share of the reduction of the same
+// fragment: nshare = 4 / ncif (4, 2, 1, 1) waves per fragment, wave w -> fragment w % ncif, share w / ncif; the k steps of a tile (4 pixels of
+// a row each) are numbered row-major and share s takes steps s, s + nshare, ...  (ncif = 3 leaves wave 3 without work: 3 does not divide 4.)
+// After the walk the shares' accumulators are added into share 0's in share order 1, 2, 3, tap by tap through LDS (the tile is dead by then),
+// and share 0 writes the workgroup's slab.  Slab of a walker = fp32 [tap][cout][cin], exactly dW's elements: nothing outside is written.
+template <int KS, int S, int NCF>
+__global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int Ho,
+                                                      int Wo, int cin, int cout, int R, int cob0, int cib0, int ncif, float *__restrict__ slabs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short swg[];
+    constexpr int TAPS = KS * KS, PAD = KS / 2, COW = NCF * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, r16 = lane & 15;
+    const int cob = cob0 + blockIdx.y, cib = cib0 + blockIdx.z;
+    const int co_live = min(64, cout - cob * 64), ci_live = min(64, cin - cib * 64);  // multiples of 8; ceil(co_live / 16) == NCF, ceil(ci_live / 16) == ncif
+    const int CIW = ncif * 16, xch = CIW >> 3, ych = COW >> 3;                       // channels per staged pixel; 16-byte chunks per pixel
+    const int nshare = 4 / ncif, frag = wave % ncif, share = wave / ncif;
+    const bool active = share < nshare;
+    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * S + KS, Rx = (R - 1) * S + KS;
+    unsigned short *sx = swg, *sdy = swg + (size_t)Rx * Wx * CIW;
+    const int tiles_y = (Ho + R - 1) / R, ntiles = B * tiles_y;
+    const int spr = Wp >> 2, nsteps = R * spr;  // k steps per row / per tile
+    f32x4g acc[NCF][TAPS];
+#pragma unroll
+    for (int c = 0; c < NCF; ++c)
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) acc[c][t] = f32x4g{0.f, 0.f, 0.f, 0.f};
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int b = tile / tiles_y, y0 = (tile % tiles_y) * R;
+        __syncthreads();
+        for (int i = tid; i < Rx * Wx * xch; i += 256) {
+            const int c8 = i % xch, px = (i / xch) % Wx, ry = (i / xch) / Wx;
+            const int yy = y0 * S + ry - PAD, xx = px - PAD;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (c8 * 8 < ci_live && yy >= 0 && yy < H && xx >= 0 && xx < W)
+                v = *reinterpret_cast<const uint4 *>(x + (((int64_t)b * H + yy) * W + xx) * cin + cib * 64 + c8 * 8);
+            *reinterpret_cast<uint4 *>(sx + ((size_t)ry * Wx + px) * CIW + c8 * 8) = v;
+        }
+        for (int i = tid; i < R * Wp * ych; i += 256) {
+            const int c8 = i % ych, px = (i / ych) % Wp, ry = (i / ych) / Wp;
+            const int yy = y0 + ry;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (c8 * 8 < co_live && yy < Ho && px < Wo) v = *reinterpret_cast<const uint4 *>(dy + (((int64_t)b * Ho + yy) * Wo + px) * cout + cob * 64 + c8 * 8);
+            *reinterpret_cast<uint4 *>(sdy + ((size_t)ry * Wp + px) * COW + c8 * 8) = v;
+        }
+        __syncthreads();
+        if (active)
+            for (int q = share; q < nsteps; q += nshare) {  // this wave's k steps of the tile
+                const int ry = q / spr, xg = (q % spr) * 4 + g;
+                float a[NCF];
+#pragma unroll
+                for (int c = 0; c < NCF; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
+#pragma unroll
+                for (int t = 0; t < TAPS; ++t) {
+                    const int ky = t / KS, kx = t % KS;
+                    const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
+#pragma unroll
+                    for (int c = 0; c < NCF; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
+                }
+            }
+    }
+    if (nshare > 1) {  // (workgroup-uniform) shares 1 .. nshare - 1 -> share 0, in share order; red[share - 1][frag][c][q][lane]
+        float *red = reinterpret_cast<float *>(swg);
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) {
+            __syncthreads();  // (t = 0: every wave is done with the tile; t > 0: share 0 has read tap t - 1)
+            if (active && share > 0)
+#pragma unroll
+                for (int c = 0; c < NCF; ++c)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) red[((((share - 1) * ncif + frag) * NCF + c) * 4 + q) * 64 + lane] = acc[c][t][q];
+            __syncthreads();
+            if (share == 0)
+                for (int s = 1; s < nshare; ++s)
+#pragma unroll
+                    for (int c = 0; c < NCF; ++c)
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) acc[c][t][q] += red[((((s - 1) * ncif + frag) * NCF + c) * 4 + q) * 64 + lane];
+        }
+    }
+    if (!active || share != 0) return;
+    // D layout: lane holds ci = frag * 16 + r16 (column), couts c * 16 + 4 g .. + 3 (rows) of each tile; only dW's own elements are stored
+    float *slab = slabs + (size_t)blockIdx.x * TAPS * cout * cin;
+    const int ci_l = frag * 16 + r16;
+    if (ci_l >= ci_live) return;
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+        for (int c = 0; c < NCF; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int co_l = c * 16 + 4 * g + q;
+                if (co_l < co_live) slab[((size_t)t * cout + cob * 64 + co_l) * cin + cib * 64 + ci_l] = acc[c][t][q];
+            }
+}
+
+// dW[co][ci][tap] = sum over the walkers' [tap][cout][cin] slabs, in walker order
+__global__ __launch_bounds__(256) void k_wgrad_reduce_c8(const float *__restrict__ slabs, int nwalk, int taps, int cin, int cout, float *__restrict__ dw) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t per = (int64_t)taps * cout * cin;
+    if (i >= per) return;
+    float s = 0.f;
+    for (int w = 0; w < nwalk; ++w) s += slabs[(size_t)w * per + i];
+    const int ci = (int)(i % cin), co = (int)((i / cin) % cout), t = (int)(i / ((int64_t)cin * cout));
+    dw[((size_t)co * cin + ci) * taps + t] = s;
 }
 
 // ---- assembled-chain pieces (round 4): device-side weight packing (no per-call host repack / synchronisation), the training forward that keeps
@@ -231,6 +352,71 @@ int wgrad_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t
     else if (ks == 3) hipLaunchKernelGGL((k_conv_wgrad<3>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
     else hipLaunchKernelGGL((k_conv_wgrad<1>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
     hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, ncob, ncib, taps, cin, cout, dw);
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
+}
+
+// ---- k_conv_wgrad_c8's launch plan
+using WgradC8Fn = void (*)(const unsigned short *, const unsigned short *, int, int, int, int, int, int, int, int, int, int, int, float *);
+
+template <int KS, int S>
+WgradC8Fn wgrad_c8_kernel(int ncf) {
+    switch (ncf) {
+        case 1: return k_conv_wgrad_c8<KS, S, 1>;
+        case 2: return k_conv_wgrad_c8<KS, S, 2>;
+        case 3: return k_conv_wgrad_c8<KS, S, 3>;
+        default: return k_conv_wgrad_c8<KS, S, 4>;
+    }
+}
+
+constexpr size_t kWgradLdsDefault = 64 * 1024, kWgradLdsMax = 160 * 1024;  // without / with allow_dyn_lds (the CU's whole LDS)
+
+// LDS of one workgroup whose block has ncif cin and ncof cout fragments: the tile at the live width, or the cross-wave reduction's 4 ncof
+// floats per lane of every wave with a share > 0, whichever is larger
+size_t wgrad_c8_lds(int R, int ks, int stride, int Wp, int Wx, int ncif, int ncof) {
+    const size_t tile = ((size_t)((R - 1) * stride + ks) * Wx * ncif + (size_t)R * Wp * ncof) * 32;
+    const int nshare = 4 / ncif;
+    return std::max(tile, (size_t)(nshare - 1) * ncif * ncof * 1024);
+}
+
+// Blocks of 64 channels per side, the last one partial; one launch per class of blocks (see k_conv_wgrad_c8).  R rows per tile: as many as the
+// default 64 KiB hold at the widest class; a single row beyond that raises the kernel's cap (allow_dyn_lds) up to the CU's 160 KiB; a row
+// that does not fit then is refused.  Walkers: at most 512 / (blocks of dW) per block, as in wgrad_launch; slabs in WS_TRAIN_C (shared with
+// wgrad_launch: both fill the slot and consume it on the same stream before returning to the caller's next op).
+int wgrad_c8_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *dy, int B, int H, int W, int cin, int cout, int ks, int stride, float *dw,
+                    hipStream_t st) {
+    const int taps = ks * ks, Ho = out_dim(H, stride), Wo = out_dim(W, stride);
+    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * stride + ks;
+    const int ncob = (cout + 63) / 64, ncib = (cin + 63) / 64;
+    const int fco = cout / 64, fci = cin / 64;                             // full blocks per side
+    const int pcof = (cout % 64 + 15) / 16, pcif = (cin % 64 + 15) / 16;  // fragments of the partial block (0: none)
+    const int wcof = fco ? 4 : pcof, wcif = fci ? 4 : pcif;               // the widest class
+    int R = 1;
+    while (R < Ho && wgrad_c8_lds(R + 1, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsDefault) ++R;
+    OBB_REQUIRE(ctx, wgrad_c8_lds(R, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsMax,
+                "%s: a row of %d pixels at %d x %d channels per block does not fit the LDS tile (%zu bytes of %zu)", fn, W, wcif * 16, wcof * 16,
+                wgrad_c8_lds(R, ks, stride, Wp, Wx, wcif, wcof), kWgradLdsMax);
+    const int ntiles = B * ((Ho + R - 1) / R);
+    const int nwalk = std::max(1, std::min(ntiles, 512 / (ncob * ncib)));
+    const size_t per = (size_t)taps * cout * cin;
+    float *slabs = (float *)ctx->workspace(WS_TRAIN_C, (size_t)nwalk * per * 4);
+    if (!slabs) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
+    // classes: {first block, block count, fragments} per side
+    const int co_cls[2][3] = {{0, fco, 4}, {fco, pcof ? 1 : 0, pcof}}, ci_cls[2][3] = {{0, fci, 4}, {fci, pcif ? 1 : 0, pcif}};
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) {
+            const int *co = co_cls[a], *ci = ci_cls[b];
+            if (!co[1] || !ci[1]) continue;
+            const WgradC8Fn k = stride == 2 ? wgrad_c8_kernel<3, 2>(co[2]) : ks == 3 ? wgrad_c8_kernel<3, 1>(co[2]) : wgrad_c8_kernel<1, 1>(co[2]);
+            const size_t lds = wgrad_c8_lds(R, ks, stride, Wp, Wx, ci[2], co[2]);
+            if (lds > kWgradLdsDefault) {
+                hipError_t e = allow_dyn_lds(reinterpret_cast<const void *>(k), kWgradLdsMax);
+                if (e != hipSuccess) return set_error(ctx, OBB_ERR_HIP, "%s: raising the LDS cap failed: %s", fn, hipGetErrorString(e));
+            }
+            hipLaunchKernelGGL(k, dim3((unsigned)nwalk, (unsigned)co[1], (unsigned)ci[1]), dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, co[0], ci[0], ci[2],
+                               slabs);
+        }
+    hipLaunchKernelGGL(k_wgrad_reduce_c8, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, taps, cin, cout, dw);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }
@@ -404,6 +590,17 @@ int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, 
                 "models 0 and 1 of the backbone (3 -> 32, 32 -> 64) have no stride-2 wgrad", (int)cin, (int)cout);
     OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_s2_bf16: NULL buffer");
     return wgrad_launch(ctx, "obb_conv_wgrad_s2_bf16", x, dy, B, H, W, cin, cout, 3, 2, dw, (hipStream_t)s);
+}
+
+int obb_conv_wgrad_c8_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t ks, int32_t stride,
+                           float *dw, obb_stream_t s) {
+    OBB_REQUIRE(ctx, ctx && B >= 1 && H > 0 && W > 0, "obb_conv_wgrad_c8_bf16: bad arguments (B = %d, H = %d, W = %d)", (int)B, (int)H, (int)W);
+    OBB_REQUIRE(ctx, (stride == 1 && (ks == 1 || ks == 3)) || (stride == 2 && ks == 3),
+                "obb_conv_wgrad_c8_bf16: k = %d at stride %d: 1x1 and 3x3 at stride 1 and 3x3 at stride 2 are built", (int)ks, (int)stride);
+    OBB_REQUIRE(ctx, cin >= 8 && cout >= 8 && cin % 8 == 0 && cout % 8 == 0,
+                "obb_conv_wgrad_c8_bf16: cin = %d, cout = %d: channel counts must be multiples of 8, at least 8 (16-byte staging chunks)", (int)cin, (int)cout);
+    OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_c8_bf16: NULL buffer");
+    return wgrad_c8_launch(ctx, "obb_conv_wgrad_c8_bf16", x, dy, B, H, W, cin, cout, ks, stride, dw, (hipStream_t)s);
 }
 
 int obb_silu_bf16(obb_ctx *ctx, const uint16_t *z, uint16_t *a, int64_t n, obb_stream_t s) {

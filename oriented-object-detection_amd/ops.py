@@ -527,6 +527,23 @@ def conv_wgrad_bf16(x, dy, ks, stride=1, out=None):
     return dw
 
 
+def conv_wgrad_c8_bf16(x, dy, ks, stride=1, out=None):
+    """conv_wgrad_bf16 for channel counts that are multiples of 8 (both at least 8), not only of 64: x bf16 [B,H,W,cin], dy bf16 [B,Ho,Wo,cout]
+    (NHWC, device) -> dw fp32 [cout,cin,ks,ks] (into `out` if given); the same fp32 accumulation of exact products, deterministic.  At multiples
+    of 64 it computes the same sums in another order than conv_wgrad_bf16 (train.wgrad_route keeps those on conv_wgrad_bf16)."""
+    _stride_ok(ks, stride)
+    xx, d = _chk(x, torch.bfloat16, "x"), _chk(dy, torch.bfloat16, "dy")
+    B, H, W, cin = xx.shape
+    cout = d.shape[3]
+    if tuple(d.shape[:3]) != (B, (H + stride - 1) // stride, (W + stride - 1) // stride):
+        raise ValueError(f"conv_wgrad_c8_bf16: dy {tuple(d.shape)} does not match x {tuple(xx.shape)} at stride {stride}")
+    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=xx.device) if out is None else _chk(out, torch.float32, "out")
+    if dw.shape != (cout, cin, ks, ks):
+        raise ValueError("conv_wgrad_c8_bf16: out has the wrong shape")
+    _call("obb_conv_wgrad_c8_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), int(stride), _p(dw), _stream())
+    return dw
+
+
 def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
     """fp32 OIHW master weights (device) -> the bf16 MFMA fragment order of the conv kernel for H x W input maps, packed ON THE DEVICE (no
     host repack, no synchronisation); dgrad_form: the flipped / channel-transposed weights whose forward convolution is the input gradient.

@@ -13,6 +13,8 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     latency-bound (7 xGMI links x ~153 GB/s per GPU: a 25 MB bucket is ~0.1 ms of wire time per hop);
   * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
     training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded;
+    `wgrad_route` names the weight-gradient kernel of a layer (64 x 64 blocks of dW, or csrc/convgrad.hip's k_conv_wgrad_c8 for the other
+    multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s except the cin = 3 stem and the 12- / 1-channel outputs;
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
     the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
   * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
@@ -201,6 +203,21 @@ class ParamGroups:
                 o.step(lr)
 
 
+def wgrad_route(c1, c2):
+    """Which weight-gradient op a dense conv c1 -> c2 takes: "c64" (ops.conv_wgrad_bf16: one workgroup per 64 x 64 block of dW) when both
+    channel counts are multiples of 64, "c8" (ops.conv_wgrad_c8_bf16: blocks at their live width) for every other pair of multiples of 8.
+    Anything else has no weight-gradient kernel (the cin = 3 stem, the 12- and 1-channel head outputs)."""
+    if c1 < 8 or c2 < 8 or c1 % 8 or c2 % 8:
+        raise ValueError(f"wgrad_route: {c1} -> {c2}: channel counts must be multiples of 8, at least 8")
+    return "c64" if c1 % 64 == 0 and c2 % 64 == 0 else "c8"
+
+
+def conv_wgrad(x, dy, k, s=1, out=None):
+    """dW of a dense conv through the op `wgrad_route` names for its channel counts."""
+    op = ops.conv_wgrad_bf16 if wgrad_route(x.shape[-1], dy.shape[-1]) == "c64" else ops.conv_wgrad_c8_bf16
+    return op(x, dy, k, stride=s, out=out)
+
+
 class ConvBN:
     """ONE Ultralytics `Conv(c1, c2, k, s)` block in training mode -- Conv2d(bias=False) -> BatchNorm2d (batch statistics, running statistics
     updated) -> SiLU (act=False: no SiLU, Ultralytics' `Conv(..., act=False)`) -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
@@ -248,7 +265,7 @@ class ConvBN:
             dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
         else:
             dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=False)
-        ops.conv_wgrad_bf16(x, dz, self.k, stride=self.s, out=self.dw)
+        conv_wgrad(x, dz, self.k, self.s, out=self.dw)
         bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
         if self.s == 2:
             return ops.conv_dgrad_s2_bf16(dz, bw, self.c1, H, W)
@@ -488,7 +505,7 @@ class DetectBoxBranchStep:
         out = ops.conv_fwd_bf16(a, ops.conv_pack_bf16(self.w3, H, W), self.b3, self.cout3, 1)
         loss, g = ops.dfl_loss(out.float().reshape(-1, self.cout3), target_ltrb, weight, target_scores_sum)
         d3 = g.reshape(out.shape).to(torch.bfloat16)
-        ops.conv_wgrad_bf16(a, d3, 1, out=self.dw3)
+        conv_wgrad(a, d3, 1, out=self.dw3)
         ops.bias_grad_bf16(d3, self.db3)
         d = ops.conv_fwd_bf16(d3, ops.conv_pack_bf16(self.w3, H, W, dgrad_form=True), None, self.w3.shape[1], 1)
         for blk in reversed(self.blocks):
