@@ -225,8 +225,8 @@ int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, 
  * channel counts are multiples of 8, both >= 8 -- what obb_conv_wgrad_bf16 / obb_conv_wgrad_s2_bf16 refuse below multiples of 64: model.1, the
  * C3k2 Bottlenecks down to 16 -> 8, the 1x1s behind a 48- / 96-channel concat, the head's angle branch.  (ks, stride) = (1, 1), (3, 1) or
  * (3, 2); x bf16[B][H][W][cin], dy bf16[B][Ho][Wo][cout] (Ho = H at stride 1, (H + 1) / 2 at stride 2) -> dw fp32[cout][cin][ks][ks], all on
- * the device; fp32 accumulation of exact products, deterministic (fixed summation order).  Multiples of 64 are accepted too (same bound, not
- * the same summation order as the two entry points above).  B >= 1. */
+ * the device; fp32 accumulation of exact products, deterministic (fixed summation order).  Multiples of 64 are accepted too: one kernel and
+ * one launch plan serve all three entry points, so there the results are bit-identical to the two above.  B >= 1. */
 int obb_conv_wgrad_c8_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t ks,
                            int32_t stride, float *dw, obb_stream_t s);
 /* Training-mode BatchNorm2d + SiLU of the Ultralytics Conv block (Conv2d(bias=False) -> BatchNorm2d -> SiLU, `model.train(...)`), z / a / da / dz

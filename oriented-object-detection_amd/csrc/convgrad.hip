@@ -18,13 +18,13 @@
 //   dgrad    dX[m] = sum_k dY_up[m + 1 - k] W[k] with dY_up[2i] = dY[i] and zeros at odd positions: the stride-1 `same` forward of the
 //            zero-inserted dY on the dgrad-form weights.  dY_up only needs the H x W extent (positions H and -1 are zeros / padding either
 //            way), so the conv writes dX directly, no crop.  It spends 4x the useful MACs (three taps of four see an inserted zero).
-//   wgrad    k_conv_wgrad<3, 2>: R output rows stage 2R + 1 input rows of width 2 Wp + 1 (one 208-pixel row of model.3 at 416 px: R = 1).
+//   wgrad    k_conv_wgrad<3, 2, ..>: R output rows stage 2R + 1 input rows of width 2 Wp + 1 (one 208-pixel row of model.3 at 416 px: R = 1).
 //
-// Channel counts that are multiples of 8 but not of 64 (obb_conv_wgrad_c8_bf16: model.1, the Bottlenecks of the C3k2 blocks down to 16 -> 8, the
-// 1x1s behind a 48- / 96-channel concat, the head's angle branch): k_conv_wgrad_c8, the same arithmetic on blocks of ceil(live / 16) fragments
-// per side -- the LDS tile at the live width, only the block's cout fragments issued, and the waves that have no cin fragment of their own
-// taking every nshare-th k step of another wave's fragment (added in fixed wave order through LDS before the slab write).  Its slabs hold
-// dW's elements only ([tap][cout][cin] per walker, summed in walker order by k_wgrad_reduce_c8).  The split is described at the kernel.
+// Channel counts: multiples of 8, at least 8, through ONE kernel (k_conv_wgrad) on blocks of ceil(live / 16) fragments per side -- the LDS tile
+// at the live width, only the block's cout fragments issued, and the waves that have no cin fragment of their own taking every nshare-th k step
+// of another wave's fragment.  The 64 x 64 blocks run the instance whose widths are compile-time constants.  obb_conv_wgrad_bf16 /
+// obb_conv_wgrad_s2_bf16 (multiples of 64 only) and obb_conv_wgrad_c8_bf16 are checks in front of the same launcher: at multiples of 64 they
+// give the same bits.  The split is described at the kernel.
 #include <algorithm>
 #include <vector>
 
@@ -38,111 +38,40 @@ typedef __attribute__((ext_vector_type(4))) float f32x4g;
 
 __device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 
-// Workgroup = 4 waves = one (64-cout block, 64-cin block) pair of dW for all KS*KS taps; wave w owns the cin fragment w (16 channels)
-// and all four cout fragments: acc[4][TAPS] tiles of 16 x 16.  A tile of the input = R rows x W pixels of one image: dY rows padded
-// with zeros to a multiple of 4 pixels (the k step), X rows with the zero halo of the convolution's padding.
-// S = 2: X is H x W, dY is Ho x Wo; R dY rows need (R - 1) S + KS X rows of (Wp - 1) S + KS pixels.
-template <int KS, int S = 1>
-__global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int Ho, int Wo,
-                                                   int cin, int cout, int R, float *__restrict__ slabs) {
-    extern __shared__ __attribute__((aligned(16))) unsigned short swg[];
-    constexpr int TAPS = KS * KS, PAD = KS / 2;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4, r16 = lane & 15;
-    const int cob = blockIdx.y, cib = blockIdx.z;
-    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * S + KS, Rx = (R - 1) * S + KS;  // padded widths of the dY / X tiles, X rows
-    unsigned short *sx = swg, *sdy = swg + (size_t)Rx * Wx * 64;
-    const int tiles_y = (Ho + R - 1) / R, ntiles = B * tiles_y;
-    f32x4g acc[4][TAPS];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int t = 0; t < TAPS; ++t) acc[c][t] = f32x4g{0.f, 0.f, 0.f, 0.f};
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int b = tile / tiles_y, y0 = (tile % tiles_y) * R;
-        __syncthreads();
-        // stage X rows y0 S - PAD .. (y0 + R - 1) S + PAD, pixels -PAD .. (Wp - 1) S + PAD, 64 channels of block cib (16-byte chunks, zeros outside)
-        for (int i = tid; i < Rx * Wx * 8; i += 256) {
-            const int c8 = i & 7, px = (i >> 3) % Wx, ry = (i >> 3) / Wx;
-            const int yy = y0 * S + ry - PAD, xx = px - PAD;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = *reinterpret_cast<const uint4 *>(x + (((int64_t)b * H + yy) * W + xx) * cin + cib * 64 + c8 * 8);
-            *reinterpret_cast<uint4 *>(sx + ((size_t)ry * Wx + px) * 64 + c8 * 8) = v;
-        }
-        for (int i = tid; i < R * Wp * 8; i += 256) {
-            const int c8 = i & 7, px = (i >> 3) % Wp, ry = (i >> 3) / Wp;
-            const int yy = y0 + ry;
-            uint4 v = make_uint4(0u, 0u, 0u, 0u);
-            if (yy < Ho && px < Wo) v = *reinterpret_cast<const uint4 *>(dy + (((int64_t)b * Ho + yy) * Wo + px) * cout + cob * 64 + c8 * 8);
-            *reinterpret_cast<uint4 *>(sdy + ((size_t)ry * Wp + px) * 64 + c8 * 8) = v;
-        }
-        __syncthreads();
-        for (int ry = 0; ry < R; ++ry)
-            for (int x0 = 0; x0 < Wp; x0 += 4) {  // one k step = 4 consecutive pixels of a row; lane group g takes pixel x0 + g
-                float a[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + x0 + g) * 64 + c * 16 + r16]);
-#pragma unroll
-                for (int t = 0; t < TAPS; ++t) {
-                    const int ky = t / KS, kx = t % KS;
-                    const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + (x0 + g) * S + kx) * 64 + wave * 16 + r16]);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
-                }
-            }
-    }
-    // slab of this workgroup: [tap][co 64][ci 64] fp32; D layout: lane holds ci = r16 (column), couts 4 g .. 4 g + 3 (rows) of each tile
-    float *slab = slabs + ((((size_t)blockIdx.x * gridDim.y + cob) * gridDim.z + cib) * TAPS) * 4096;
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) slab[(size_t)t * 4096 + (c * 16 + 4 * g + q) * 64 + wave * 16 + r16] = acc[c][t][q];
-}
-
-// dW[co][ci][tap] (OIHW, fp32) = sum over the walkers' slabs, in walker order
-__global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ slabs, int nwalk, int ncob, int ncib, int taps, int cin, int cout, float *__restrict__ dw) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t per = (int64_t)ncob * ncib * taps * 4096;
-    if (i >= per) return;
-    float s = 0.f;
-    for (int w = 0; w < nwalk; ++w) s += slabs[(size_t)w * per + i];
-    const int ci_l = (int)(i & 63), co_l = (int)((i >> 6) & 63), t = (int)((i >> 12) % taps), blk = (int)(i / ((int64_t)taps * 4096));
-    const int cib = blk % ncib, cob = blk / ncib;
-    const int co = cob * 64 + co_l, ci = cib * 64 + ci_l;
-    if (co < cout && ci < cin) dw[((size_t)co * cin + ci) * taps + t] = s;
-}
-
-// ---- wgrad at any channel counts that are multiples of 8 (k_conv_wgrad_c8): the same tiles, the same walk and the same arithmetic as
-// k_conv_wgrad, for blocks of dW that are narrower than 64 x 64.  Channel blocks are ceil(c / 64) per side; the last block of a side holds
-// c % 64 live channels (8 .. 56).  The launcher issues one launch per CLASS of blocks -- (full | partial cout block) x (full | partial cin
-// block), at most four -- so that within a launch every workgroup has the same shape:
-//   NCF   (template) cout fragments of the block = ceil(live cout / 16): acc[NCF][TAPS]; a 16 -> 8 layer issues 1 x TAPS MFMAs per k step
-//   ncif  cin fragments of the block = ceil(live cin / 16)
-// LDS tile at the LIVE width: X pixels are ncif * 16 channels apart, dY pixels NCF * 16 (not 64), staged in 16-byte chunks; a chunk whose
-// first channel is >= the live count (the upper half of a fragment with 8 live channels) is zero-filled and never read from memory.
-// Wave split: a wave owns ONE cin fragment, as in k_conv_wgrad.  With ncif < 4 the other waves take a share of the reduction of the same
+// One workgroup = 4 waves = one (cout block, cin block) pair of dW for all KS*KS taps.  Channel blocks are ceil(c / 64) per side; the last block
+// of a side holds c % 64 live channels (8 .. 56).  A tile of the input = R rows x W pixels of one image: dY rows padded with zeros to a multiple
+// of 4 pixels (the k step), X rows with the zero halo of the convolution's padding.  S = 2: X is H x W, dY is Ho x Wo; R dY rows need
+// (R - 1) S + KS X rows of (Wp - 1) S + KS pixels.  The launcher issues one launch per CLASS of blocks -- (full | partial cout block) x
+// (full | partial cin block), at most four -- so that within a launch every workgroup has the same shape:
+//   NCF   cout fragments of the block = ceil(live cout / 16): acc[NCF][TAPS] tiles of 16 x 16; a 16 -> 8 layer issues 1 x TAPS MFMAs per k step
+//   CIF   4: the (full cout block) x (full cin block) class -- 64 live channels per side, so the pixel strides, the staging index arithmetic and
+//         the wave split are compile-time constants and no liveness test is left; 0: cin fragments = the argument ncif = ceil(live cin / 16)
+// LDS tile at the LIVE width: X pixels are ncif * 16 channels apart, dY pixels NCF * 16, staged in 16-byte chunks; a chunk whose first channel
+// is >= the live count (the upper half of a fragment with 8 live channels) is zero-filled and never read from memory.
+// Wave split: a wave owns ONE cin fragment and all NCF cout fragments.  With ncif < 4 the other waves take a share of the reduction of the same
 // fragment: nshare = 4 / ncif (4, 2, 1, 1) waves per fragment, wave w -> fragment w % ncif, share w / ncif; the k steps of a tile (4 pixels of
 // a row each) are numbered row-major and share s takes steps s, s + nshare, ...  (ncif = 3 leaves wave 3 without work: 3 does not divide 4.)
 // After the walk the shares' accumulators are added into share 0's in share order 1, 2, 3, tap by tap through LDS (the tile is dead by then),
 // and share 0 writes the workgroup's slab.  Slab of a walker = fp32 [tap][cout][cin], exactly dW's elements: nothing outside is written.
-template <int KS, int S, int NCF>
-__global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int Ho,
-                                                      int Wo, int cin, int cout, int R, int cob0, int cib0, int ncif, float *__restrict__ slabs) {
+template <int KS, int S, int NCF, int CIF>
+__global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__restrict__ x, const unsigned short *__restrict__ dy, int B, int H, int W, int Ho, int Wo,
+                                                   int cin, int cout, int R, int cob0, int cib0, int ncif_arg, float *__restrict__ slabs) {
+    static_assert(CIF == 0 || (CIF == 4 && NCF == 4), "CIF = 4 is the full x full class; every other class reads ncif from the argument");
     extern __shared__ __attribute__((aligned(16))) unsigned short swg[];
-    constexpr int TAPS = KS * KS, PAD = KS / 2, COW = NCF * 16;
+    constexpr int TAPS = KS * KS, PAD = KS / 2, COW = NCF * 16, ych = COW >> 3;
+    constexpr bool FULL = CIF == 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, r16 = lane & 15;
     const int cob = cob0 + blockIdx.y, cib = cib0 + blockIdx.z;
-    const int co_live = min(64, cout - cob * 64), ci_live = min(64, cin - cib * 64);  // multiples of 8; ceil(co_live / 16) == NCF, ceil(ci_live / 16) == ncif
-    const int CIW = ncif * 16, xch = CIW >> 3, ych = COW >> 3;                       // channels per staged pixel; 16-byte chunks per pixel
-    const int nshare = 4 / ncif, frag = wave % ncif, share = wave / ncif;
+    const int ncif = FULL ? 4 : ncif_arg;
+    const int co_live = FULL ? 64 : min(64, cout - cob * 64), ci_live = FULL ? 64 : min(64, cin - cib * 64);  // multiples of 8; ceil(live / 16) == NCF, ncif
+    const int CIW = ncif * 16, xch = CIW >> 3;  // channels per staged pixel; 16-byte chunks per pixel
+    const int nshare = 4 / ncif, frag = FULL ? wave : wave % ncif, share = FULL ? 0 : wave / ncif;
     const bool active = share < nshare;
-    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * S + KS, Rx = (R - 1) * S + KS;
+    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * S + KS, Rx = (R - 1) * S + KS;  // padded widths of the dY / X tiles, X rows
     unsigned short *sx = swg, *sdy = swg + (size_t)Rx * Wx * CIW;
     const int tiles_y = (Ho + R - 1) / R, ntiles = B * tiles_y;
-    const int spr = Wp >> 2, nsteps = R * spr;  // k steps per row / per tile
+    const int spr = Wp >> 2;  // k steps per row
     f32x4g acc[NCF][TAPS];
 #pragma unroll
     for (int c = 0; c < NCF; ++c)
@@ -151,6 +80,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__r
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int b = tile / tiles_y, y0 = (tile % tiles_y) * R;
         __syncthreads();
+        // stage X rows y0 S - PAD .. (y0 + R - 1) S + PAD, pixels -PAD .. (Wp - 1) S + PAD of block cib (16-byte chunks, zeros outside)
         for (int i = tid; i < Rx * Wx * xch; i += 256) {
             const int c8 = i % xch, px = (i / xch) % Wx, ry = (i / xch) / Wx;
             const int yy = y0 * S + ry - PAD, xx = px - PAD;
@@ -167,9 +97,28 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__r
             *reinterpret_cast<uint4 *>(sdy + ((size_t)ry * Wp + px) * COW + c8 * 8) = v;
         }
         __syncthreads();
-        if (active)
-            for (int q = share; q < nsteps; q += nshare) {  // this wave's k steps of the tile
-                const int ry = q / spr, xg = (q % spr) * 4 + g;
+        // One k step = 4 consecutive pixels of row ry, from pixel 4 xs: lane group g takes one.  The step body stands twice, once per walk: as a
+        // lambda shared by both, four narrow shapes measured 2 - 3 % slower than the former kernel (profiles/wgrad_unified.md).
+        if constexpr (FULL) {  // every step of the tile, row by row: no division in the walk
+            for (int ry = 0; ry < R; ++ry)
+                for (int xs = 0; xs < spr; ++xs) {
+                    const int xg = xs * 4 + g;
+                    float a[NCF];
+#pragma unroll
+                    for (int c = 0; c < NCF; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
+#pragma unroll
+                    for (int t = 0; t < TAPS; ++t) {
+                        const int ky = t / KS, kx = t % KS;
+                        const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
+#pragma unroll
+                        for (int c = 0; c < NCF; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
+                    }
+                }
+        } else if (active) {  // the steps of a tile are numbered row-major; this wave takes steps share, share + nshare, ...
+            const int nsteps = R * spr;
+            for (int q = share; q < nsteps; q += nshare) {
+                const int ry = q / spr, xs = q % spr;
+                const int xg = xs * 4 + g;
                 float a[NCF];
 #pragma unroll
                 for (int c = 0; c < NCF; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
@@ -181,6 +130,7 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__r
                     for (int c = 0; c < NCF; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
                 }
             }
+        }
     }
     if (nshare > 1) {  // (workgroup-uniform) shares 1 .. nshare - 1 -> share 0, in share order; red[share - 1][frag][c][q][lane]
         float *red = reinterpret_cast<float *>(swg);
@@ -202,23 +152,25 @@ __global__ __launch_bounds__(256) void k_conv_wgrad_c8(const unsigned short *__r
         }
     }
     if (!active || share != 0) return;
-    // D layout: lane holds ci = frag * 16 + r16 (column), couts c * 16 + 4 g .. + 3 (rows) of each tile; only dW's own elements are stored
-    float *slab = slabs + (size_t)blockIdx.x * TAPS * cout * cin;
+    // D layout: lane holds ci = frag * 16 + r16 (column), couts c * 16 + 4 g .. + 3 (rows) of each tile; only dW's own elements are stored.
+    // Address = a workgroup-uniform row pointer + one per-lane byte offset that is the same for every store.
     const int ci_l = frag * 16 + r16;
     if (ci_l >= ci_live) return;
+    const size_t tap_stride = (size_t)cout * cin;
+    const float *slab = slabs + (size_t)blockIdx.x * TAPS * tap_stride + (size_t)cob * 64 * cin + cib * 64;
+    const unsigned lane_bytes = ((unsigned)(4 * g) * cin + ci_l) * 4u;
 #pragma unroll
-    for (int t = 0; t < TAPS; ++t)
+    for (int t = 0; t < TAPS; ++t, slab += tap_stride)
 #pragma unroll
         for (int c = 0; c < NCF; ++c)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int co_l = c * 16 + 4 * g + q;
-                if (co_l < co_live) slab[((size_t)t * cout + cob * 64 + co_l) * cin + cib * 64 + ci_l] = acc[c][t][q];
-            }
+            for (int q = 0; q < 4; ++q)
+                if (c * 16 + 4 * g + q < co_live)
+                    *reinterpret_cast<float *>((char *)(slab + (unsigned)(c * 16 + q) * (unsigned)cin) + lane_bytes) = acc[c][t][q];
 }
 
-// dW[co][ci][tap] = sum over the walkers' [tap][cout][cin] slabs, in walker order
-__global__ __launch_bounds__(256) void k_wgrad_reduce_c8(const float *__restrict__ slabs, int nwalk, int taps, int cin, int cout, float *__restrict__ dw) {
+// dW[co][ci][tap] (OIHW, fp32) = sum over the walkers' [tap][cout][cin] slabs, in walker order
+__global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ slabs, int nwalk, int taps, int cin, int cout, float *__restrict__ dw) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t per = (int64_t)taps * cout * cin;
     if (i >= per) return;
@@ -331,41 +283,17 @@ namespace {
 // the layer shapes of the training entry points: (stride 1) H x W -> H x W, (stride 2, 3x3) H x W -> (H + 1) / 2 x (W + 1) / 2
 int out_dim(int n, int stride) { return stride == 2 ? (n + 1) / 2 : n; }
 
-int wgrad_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *dy, int B, int H, int W, int cin, int cout, int ks, int stride, float *dw,
-                 hipStream_t st) {
-    const int taps = ks * ks, Ho = out_dim(H, stride), Wo = out_dim(W, stride);
-    const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * stride + ks;
-    auto lds_of = [&](int R) { return ((size_t)((R - 1) * stride + ks) * Wx + (size_t)R * Wp) * 128; };
-    int R = 1;  // rows per tile: as many as 64 KiB of LDS hold
-    while (R < Ho && lds_of(R + 1) <= 64 * 1024) ++R;
-    const size_t lds = lds_of(R);
-    OBB_REQUIRE(ctx, lds <= 64 * 1024, "%s: a row of %d pixels does not fit the LDS tile", fn, W);
-    const int ncob = cout / 64, ncib = cin / 64;
-    OBB_REQUIRE(ctx, ncob >= 1 && ncib >= 1, "%s: cin = %d, cout = %d: at least 64 channels each", fn, cin, cout);  // (0 % 64 == 0: no division by zero below)
-    const int ntiles = B * ((Ho + R - 1) / R);
-    int nwalk = std::max(1, std::min(ntiles, 512 / (ncob * ncib)));
-    const size_t per = (size_t)ncob * ncib * taps * 4096;
-    float *slabs = (float *)ctx->workspace(WS_TRAIN_C, (size_t)nwalk * per * 4);
-    if (!slabs) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
-    const dim3 grid((unsigned)nwalk, (unsigned)ncob, (unsigned)ncib);
-    if (stride == 2) hipLaunchKernelGGL((k_conv_wgrad<3, 2>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
-    else if (ks == 3) hipLaunchKernelGGL((k_conv_wgrad<3>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
-    else hipLaunchKernelGGL((k_conv_wgrad<1>), grid, dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, slabs);
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, ncob, ncib, taps, cin, cout, dw);
-    OBB_LAUNCH_CHECK(ctx);
-    return OBB_OK;
-}
-
-// ---- k_conv_wgrad_c8's launch plan
-using WgradC8Fn = void (*)(const unsigned short *, const unsigned short *, int, int, int, int, int, int, int, int, int, int, int, float *);
+// ---- k_conv_wgrad's launch plan
+using WgradFn = void (*)(const unsigned short *, const unsigned short *, int, int, int, int, int, int, int, int, int, int, int, float *);
 
 template <int KS, int S>
-WgradC8Fn wgrad_c8_kernel(int ncf) {
-    switch (ncf) {
-        case 1: return k_conv_wgrad_c8<KS, S, 1>;
-        case 2: return k_conv_wgrad_c8<KS, S, 2>;
-        case 3: return k_conv_wgrad_c8<KS, S, 3>;
-        default: return k_conv_wgrad_c8<KS, S, 4>;
+WgradFn wgrad_kernel(int ncof, bool full) {
+    if (full) return k_conv_wgrad<KS, S, 4, 4>;
+    switch (ncof) {
+        case 1: return k_conv_wgrad<KS, S, 1, 0>;
+        case 2: return k_conv_wgrad<KS, S, 2, 0>;
+        case 3: return k_conv_wgrad<KS, S, 3, 0>;
+        default: return k_conv_wgrad<KS, S, 4, 0>;
     }
 }
 
@@ -373,18 +301,17 @@ constexpr size_t kWgradLdsDefault = 64 * 1024, kWgradLdsMax = 160 * 1024;  // wi
 
 // LDS of one workgroup whose block has ncif cin and ncof cout fragments: the tile at the live width, or the cross-wave reduction's 4 ncof
 // floats per lane of every wave with a share > 0, whichever is larger
-size_t wgrad_c8_lds(int R, int ks, int stride, int Wp, int Wx, int ncif, int ncof) {
+size_t wgrad_lds(int R, int ks, int stride, int Wp, int Wx, int ncif, int ncof) {
     const size_t tile = ((size_t)((R - 1) * stride + ks) * Wx * ncif + (size_t)R * Wp * ncof) * 32;
     const int nshare = 4 / ncif;
     return std::max(tile, (size_t)(nshare - 1) * ncif * ncof * 1024);
 }
 
-// Blocks of 64 channels per side, the last one partial; one launch per class of blocks (see k_conv_wgrad_c8).  R rows per tile: as many as the
+// Blocks of 64 channels per side, the last one partial; one launch per class of blocks (see k_conv_wgrad).  R rows per tile: as many as the
 // default 64 KiB hold at the widest class; a single row beyond that raises the kernel's cap (allow_dyn_lds) up to the CU's 160 KiB; a row
-// that does not fit then is refused.  Walkers: at most 512 / (blocks of dW) per block, as in wgrad_launch; slabs in WS_TRAIN_C (shared with
-// wgrad_launch: both fill the slot and consume it on the same stream before returning to the caller's next op).
-int wgrad_c8_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *dy, int B, int H, int W, int cin, int cout, int ks, int stride, float *dw,
-                    hipStream_t st) {
+// that does not fit then is refused.  Walkers: at most 512 / (blocks of dW) per block; slabs in WS_TRAIN_C.
+int wgrad_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint16_t *dy, int B, int H, int W, int cin, int cout, int ks, int stride, float *dw,
+                 hipStream_t st) {
     const int taps = ks * ks, Ho = out_dim(H, stride), Wo = out_dim(W, stride);
     const int Wp = (Wo + 3) & ~3, Wx = (Wp - 1) * stride + ks;
     const int ncob = (cout + 63) / 64, ncib = (cin + 63) / 64;
@@ -392,23 +319,24 @@ int wgrad_c8_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint1
     const int pcof = (cout % 64 + 15) / 16, pcif = (cin % 64 + 15) / 16;  // fragments of the partial block (0: none)
     const int wcof = fco ? 4 : pcof, wcif = fci ? 4 : pcif;               // the widest class
     int R = 1;
-    while (R < Ho && wgrad_c8_lds(R + 1, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsDefault) ++R;
-    OBB_REQUIRE(ctx, wgrad_c8_lds(R, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsMax,
+    while (R < Ho && wgrad_lds(R + 1, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsDefault) ++R;
+    OBB_REQUIRE(ctx, wgrad_lds(R, ks, stride, Wp, Wx, wcif, wcof) <= kWgradLdsMax,
                 "%s: a row of %d pixels at %d x %d channels per block does not fit the LDS tile (%zu bytes of %zu)", fn, W, wcif * 16, wcof * 16,
-                wgrad_c8_lds(R, ks, stride, Wp, Wx, wcif, wcof), kWgradLdsMax);
+                wgrad_lds(R, ks, stride, Wp, Wx, wcif, wcof), kWgradLdsMax);
     const int ntiles = B * ((Ho + R - 1) / R);
     const int nwalk = std::max(1, std::min(ntiles, 512 / (ncob * ncib)));
     const size_t per = (size_t)taps * cout * cin;
     float *slabs = (float *)ctx->workspace(WS_TRAIN_C, (size_t)nwalk * per * 4);
     if (!slabs) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
-    // classes: {first block, block count, fragments} per side
+    // classes: {first block, block count, fragments} per side; class 0 of a side = its full blocks
     const int co_cls[2][3] = {{0, fco, 4}, {fco, pcof ? 1 : 0, pcof}}, ci_cls[2][3] = {{0, fci, 4}, {fci, pcif ? 1 : 0, pcif}};
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 2; ++b) {
             const int *co = co_cls[a], *ci = ci_cls[b];
             if (!co[1] || !ci[1]) continue;
-            const WgradC8Fn k = stride == 2 ? wgrad_c8_kernel<3, 2>(co[2]) : ks == 3 ? wgrad_c8_kernel<3, 1>(co[2]) : wgrad_c8_kernel<1, 1>(co[2]);
-            const size_t lds = wgrad_c8_lds(R, ks, stride, Wp, Wx, ci[2], co[2]);
+            const bool full = a == 0 && b == 0;
+            const WgradFn k = stride == 2 ? wgrad_kernel<3, 2>(co[2], full) : ks == 3 ? wgrad_kernel<3, 1>(co[2], full) : wgrad_kernel<1, 1>(co[2], full);
+            const size_t lds = wgrad_lds(R, ks, stride, Wp, Wx, ci[2], co[2]);
             if (lds > kWgradLdsDefault) {
                 hipError_t e = allow_dyn_lds(reinterpret_cast<const void *>(k), kWgradLdsMax);
                 if (e != hipSuccess) return set_error(ctx, OBB_ERR_HIP, "%s: raising the LDS cap failed: %s", fn, hipGetErrorString(e));
@@ -416,7 +344,7 @@ int wgrad_c8_launch(obb_ctx *ctx, const char *fn, const uint16_t *x, const uint1
             hipLaunchKernelGGL(k, dim3((unsigned)nwalk, (unsigned)co[1], (unsigned)ci[1]), dim3(256), lds, st, x, dy, B, H, W, Ho, Wo, cin, cout, R, co[0], ci[0], ci[2],
                                slabs);
         }
-    hipLaunchKernelGGL(k_wgrad_reduce_c8, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, taps, cin, cout, dw);
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)cdiv((int64_t)per, 256)), dim3(256), 0, st, slabs, nwalk, taps, cin, cout, dw);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }
@@ -494,33 +422,12 @@ int obb_conv_dgrad_bf16(obb_ctx *ctx, const uint16_t *dy, const float *w_oihw_ho
             for (int t = 0; t < taps; ++t) wt[((size_t)ci * cout + co) * taps + (taps - 1 - t)] = w_oihw_host[((size_t)co * cin + ci) * taps + t];
     const ConvTiling t = plan_conv(ks, 1, cout, cin, H, W, false);
     const std::vector<bf16_t> pk = pack_conv_weights(wt.data(), cin, cout, ks, t, nullptr, 0, false);
-    const size_t wbytes = pk.size() * sizeof(bf16_t), bbytes = ((size_t)cin + 63) / 64 * 64 * 4 + 256;
-    // [packed weights][zero bias][2 KiB: the forward kernel's `lut` argument -- unused as a table here (no uint8 input), but lanes without an
-    //  output pixel store into lut + 512 B .. + 1.5 KiB (conv.hip EXACT: every store unconditional), so it must be real memory]
-    const size_t woff = (wbytes + 255) & ~(size_t)255, boff = (bbytes + 255) & ~(size_t)255;
-    char *ws = (char *)ctx->workspace(WS_TRAIN_B, woff + boff + 2048);
-    if (!ws) return set_error(ctx, OBB_ERR_HIP, "obb_conv_dgrad_bf16: workspace allocation failed");
-    float *bias = (float *)(ws + woff);
-    const bf16_t *sink = (const bf16_t *)(ws + woff + boff);
-    OBB_HIP(ctx, hipMemcpyAsync(ws, pk.data(), wbytes, hipMemcpyHostToDevice, st));
-    OBB_HIP(ctx, hipMemsetAsync(bias, 0, bbytes, st));
+    const size_t wbytes = pk.size() * sizeof(bf16_t);
+    bf16_t *wpk = (bf16_t *)ctx->workspace(WS_TRAIN_B, wbytes);
+    if (!wpk) return set_error(ctx, OBB_ERR_HIP, "obb_conv_dgrad_bf16: workspace allocation failed");
+    OBB_HIP(ctx, hipMemcpyAsync(wpk, pk.data(), wbytes, hipMemcpyHostToDevice, st));
     OBB_HIP(ctx, hipStreamSynchronize(st));  // (the packed weights live in host memory that goes out of scope)
-    ConvLaunch L;
-    L.in.p = (void *)dy; L.in.bs = (int64_t)H * W * cout; L.in.cs = cout; L.in.co = 0;
-    L.out.p = (void *)dx; L.out.bs = (int64_t)H * W * cin; L.out.cs = cin; L.out.co = 0;
-    L.wpk = (const bf16_t *)ws; L.bias = bias; L.lut = sink;
-    L.B = B; L.Hin = L.Hout = H; L.Win = L.Wout = W; L.cin = cout; L.cout = cin; L.ks = ks; L.stride = 1; L.act = 0; L.f16 = 0;
-    L.TH = t.TH; L.TW = t.TW; L.MF = t.MF; L.NF = t.NF; L.CK = t.CK;
-    L.tiles_y = (H + t.TH - 1) / t.TH; L.tiles_x = (W + t.TW - 1) / t.TW;
-    if (ks == 1) {  // 1x1: batch x pixels is one dense pixel row (as the forward engine issues it)
-        const int64_t npx = (int64_t)B * H * W;
-        OBB_REQUIRE(ctx, npx < (1ll << 31) / 4, "obb_conv_dgrad_bf16: too many pixels for one launch");
-        L.B = 1; L.Hin = L.Hout = 1; L.Win = L.Wout = (int)npx;
-        L.tiles_y = 1; L.tiles_x = (int)((npx + L.TW - 1) / L.TW);
-    }
-    hipError_t e = launch_conv(L, st);
-    if (e != hipSuccess) return set_error(ctx, OBB_ERR_HIP, "obb_conv_dgrad_bf16: launch failed: %s", hipGetErrorString(e));
-    return OBB_OK;
+    return fwd_launch(ctx, "obb_conv_dgrad_bf16", dy, (const uint16_t *)wpk, nullptr, B, H, W, cout, cin, ks, 1, dx, st);
 }
 
 int obb_conv_wgrad_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t ks, float *dw,
@@ -528,6 +435,7 @@ int obb_conv_wgrad_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int
     OBB_REQUIRE(ctx, ctx && B >= 1 && H > 0 && W > 0 && (ks == 1 || ks == 3), "obb_conv_wgrad_bf16: bad arguments");
     OBB_REQUIRE(ctx, cin % 64 == 0 && cout % 64 == 0, "obb_conv_wgrad_bf16: channel counts must be multiples of 64 (one workgroup = a 64 x 64 block of dW)");
     OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_bf16: NULL buffer");
+    OBB_REQUIRE(ctx, cin >= 64 && cout >= 64, "obb_conv_wgrad_bf16: cin = %d, cout = %d: at least 64 channels each", (int)cin, (int)cout);  // (0 % 64 == 0)
     return wgrad_launch(ctx, "obb_conv_wgrad_bf16", x, dy, B, H, W, cin, cout, ks, 1, dw, (hipStream_t)s);
 }
 
@@ -589,6 +497,7 @@ int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, 
                 "obb_conv_wgrad_s2_bf16: cin = %d, cout = %d: channel counts must be multiples of 64 (one workgroup = a 64 x 64 block of dW); "
                 "models 0 and 1 of the backbone (3 -> 32, 32 -> 64) have no stride-2 wgrad", (int)cin, (int)cout);
     OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_s2_bf16: NULL buffer");
+    OBB_REQUIRE(ctx, cin >= 64 && cout >= 64, "obb_conv_wgrad_s2_bf16: cin = %d, cout = %d: at least 64 channels each", (int)cin, (int)cout);  // (0 % 64 == 0)
     return wgrad_launch(ctx, "obb_conv_wgrad_s2_bf16", x, dy, B, H, W, cin, cout, 3, 2, dw, (hipStream_t)s);
 }
 
@@ -600,7 +509,7 @@ int obb_conv_wgrad_c8_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, 
     OBB_REQUIRE(ctx, cin >= 8 && cout >= 8 && cin % 8 == 0 && cout % 8 == 0,
                 "obb_conv_wgrad_c8_bf16: cin = %d, cout = %d: channel counts must be multiples of 8, at least 8 (16-byte staging chunks)", (int)cin, (int)cout);
     OBB_REQUIRE(ctx, x && dy && dw, "obb_conv_wgrad_c8_bf16: NULL buffer");
-    return wgrad_c8_launch(ctx, "obb_conv_wgrad_c8_bf16", x, dy, B, H, W, cin, cout, ks, stride, dw, (hipStream_t)s);
+    return wgrad_launch(ctx, "obb_conv_wgrad_c8_bf16", x, dy, B, H, W, cin, cout, ks, stride, dw, (hipStream_t)s);
 }
 
 int obb_silu_bf16(obb_ctx *ctx, const uint16_t *z, uint16_t *a, int64_t n, obb_stream_t s) {

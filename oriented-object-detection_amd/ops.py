@@ -508,40 +508,37 @@ def _stride_ok(ks, stride):
         raise ValueError(f"stride {stride} with k = {ks}: stride 1 (k 1 or 3) and stride 2 (k 3) are built")
 
 
-def conv_wgrad_bf16(x, dy, ks, stride=1, out=None):
-    """x bf16 [B,H,W,cin], dy bf16 [B,Ho,Wo,cout] (NHWC, device) -> dw fp32 [cout,cin,ks,ks] (into `out` if given): the weight gradient of the
-    `same`-padded convolution (stride 1: Ho = H; stride 2, k 3: Ho = (H + 1) // 2), fp32 accumulation, deterministic."""
+def _conv_wgrad(fn, x, dy, ks, stride, out):
+    """The body of conv_wgrad_bf16 / conv_wgrad_c8_bf16 (`fn`: the public name): the C entry points differ in the channel counts they accept."""
     _stride_ok(ks, stride)
     xx, d = _chk(x, torch.bfloat16, "x"), _chk(dy, torch.bfloat16, "dy")
     B, H, W, cin = xx.shape
     cout = d.shape[3]
     if tuple(d.shape[:3]) != (B, (H + stride - 1) // stride, (W + stride - 1) // stride):
-        raise ValueError(f"conv_wgrad_bf16: dy {tuple(d.shape)} does not match x {tuple(xx.shape)} at stride {stride}")
+        raise ValueError(f"{fn}: dy {tuple(d.shape)} does not match x {tuple(xx.shape)} at stride {stride}")
     dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=xx.device) if out is None else _chk(out, torch.float32, "out")
     if dw.shape != (cout, cin, ks, ks):
-        raise ValueError("conv_wgrad_bf16: out has the wrong shape")
-    if stride == 2:
+        raise ValueError(f"{fn}: out has the wrong shape")
+    if fn == "conv_wgrad_c8_bf16":
+        _call("obb_conv_wgrad_c8_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), int(stride), _p(dw), _stream())
+    elif stride == 2:
         _call("obb_conv_wgrad_s2_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, _p(dw), _stream())
     else:
         _call("obb_conv_wgrad_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), _p(dw), _stream())
     return dw
 
 
+def conv_wgrad_bf16(x, dy, ks, stride=1, out=None):
+    """x bf16 [B,H,W,cin], dy bf16 [B,Ho,Wo,cout] (NHWC, device) -> dw fp32 [cout,cin,ks,ks] (into `out` if given): the weight gradient of the
+    `same`-padded convolution (stride 1: Ho = H; stride 2, k 3: Ho = (H + 1) // 2), fp32 accumulation, deterministic.  Channel counts in
+    multiples of 64; anything else is refused."""
+    return _conv_wgrad("conv_wgrad_bf16", x, dy, ks, stride, out)
+
+
 def conv_wgrad_c8_bf16(x, dy, ks, stride=1, out=None):
-    """conv_wgrad_bf16 for channel counts that are multiples of 8 (both at least 8), not only of 64: x bf16 [B,H,W,cin], dy bf16 [B,Ho,Wo,cout]
-    (NHWC, device) -> dw fp32 [cout,cin,ks,ks] (into `out` if given); the same fp32 accumulation of exact products, deterministic.  At multiples
-    of 64 it computes the same sums in another order than conv_wgrad_bf16 (train.wgrad_route keeps those on conv_wgrad_bf16)."""
-    _stride_ok(ks, stride)
-    xx, d = _chk(x, torch.bfloat16, "x"), _chk(dy, torch.bfloat16, "dy")
-    B, H, W, cin = xx.shape
-    cout = d.shape[3]
-    if tuple(d.shape[:3]) != (B, (H + stride - 1) // stride, (W + stride - 1) // stride):
-        raise ValueError(f"conv_wgrad_c8_bf16: dy {tuple(d.shape)} does not match x {tuple(xx.shape)} at stride {stride}")
-    dw = torch.empty((cout, cin, ks, ks), dtype=torch.float32, device=xx.device) if out is None else _chk(out, torch.float32, "out")
-    if dw.shape != (cout, cin, ks, ks):
-        raise ValueError("conv_wgrad_c8_bf16: out has the wrong shape")
-    _call("obb_conv_wgrad_c8_bf16", ctx(xx.device), _p(xx), _p(d), B, H, W, cin, cout, int(ks), int(stride), _p(dw), _stream())
-    return dw
+    """conv_wgrad_bf16 for channel counts that are multiples of 8 (both at least 8), not only of 64: the same kernel behind another check, so at
+    multiples of 64 the two give the same bits."""
+    return _conv_wgrad("conv_wgrad_c8_bf16", x, dy, ks, stride, out)
 
 
 def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):

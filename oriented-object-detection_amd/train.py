@@ -13,8 +13,8 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     latency-bound (7 xGMI links x ~153 GB/s per GPU: a 25 MB bucket is ~0.1 ms of wire time per hop);
   * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
     training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded;
-    `wgrad_route` names the weight-gradient kernel of a layer (64 x 64 blocks of dW, or csrc/convgrad.hip's k_conv_wgrad_c8 for the other
-    multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s except the cin = 3 stem and the 12- / 1-channel outputs;
+    `wgrad_route` names the block class a layer's weight gradient runs in (csrc/convgrad.hip's k_conv_wgrad: 64 x 64 blocks of dW, or blocks at
+    their live width for the other multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s except the cin = 3 stem and the 12- / 1-channel outputs;
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
     the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
   * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
@@ -204,18 +204,18 @@ class ParamGroups:
 
 
 def wgrad_route(c1, c2):
-    """Which weight-gradient op a dense conv c1 -> c2 takes: "c64" (ops.conv_wgrad_bf16: one workgroup per 64 x 64 block of dW) when both
-    channel counts are multiples of 64, "c8" (ops.conv_wgrad_c8_bf16: blocks at their live width) for every other pair of multiples of 8.
-    Anything else has no weight-gradient kernel (the cin = 3 stem, the 12- and 1-channel head outputs)."""
+    """Which block class of the weight-gradient kernel a dense conv c1 -> c2 runs in: "c64" when both channel counts are multiples of 64 (every
+    block of dW is 64 x 64: the kernel instance with compile-time widths), "c8" for every other pair of multiples of 8 (some block at its
+    live width).  Anything else has no weight-gradient kernel (the cin = 3 stem, the 12- and 1-channel head outputs)."""
     if c1 < 8 or c2 < 8 or c1 % 8 or c2 % 8:
         raise ValueError(f"wgrad_route: {c1} -> {c2}: channel counts must be multiples of 8, at least 8")
     return "c64" if c1 % 64 == 0 and c2 % 64 == 0 else "c8"
 
 
 def conv_wgrad(x, dy, k, s=1, out=None):
-    """dW of a dense conv through the op `wgrad_route` names for its channel counts."""
-    op = ops.conv_wgrad_bf16 if wgrad_route(x.shape[-1], dy.shape[-1]) == "c64" else ops.conv_wgrad_c8_bf16
-    return op(x, dy, k, stride=s, out=out)
+    """dW of a dense conv at any channel counts `wgrad_route` accepts."""
+    wgrad_route(x.shape[-1], dy.shape[-1])  # (ValueError for channel counts without a kernel)
+    return ops.conv_wgrad_c8_bf16(x, dy, k, stride=s, out=out)
 
 
 class ConvBN:

@@ -297,3 +297,7 @@ def test_train_bn_argument_checks():
     for name, args in (("obb_conv_wgrad_s2_bf16", (1, 8, 8, 0, 64)), ("obb_conv_wgrad_bf16", (1, 4, 4, 64, 0, 3))):
         with pytest.raises(_lib.ObbHipError, match="at least 64 channels"):
             ops._call(name, ops.ctx(x64.device), ops._p(x64), ops._p(dy), *args, ops._p(dw), ops._stream())
+    # one 400-pixel row at stride 2 with 64 channels per side: 3 x 401 + 200 pixels of 128 bytes = 175 KiB, more than a CU's LDS (refused
+    # before any buffer is touched)
+    with pytest.raises(_lib.ObbHipError, match="does not fit"):
+        ops._call("obb_conv_wgrad_s2_bf16", ops.ctx(x64.device), ops._p(x64), ops._p(dy), 1, 2, 400, 64, 64, ops._p(dw), ops._stream())

@@ -1,4 +1,4 @@
-"""The weight gradient at channel counts that are multiples of 8 (csrc/convgrad.hip: k_conv_wgrad_c8 / obb_conv_wgrad_c8_bf16,
+"""The weight gradient at channel counts that are multiples of 8 (csrc/convgrad.hip: k_conv_wgrad / obb_conv_wgrad_c8_bf16,
 ops.conv_wgrad_c8_bf16) and `train.ConvBN` / `train.ClassBranchPair` on top of it, against fp64 references on the CPU computed from the same
 bf16 values the device sees.
 
@@ -70,7 +70,7 @@ def test_wgrad_c8_known_answer(c, kind):
     """Small-integer inputs: every product and every partial sum is an integer below 2^24, so the fp32 result equals the fp64 reference exactly,
     whatever the summation order.  onehot: x all ones, dy one at a single pixel and channel -- dW[co] is the indicator of the taps that land
     inside the map.  integers: x = ci + 1 + 3 (pixel index mod 5) (<= 28), dy = (co + 1)(1 + (y + 2 x + b) mod 3) (<= 24): a swapped tap, row
-    or channel changes the sums (|products| <= 672, K <= 234 terms)."""
+    or channel changes the sums (16 -> 8: |products| <= 672; 64 -> 64: x <= 76, dy <= 192, |products| <= 14592; K <= 234 terms)."""
     ops, _, _ = _mods()
     Ho, Wo = _out_map(c)
     if kind == "onehot":
@@ -89,6 +89,36 @@ def test_wgrad_c8_known_answer(c, kind):
     if kind == "onehot":
         assert float(ref[5].sum()) == c.c1 * (1 if c.k == 1 else 4) and float(ref.sum()) == float(ref[5].sum())
     assert torch.equal(got.double().cpu(), ref), f"{kind}: {int((got.double().cpu() != ref).sum())} of {ref.numel()} elements differ"
+
+
+@pytest.mark.parametrize("c", WC.ENTRY_EQUALITY_CASES, ids=[WC.case_id(c) for c in WC.ENTRY_EQUALITY_CASES])
+def test_wgrad_entry_points_agree_at_multiples_of_64(c):
+    """ops.conv_wgrad_bf16 and ops.conv_wgrad_c8_bf16 are two checks in front of one launcher: the same bits."""
+    ops, _, _ = _mods()
+    Ho, Wo = _out_map(c)
+    g = torch.Generator().manual_seed(c.k * 1000003 + c.s * 100003 + c.c1 * 1009 + c.c2 * 101 + c.B * 31 + c.H * 7 + c.W)
+    x = (torch.randn((c.B, c.H, c.W, c.c1), generator=g) * 0.7).bfloat16().cuda()
+    dy = torch.randn((c.B, Ho, Wo, c.c2), generator=g).bfloat16().cuda()
+    a, b = ops.conv_wgrad_bf16(x, dy, c.k, stride=c.s), ops.conv_wgrad_c8_bf16(x, dy, c.k, stride=c.s)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0
+    assert torch.equal(a, b), f"{int((a != b).sum())} of {a.numel()} elements differ"
+
+
+@pytest.mark.parametrize("k,c1,c2", [(3, 64, 64), (1, 64, 128)])
+def test_host_packed_dgrad_equals_the_device_packed_forward(k, c1, c2):
+    """obb_conv_dgrad_bf16 (weights flipped, transposed and packed on the host) and ops.conv_fwd_bf16 on conv_pack_bf16(..., dgrad_form=True)
+    share one packing and one launch: the same bits."""
+    ops, _lib, _ = _mods()
+    B, H, W = 2, 13, 9
+    g = torch.Generator().manual_seed(k * 1009 + c1 * 101 + c2)
+    w = torch.randn((c2, c1, k, k), generator=g) / (c1 * k * k) ** 0.5
+    dy = torch.randn((B, H, W, c2), generator=g).bfloat16().cuda()
+    host = ops.conv_dgrad_bf16(dy, w)
+    dev = ops.conv_fwd_bf16(dy, ops.conv_pack_bf16(w.cuda(), H, W, dgrad_form=True), None, c1, k)
+    torch.cuda.synchronize()
+    assert host.shape == (B, H, W, c1) and bool(torch.isfinite(host.float()).all()) and float(host.float().abs().max()) > 0
+    assert torch.equal(host, dev), f"{int((host != dev).sum())} of {host.numel()} elements differ"
 
 
 REFUSALS = [

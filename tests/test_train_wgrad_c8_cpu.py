@@ -82,4 +82,8 @@ def test_gpu_case_lists():
         if c.group == "c64":
             assert c.c1 % 64 == 0 and c.c2 % 64 == 0
     assert any(((c.W + c.s - 1) // c.s) % 4 for c in WC.GPU_CASES if c.group == "pair")
-    assert sorted((c.k, c.s) for c in WC.EXACT_CASES) == [(1, 1), (3, 1), (3, 2)] and all((c.c1, c.c2) == (16, 8) for c in WC.EXACT_CASES)
+    for cc in ((16, 8), (64, 64)):  # a narrow block and the full x full instance, each at every (k, s)
+        assert sorted((c.k, c.s) for c in WC.EXACT_CASES if (c.c1, c.c2) == cc) == [(1, 1), (3, 1), (3, 2)]
+    assert len(WC.EXACT_CASES) == 6
+    assert [(c.k, c.s, c.c1, c.c2, c.B, c.H, c.W) for c in WC.ENTRY_EQUALITY_CASES] == [
+        (3, 1, 64, 64, 2, 13, 9), (1, 1, 128, 64, 2, 13, 9), (3, 2, 64, 128, 2, 13, 9), (3, 1, 128, 128, 1, 26, 18)]

@@ -1,4 +1,4 @@
-"""Shapes of the multiple-of-8 weight-gradient kernel (csrc/convgrad.hip, k_conv_wgrad_c8 / obb_conv_wgrad_c8_bf16), shared by
+"""Shapes of the weight-gradient kernel at multiples of 8 (csrc/convgrad.hip, k_conv_wgrad / obb_conv_wgrad_c8_bf16), shared by
 test_train_wgrad_c8_cpu.py (the lists against the catalogue) and test_gpu_train_wgrad_c8.py (the kernel at each of them).
 
 NARROW_SHAPES: the dense conv shapes of YOLO11 n and s at 416 x 416 that have forward / dgrad kernels but whose channel counts are not both
@@ -60,8 +60,13 @@ GPU_CASES = (
     + _cross("lds>64K", [(3, 2, 64, 64)], [(1, 2, 208)])
 )
 
-# inputs with a known answer, one per (k, s) at 16 -> 8
-EXACT_CASES = _cross("exact", [(1, 1, 16, 8), (3, 1, 16, 8), (3, 2, 16, 8)], [(2, 13, 9)])
+# inputs with a known answer, one per (k, s) at 16 -> 8 (a narrow block) and at 64 -> 64 (the kernel instance with compile-time widths)
+EXACT_CASES = _cross("exact", [(1, 1, 16, 8), (3, 1, 16, 8), (3, 2, 16, 8), (3, 1, 64, 64), (1, 1, 64, 64), (3, 2, 64, 64)], [(2, 13, 9)])
+
+# multiples of 64, where obb_conv_wgrad_bf16 / obb_conv_wgrad_s2_bf16 and obb_conv_wgrad_c8_bf16 must give the same bits; 1 x 26 x 18 at
+# 128 -> 128: several tiles per walker, more than one row per tile, four blocks
+ENTRY_EQUALITY_CASES = (_cross("entries", [(3, 1, 64, 64), (1, 1, 128, 64), (3, 2, 64, 128)], [(2, 13, 9)])
+                        + _cross("entries", [(3, 1, 128, 128)], [(1, 26, 18)]))
 
 # train.ConvBN end to end: (k, s, c1, c2, B, H, W)
 CONVBN_CASES = [(3, 1, 16, 8, 2, 13, 9), (1, 1, 48, 64, 2, 13, 9), (3, 2, 16, 32, 2, 8, 6)]
