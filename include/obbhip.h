@@ -287,6 +287,40 @@ int obb_bn_fwd_bf16(obb_ctx *ctx, const uint16_t *z, int64_t npix, int32_t C, co
                     float *running_mean, float *running_var, float *mean, float *invstd, uint16_t *a, int32_t act, obb_stream_t s);
 int obb_bn_bwd_bf16(obb_ctx *ctx, const uint16_t *z, const uint16_t *da, int64_t npix, int32_t C, const float *gamma, const float *beta,
                     const float *mean, const float *invstd, float *dgamma, float *dbeta, uint16_t *dz, int32_t act, obb_stream_t s);
+/* The conv layers whose channel counts are no multiples of 8, in training mode (`model.train(...)`, Train_OBB.py:796-841): the head's plain
+ * Conv2d 1x1 + bias outputs (model.23.cv3.i.2: c -> nc class logits, model.23.cv4.i.2: c -> 1 angle logit) and the stem (model.0: Conv 3x3,
+ * stride 2, pad 1 on the 3- or 4-channel uint8 tile).  All buffers on the device.  w: the fp32 MASTER weights, rounded to bf16 (nearest even) by
+ * every kernel as it loads them (w~; no pack step); products and sums fp32; no padded channel is ever read from or written to global memory.
+ * HEAD, pixels flattened (N = B H W >= 1): x, dx bf16 [N][cin], cin % 8 == 0, 8 <= cin <= 512; w, dw fp32 [cout][cin], bias, db fp32 [cout],
+ *   1 <= cout <= 64; y, dy fp32 [N][cout], DENSE rows of cout floats (4-byte accesses: no row alignment is assumed); x 16-byte aligned.
+ * obb_headconv_fwd_bf16: y[n,o] = (sum_c w~[o,c] x[n,c]) + bias[o], c ascending from 0, the bias last (bias NULL: none).  fp32 out: no rounding.
+ * obb_headconv_bwd_bf16: ALL gradients from one pass over x and dy; dy is rounded to bf16 as it is loaded (dy~):
+ *   dx[n,c] = sum_o w~[o,c] dy~[n,o] (o ascending, one bf16 rounding);  dw[o,c] = sum_n dy~[n,o] x[n,c];  db[o] = sum_n dy~[n,o].
+ *   dx NULL, or dw and db both NULL: that half is skipped and nothing of it is written (x may then be NULL for dx alone, w for dw / db alone);
+ *   the half that is computed is bit-equal to the fused call's.  One of dw / db NULL: only the other is stored.  All three NULL:
+ *   OBB_ERR_INVALID.  dw / db: per-lane fp32 sums, a fixed LDS tree over the lanes of a channel, one fp32 slab per workgroup in a ctx workspace
+ *   slot, a second launch that adds the slabs in index order.  No atomics: bit-reproducible, also after the workspace slot has grown.
+ * STEM: x uint8 [B][H][W][cin], cin 3 or 4, B, H, W >= 1, channel order as stored; the operand is x~ = bf16(v / 255) (fp32 division, nearest
+ *   even: the inference stem's bf16-mode value); w, dw fp32 [cout][cin][3][3], cout % 8 == 0, 8 <= cout <= 64; z, dz bf16 [B][Ho][Wo][cout],
+ *   Ho = (H + 1) / 2, Wo = (W + 1) / 2, 16-byte aligned; x 4-byte aligned at cin = 4 (byte loads at cin = 3: any address).
+ * obb_stemconv_fwd_u8: z[b,i,j,o] = sum_{ky,kx,c} w~[o,c,ky,kx] x~[b, 2i+ky-1, 2j+kx-1, c], (ky, kx, c) ascending from 0, taps outside the map
+ *   skipped, one bf16 rounding.  No bias (BatchNorm follows).
+ * obb_stemconv_wgrad_u8: dw[o,c,ky,kx] = sum_{b,i,j} dz[b,i,j,o] x~[b, 2i+ky-1, 2j+kx-1, c]; slabs and a second launch as above.  There is no
+ *   input gradient: the input is the image.
+ * obb_headconv_bwd_geometry / obb_stemconv_wgrad_geometry: host only, no context.  out = {pixels per lane run, lane rows per workgroup RP,
+ *   number of slabs nbx, L} -- the split the launcher itself uses for that shape (it calls the same function): lane row r of workgroup bx walks
+ *   (output) pixels bx RP + r + t nbx RP, t = 0 .. run - 1; L = the longest chain of fp32 additions a dw / db element passes through
+ *   (run + ceil(log2 RP) + ceil(nbx / 64) + 6).  OBB_ERR_INVALID on a bad shape. */
+int obb_headconv_fwd_bf16(obb_ctx *ctx, const uint16_t *x, const float *w, const float *bias, int64_t N, int32_t cin, int32_t cout, float *y,
+                          obb_stream_t s);
+int obb_headconv_bwd_bf16(obb_ctx *ctx, const uint16_t *x, const float *dy, const float *w, int64_t N, int32_t cin, int32_t cout, uint16_t *dx,
+                          float *dw, float *db, obb_stream_t s);
+int obb_headconv_bwd_geometry(int64_t N, int32_t cin, int32_t cout, int32_t out[4]);
+int obb_stemconv_fwd_u8(obb_ctx *ctx, const uint8_t *x, const float *w, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, uint16_t *z,
+                        obb_stream_t s);
+int obb_stemconv_wgrad_u8(obb_ctx *ctx, const uint8_t *x, const uint16_t *dz, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,
+                          float *dw, obb_stream_t s);
+int obb_stemconv_wgrad_geometry(int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t out[4]);
 /* Softmax attention core of C2PSA in training mode (`model.train(...)`, Train_OBB.py:796-841 -> ultralytics Attention(dim, num_heads,
  * attn_ratio = 0.5), model.10.m.*.attn), key_dim 32, head_dim 64, all tensors on the device.  Layout, the inference core's: qkv and dqkv bf16
  * [B][N][nh * 128], per token [q: nh * 32 | k: nh * 32 | v: nh * 64] (the qkv conv's output channels in DEVICE order, heads grouped); out, dout

@@ -62,6 +62,12 @@ SIGNATURES = {
     "obb_dwconv3_fwd_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_dwconv3_bwd_bf16": [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],
     "obb_dwconv3_bwd_geometry": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip],
+    "obb_headconv_fwd_bf16": [_V, _V, _V, _V, C.c_int64, C.c_int32, C.c_int32, _V, _V],
+    "obb_headconv_bwd_bf16": [_V, _V, _V, _V, C.c_int64, C.c_int32, C.c_int32, _V, _V, _V, _V],
+    "obb_headconv_bwd_geometry": [C.c_int64, C.c_int32, C.c_int32, c_ip],
+    "obb_stemconv_fwd_u8": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_stemconv_wgrad_u8": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_stemconv_wgrad_geometry": [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_ip],
     "obb_bn_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, C.c_int32, _V],
     "obb_bn_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, C.c_int32, _V],
     "obb_attn_fwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],

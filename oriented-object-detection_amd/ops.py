@@ -295,6 +295,30 @@ def _dwconv3_bwd(x: T, dz: T, w: T, dx: Optional[T], dw: Optional[T]) -> None:
     _call("obb_dwconv3_bwd_bf16", ctx(dz.device), _p(x), _p(dz), _p(w), B, H, W, C, _p(dx), _p(dw), _stream())
 
 
+@_op("headconv_fwd", ("y",))
+def _headconv_fwd(x: T, w: T, bias: Optional[T], y: T) -> None:
+    cout, cin = w.shape
+    _call("obb_headconv_fwd_bf16", ctx(x.device), _p(x), _p(w), _p(bias), x.numel() // cin, cin, cout, _p(y), _stream())
+
+
+@_op("headconv_bwd", ("dx", "dw", "db"))
+def _headconv_bwd(x: T, dy: T, w: T, dx: Optional[T], dw: Optional[T], db: Optional[T]) -> None:
+    cout, cin = w.shape
+    _call("obb_headconv_bwd_bf16", ctx(dy.device), _p(x), _p(dy), _p(w), dy.numel() // cout, cin, cout, _p(dx), _p(dw), _p(db), _stream())
+
+
+@_op("stemconv_fwd", ("z",))
+def _stemconv_fwd(x: T, w: T, z: T) -> None:
+    B, H, W, cin = x.shape
+    _call("obb_stemconv_fwd_u8", ctx(x.device), _p(x), _p(w), B, H, W, cin, w.shape[0], _p(z), _stream())
+
+
+@_op("stemconv_wgrad", ("dw",))
+def _stemconv_wgrad(x: T, dz: T, dw: T) -> None:
+    B, H, W, cin = x.shape
+    _call("obb_stemconv_wgrad_u8", ctx(x.device), _p(x), _p(dz), B, H, W, cin, dz.shape[-1], _p(dw), _stream())
+
+
 @_op("bn_fwd", ("running_mean", "running_var", "mean", "invstd", "a"))
 def _bn_fwd(z: T, gamma: T, beta: T, eps: float, momentum: float, running_mean: T, running_var: T, mean: T, invstd: T, a: T, act: bool) -> None:
     C = z.shape[-1]
@@ -712,6 +736,113 @@ def dwconv3_bwd_geometry(B, H, W, C):
     longest chain of fp32 additions one dw element passes through."""
     out = (_ct.c_int32 * 4)()
     _lib.check(_lib.lib().obb_dwconv3_bwd_geometry(int(B), int(H), int(W), int(C), out))
+    return tuple(int(v) for v in out)
+
+
+def _head_weights(w, cin, fn):
+    ww = _chk(w, torch.float32, "w")
+    if ww.dim() == 4 and tuple(ww.shape[2:]) == (1, 1):
+        ww = ww.view(ww.shape[0], ww.shape[1])
+    if ww.dim() != 2 or ww.shape[1] != cin or not 1 <= ww.shape[0] <= 64:
+        raise ValueError(f"{fn}: w must be the 1x1 weights [cout,cin(,1,1)] with cin = {cin}, 1 <= cout <= 64, got {tuple(w.shape)}")
+    if cin % 8 or not 8 <= cin <= 512:
+        raise ValueError(f"{fn}: cin = {cin} must be a multiple of 8 in [8, 512]")
+    return ww
+
+
+def headconv_fwd_bf16(x, w, bias=None):
+    """Narrow-output 1x1 conv with bias (the head's plain Conv2d outputs: nc class logits, 1 angle logit): x bf16 [..., cin] NHWC, w fp32 MASTER
+    weights [cout,cin] or [cout,cin,1,1] (rounded to bf16 as the kernel loads them), bias fp32 [cout] or None -> y FP32 [..., cout], dense rows
+    of cout floats (what the losses read); fp32 sums, c ascending, the bias last.  cin % 8 == 0 (8 .. 512), cout 1 .. 64."""
+    xx = _chk(x, torch.bfloat16, "x")
+    if xx.dim() < 2:
+        raise ValueError("headconv_fwd_bf16: x must be [..., cin]")
+    ww = _head_weights(w, xx.shape[-1], "headconv_fwd_bf16")
+    cout = ww.shape[0]
+    bb = None if bias is None else _chk(bias, torch.float32, "bias")
+    if bb is not None and bb.numel() != cout:
+        raise ValueError("headconv_fwd_bf16: bias must have cout entries")
+    y = torch.empty(tuple(xx.shape[:-1]) + (cout,), dtype=torch.float32, device=xx.device)
+    if xx.numel():
+        _O.headconv_fwd(xx, ww, bb, y)
+    return y
+
+
+def headconv_bwd_bf16(x, dy, w, dw_out=None, db_out=None, need_dx=True):
+    """Fused backward of headconv_fwd_bf16, everything from one pass over x (bf16 [..., cin]) and dy (FP32 [..., cout], rounded to bf16 as it is
+    loaded) -> (dx bf16 like x or None when need_dx is False, dw fp32 like w, db fp32 [cout]); dw / db go into `dw_out` / `db_out` when given (e.g.
+    views of an optimiser group's gradient buffer).  Deterministic (no atomics)."""
+    xx, d = _chk(x, torch.bfloat16, "x"), _chk(dy, torch.float32, "dy")
+    if xx.dim() < 2 or d.shape[:-1] != xx.shape[:-1]:
+        raise ValueError("headconv_bwd_bf16: x [..., cin] and dy [..., cout] must agree in every dimension but the last")
+    ww = _head_weights(w, xx.shape[-1], "headconv_bwd_bf16")
+    cout, cin = ww.shape
+    if d.shape[-1] != cout:
+        raise ValueError(f"headconv_bwd_bf16: dy has {d.shape[-1]} channels, w {cout} outputs")
+    dw = torch.empty_like(w) if dw_out is None else _chk(dw_out, torch.float32, "dw_out")
+    db = torch.empty(cout, dtype=torch.float32, device=xx.device) if db_out is None else _chk(db_out, torch.float32, "db_out")
+    if dw.numel() != cout * cin or db.numel() != cout:
+        raise ValueError("headconv_bwd_bf16: dw_out must have the size of w, db_out cout entries")
+    dx = torch.empty_like(xx) if need_dx else None
+    if not xx.numel():
+        raise ValueError("headconv_bwd_bf16: no pixels")
+    _O.headconv_bwd(xx, d, ww, dx, dw, db)
+    return dx, dw, db
+
+
+def headconv_bwd_geometry(N, cin, cout):
+    """Host helper -> (pixels per lane run, lane rows per workgroup RP, number of slabs nbx, L): the split obb_headconv_bwd_bf16 uses at this shape
+    (lane row r of workgroup bx walks pixels bx RP + r + t nbx RP); L is the longest chain of fp32 additions one dw / db element passes through."""
+    out = (_ct.c_int32 * 4)()
+    _lib.check(_lib.lib().obb_headconv_bwd_geometry(int(N), int(cin), int(cout), out))
+    return tuple(int(v) for v in out)
+
+
+def _stem_args(x, w_shape, fn):
+    xx = _chk(x, torch.uint8, "x")
+    if xx.dim() != 4 or xx.shape[-1] not in (3, 4):
+        raise ValueError(f"{fn}: x must be the uint8 tile [B,H,W,3 or 4], got {tuple(xx.shape)}")
+    cin = xx.shape[-1]
+    if len(w_shape) != 4 or tuple(w_shape[1:]) != (cin, 3, 3) or w_shape[0] % 8 or not 8 <= w_shape[0] <= 64:
+        raise ValueError(f"{fn}: w must be [cout,{cin},3,3] with cout a multiple of 8 in [8, 64], got {tuple(w_shape)}")
+    return xx
+
+
+def stemconv_fwd_u8(x, w):
+    """The stem's conv (3x3, stride 2, pad 1, no bias) straight from the uint8 tile: x uint8 [B,H,W,cin] (cin 3 or 4, channel order as stored), w
+    fp32 MASTER weights [cout,cin,3,3] -> z bf16 [B,(H+1)//2,(W+1)//2,cout]; the operand is bf16(v / 255), fp32 sums, one bf16 rounding."""
+    ww = _chk(w, torch.float32, "w")
+    xx = _stem_args(x, ww.shape, "stemconv_fwd_u8")
+    B, H, W, _ = xx.shape
+    z = torch.empty((B, (H + 1) // 2, (W + 1) // 2, ww.shape[0]), dtype=torch.bfloat16, device=xx.device)
+    if z.numel():
+        _O.stemconv_fwd(xx, ww, z)
+    return z
+
+
+def stemconv_wgrad_u8(x, dz, out=None):
+    """dW of stemconv_fwd_u8: x uint8 [B,H,W,cin], dz bf16 [B,(H+1)//2,(W+1)//2,cout] -> dw fp32 [cout,cin,3,3] (into `out` when given).  There is
+    no input gradient: the input is the image.  Deterministic (no atomics)."""
+    d = _chk(dz, torch.bfloat16, "dz")
+    if d.dim() != 4:
+        raise ValueError("stemconv_wgrad_u8: dz must be [B,Ho,Wo,cout]")
+    cout = d.shape[-1]
+    xx = _stem_args(x, (cout, x.shape[-1] if x.dim() == 4 else 0, 3, 3), "stemconv_wgrad_u8")
+    B, H, W, cin = xx.shape
+    if tuple(d.shape[:3]) != (B, (H + 1) // 2, (W + 1) // 2) or not d.numel():
+        raise ValueError(f"stemconv_wgrad_u8: dz {tuple(d.shape)} is not the stride-2 output of {tuple(xx.shape)}")
+    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=xx.device) if out is None else _chk(out, torch.float32, "out")
+    if tuple(dw.shape) != (cout, cin, 3, 3):
+        raise ValueError(f"stemconv_wgrad_u8: out must be [{cout},{cin},3,3]")
+    _O.stemconv_wgrad(xx, d, dw)
+    return dw
+
+
+def stemconv_wgrad_geometry(B, H, W, cin, cout):
+    """Host helper -> (output pixels per lane run, lane rows per workgroup RP, number of slabs nbx, L): the split obb_stemconv_wgrad_u8 uses at this
+    shape (lane row r of workgroup bx walks output pixels bx RP + r + t nbx RP); L as for headconv_bwd_geometry."""
+    out = (_ct.c_int32 * 4)()
+    _lib.check(_lib.lib().obb_stemconv_wgrad_geometry(int(B), int(H), int(W), int(cin), int(cout), out))
     return tuple(int(v) for v in out)
 
 

@@ -14,7 +14,12 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
   * `ParamGroups` / `ConvBN` / `DetectBoxBranchStep`: the trainer's three groups as FlatOptimizers, the Ultralytics `Conv` block in
     training mode (batch-statistics BatchNorm + SiLU, stride 1 or 2) and the head's box branch built from it, BatchNorm unfolded;
     `wgrad_route` names the block class a layer's weight gradient runs in (csrc/convgrad.hip's k_conv_wgrad: 64 x 64 blocks of dW, or blocks at
-    their live width for the other multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s except the cin = 3 stem and the 12- / 1-channel outputs;
+    their live width for the other multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s with channels in multiples of 8;
+    `train_kernel_of` names the kernel family of ANY conv of the model ("dense" / "depthwise" / "stem" / "head_out");
+  * `StemConvBN` / `HeadOut`: the two layer kinds outside the multiples of 8 (csrc/narrowgrad.hip) -- model.0 on the 3- or 4-channel uint8 tile under
+    ConvBN's contract, and the head's plain `Conv2d` 1x1 + bias outputs (nc class logits, 1 angle logit) with fp32 logits and a fused dx + dW + db
+    backward; `DetectClassBranchStep` (Detect.cv3[i] under the BCE term, the counterpart of DetectBoxBranchStep) and `DetectAngleBranch`
+    (OBB.cv4[i], no loss of its own) are built from them;
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
     the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
   * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
@@ -206,7 +211,8 @@ class ParamGroups:
 def wgrad_route(c1, c2):
     """Which block class of the weight-gradient kernel a dense conv c1 -> c2 runs in: "c64" when both channel counts are multiples of 64 (every
     block of dW is 64 x 64: the kernel instance with compile-time widths), "c8" for every other pair of multiples of 8 (some block at its
-    live width).  Anything else has no weight-gradient kernel (the cin = 3 stem, the 12- and 1-channel head outputs)."""
+    live width).  Anything else is not a dense-kernel shape: the cin = 3 / 4 stem and the 12- and 1-channel head outputs have kernels of their
+    own (StemConvBN, HeadOut; `train_kernel_of` routes every conv of the model)."""
     if c1 < 8 or c2 < 8 or c1 % 8 or c2 % 8:
         raise ValueError(f"wgrad_route: {c1} -> {c2}: channel counts must be multiples of 8, at least 8")
     return "c64" if c1 % 64 == 0 and c2 % 64 == 0 else "c8"
@@ -216,6 +222,25 @@ def conv_wgrad(x, dy, k, s=1, out=None):
     """dW of a dense conv at any channel counts `wgrad_route` accepts."""
     wgrad_route(x.shape[-1], dy.shape[-1])  # (ValueError for channel counts without a kernel)
     return ops.conv_wgrad_c8_bf16(x, dy, k, stride=s, out=out)
+
+
+def train_kernel_of(k, s, g, c1, c2):
+    """The kernel family that trains a conv layer (kernel k, stride s, groups g, c1 -> c2) of YOLO11-OBB:
+        "dense"      ConvBN / the dense kernels, channel counts `wgrad_route` accepts, k 1 or 3 at stride 1, k 3 at stride 2;
+        "depthwise"  DWConvBN: 3x3, stride 1, g = c1 = c2, a multiple of 8;
+        "stem"       StemConvBN: 3x3, stride 2, c1 3 or 4 (the uint8 tile), c2 a multiple of 8 up to 64;
+        "head_out"   HeadOut: 1x1, stride 1, c1 a multiple of 8 up to 512, 1 <= c2 <= 64 and c2 no multiple of 8.
+    ValueError when no kernel exists."""
+    if g == 1 and c1 >= 8 and c2 >= 8 and c1 % 8 == 0 and c2 % 8 == 0 and ((k in (1, 3) and s == 1) or (k == 3 and s == 2)):
+        wgrad_route(c1, c2)
+        return "dense"
+    if g > 1 and g == c1 == c2 and c1 % 8 == 0 and k == 3 and s == 1:
+        return "depthwise"
+    if g == 1 and k == 3 and s == 2 and c1 in (3, 4) and c2 % 8 == 0 and 8 <= c2 <= 64:
+        return "stem"
+    if g == 1 and k == 1 and s == 1 and c1 % 8 == 0 and 8 <= c1 <= 512 and 1 <= c2 <= 64 and c2 % 8:
+        return "head_out"
+    raise ValueError(f"train_kernel_of: no training kernel for a {k}x{k} conv, stride {s}, groups {g}, {c1} -> {c2}")
 
 
 class ConvBN:
@@ -517,3 +542,132 @@ class DetectBoxBranchStep:
         allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
         self.groups.step()
         return loss, dx
+
+
+class StemConvBN:
+    """model.0 in training mode -- Conv2d(cin, c2, 3, 2, 1, bias=False) on the uint8 NHWC tile [B,H,W,cin] (cin 3 or 4, the operand is bf16(v / 255),
+    channel order as stored) -> BatchNorm2d (batch statistics) -> SiLU -- under ConvBN's contract and parameter groups (w [c2,cin,3,3] in group 0,
+    gamma in 1, beta in 2, running statistics as buffers).  The conv kernels read the tile and the master weights directly (csrc/narrowgrad.hip:
+    no float copy of the image, no pack step); BatchNorm and SiLU are the bn_silu_* ops.  `backward` returns None: the input is the image."""
+
+    def __init__(self, groups, w, gamma=None, beta=None, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
+        if w.dim() != 4 or w.shape[1] not in (3, 4) or tuple(w.shape[2:]) != (3, 3) or w.shape[0] % 8 or not 8 <= w.shape[0] <= 64:
+            raise ValueError(f"StemConvBN: w must be [c2,3 or 4,3,3] with c2 a multiple of 8 in [8, 64], got {tuple(w.shape)}")
+        c2, c1 = w.shape[0], w.shape[1]
+        self.c1, self.c2, self.k, self.s, self.eps, self.momentum, self.act = c1, c2, 3, 2, eps, momentum, True
+        dev = w.device
+        self.groups = groups
+        self._iw = groups.add(0, w)
+        self._ig = groups.add(1, gamma if gamma is not None else torch.ones(c2, device=dev))
+        self._ib = groups.add(2, beta if beta is not None else torch.zeros(c2, device=dev))
+        self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c2, device=dev)).float().contiguous()
+        self.running_var = (running_var.clone() if running_var is not None else torch.ones(c2, device=dev)).float().contiguous()
+        self.saved = None
+
+    w = property(lambda self: self.groups.param[self._iw])
+    gamma = property(lambda self: self.groups.param[self._ig])
+    beta = property(lambda self: self.groups.param[self._ib])
+    dw = property(lambda self: self.groups.grad[self._iw])
+    dgamma = property(lambda self: self.groups.grad[self._ig])
+    dbeta = property(lambda self: self.groups.grad[self._ib])
+
+    def forward(self, x):
+        """x uint8 [B,H,W,cin] -> a bf16 [B,(H+1)//2,(W+1)//2,c2]; keeps (x, z, mean, invstd) for the backward."""
+        z = ops.stemconv_fwd_u8(x, self.w)
+        a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
+        self.saved = (x, z, mean, invstd)
+        return a
+
+    def backward(self, da):
+        """da bf16 like the forward's output -> None (no gradient flows into the image); dW, dgamma, dbeta go into the groups' gradient buffers."""
+        x, z, mean, invstd = self.saved
+        dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
+        ops.stemconv_wgrad_u8(x, dz, out=self.dw)
+        return None
+
+    def fold(self):
+        """-> (w, b): the eval-mode BN folded into the conv, fp32 (the weights of a conv on v / 255)."""
+        f = self.gamma / torch.sqrt(self.running_var + self.eps)
+        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+
+class HeadOut:
+    """A plain `nn.Conv2d(c, cout, 1)` with bias at the end of a head branch (model.23.cv3.i.2: nc class logits; model.23.cv4.i.2: the angle logit)
+    in training mode: w [cout,c,1,1] in group 0, b [cout] in group 2.  forward(x bf16 [B,H,W,c]) -> FP32 logits [B,H,W,cout] (what the losses
+    read); backward(dy fp32) -> dx bf16, with dW and db written straight into the groups' gradient views by the same pass (csrc/narrowgrad.hip)."""
+
+    def __init__(self, groups, w, b):
+        if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or b.dim() != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"HeadOut: w must be [cout,c,1,1] and b [cout], got {tuple(w.shape)}, {tuple(b.shape)}")
+        self.c2, self.c1 = w.shape[0], w.shape[1]
+        if self.c1 % 8 or not 8 <= self.c1 <= 512 or not 1 <= self.c2 <= 64:
+            raise ValueError(f"HeadOut: {self.c1} -> {self.c2}: c a multiple of 8 in [8, 512], 1 <= cout <= 64")
+        self.groups = groups
+        self._iw, self._ib = groups.add(0, w), groups.add(2, b)
+        self.saved = None
+
+    w = property(lambda self: self.groups.param[self._iw])
+    b = property(lambda self: self.groups.param[self._ib])
+    dw = property(lambda self: self.groups.grad[self._iw])
+    db = property(lambda self: self.groups.grad[self._ib])
+
+    def forward(self, x):
+        self.saved = x
+        return ops.headconv_fwd_bf16(x, self.w, self.b)
+
+    def backward(self, dy, need_dx=True):
+        dx, _, _ = ops.headconv_bwd_bf16(self.saved, dy, self.w, dw_out=self.dw, db_out=self.db, need_dx=need_dx)
+        return dx
+
+
+class DetectClassBranchStep:
+    """Ultralytics Detect.cv3[i] trained as the reference trains it (the counterpart of DetectBoxBranchStep): two `ClassBranchPair`s (DWConv 3x3 ->
+    Conv 1x1, BatchNorm unfolded) -> HeadOut(nc) -> BCE term of the OBB loss -> backward -> DDP gradient average -> optimiser step, over the
+    trainer's three parameter groups.  pairs: two (dw, pw) with dw / pw = (w, gamma, beta[, running_mean, running_var]); w3 [nc,c,1,1], b3 [nc]."""
+
+    def __init__(self, pairs, w3, b3, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3, bn_momentum=0.03):
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        self.pairs = [ClassBranchPair(self.groups, dw, pw, eps, bn_momentum) for (dw, pw) in pairs]
+        self.out = HeadOut(self.groups, w3, b3)
+        self.groups.build()
+
+    def forward_backward(self, x, targets, target_scores_sum=1.0):
+        """x bf16 [B,H,W,cin]; targets fp32 [B,H,W,nc] (or [B*H*W, nc]) -> (loss fp32[1], dx bf16 like x); every parameter gradient is left in the
+        groups' gradient buffers."""
+        a = x
+        for p in self.pairs:
+            a = p.forward(a)
+        logits = self.out.forward(a)
+        loss, g = ops.bce_loss(logits, targets.reshape(logits.shape), target_scores_sum)
+        d = self.out.backward(g)
+        for p in reversed(self.pairs):
+            d = p.backward(d)
+        return loss, d
+
+    def step(self, x, targets, target_scores_sum=1.0, group=None):
+        loss, dx = self.forward_backward(x, targets, target_scores_sum)
+        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
+        self.groups.step()
+        return loss, dx
+
+
+class DetectAngleBranch:
+    """Ultralytics OBB.cv4[i]: ConvBN 3x3 -> ConvBN 3x3 -> HeadOut(1), as forward(x bf16) -> fp32 angle logits [B,H,W,1] and backward(dangle fp32) ->
+    dx bf16.  There is no loss here: the angle's gradient arrives through ProbIoU on the decoded boxes.  convs: two (w, gamma, beta) triples
+    (gamma / beta None: 1 / 0), registered in `groups` before w3 [ne,c,1,1] and b3 [ne]."""
+
+    def __init__(self, groups, convs, w3, b3, eps=1e-3, momentum=0.03):
+        self.blocks = [ConvBN(groups, w, g, b, eps=eps, momentum=momentum) for (w, g, b) in convs]
+        self.out = HeadOut(groups, w3, b3)
+
+    def forward(self, x):
+        a = x
+        for blk in self.blocks:
+            a = blk.forward(a)
+        return self.out.forward(a)
+
+    def backward(self, dangle):
+        d = self.out.backward(dangle)
+        for blk in reversed(self.blocks):
+            d = blk.backward(d)
+        return d
