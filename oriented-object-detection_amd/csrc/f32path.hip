@@ -639,6 +639,7 @@ static Conv32Tiling plan_conv32_nc(int ks, int stride, int cin, int cout, int Ho
     Conv32Tiling t;
     t.NC = NC;
     t.WC = NC == 2 ? 2 : (cout >= 64 ? 4 : (cout >= 32 ? 2 : 1));
+    if (in_u8) t.WC = 1;  // the uint8 form exists with one cout fragment per workgroup only (launch32_f): 32 couts (the s widths) are two cout blocks
     if (in_u8) t.CK = 4;
     else {
         // (1x1: 64-channel stages = half the barriers and LDS commits of 32: 18.40 -> 18.27 ms per 512 tiles, the 13 x 13 layers 4-6 %)

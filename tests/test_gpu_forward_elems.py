@@ -31,6 +31,7 @@ import torch
 
 import bounds
 import forward_ref as fr
+from forward_obs import _head_obs, _observe, _read, _stale
 from oracle.yolo11_obb import Yolo11OBB
 
 pytestmark = pytest.mark.gpu
@@ -50,73 +51,6 @@ def ops():
     import oriented_object_detection_amd  # noqa: F401
     from oriented_object_detection_amd import ops as o
     return o
-
-
-# Named tensors that are overwritten in place by the time the forward returns.  A tabled name is used neither as input nor as output: the
-# groups around it extend across it with propagated E.  (netplan.hip, Builder)
-#   model.10.cv1 (b half), model.10.m.0.attn.proj
-#       build(): `conv(nm + ".attn.proj", whole(po), H32, W32, bsl, bsl);  // x = x + attn(x), in place on the b half` and
-#                `conv(nm + ".ffn.1", whole(ff), H32, W32, bsl, bsl);      // x = x + ffn(x)`: the b half of psa.ab is written by cv1, by
-#       attn.proj and by ffn.1; only the last (ffn.1) survives.  The a half is read back as "model.10.a".
-#   <C3k>.cv1 where cv1|cv2 run as one merged launch
-#       c3k(): "cv1 and cv2 read the same tensor: one launch writes [a | b]; the last Bottleneck later overwrites the (then dead) `a`
-#       member, so the same buffer is cv3's concat input."  (<C3k>.m.1.cv2 is that same slot and is what survives.)
-STALE_ALWAYS = ("model.10.cv1", "model.10.m.0.attn.proj")
-C3K_BLOCKS = ("model.6.m.0", "model.8.m.0", "model.22.m.0")
-
-
-def _stale(plan):
-    return set(STALE_ALWAYS) | {b + ".cv1" for b in C3K_BLOCKS if any(f"{b}.cv1|{b}.cv2" in l for l in plan)}
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).double().cpu()
-
-
-def _read(ops, m, name, B, h, w):
-    """debug_activation(name) as an NCHW fp64 tensor in the oracle's channel order, or None where the plan has no such tensor"""
-    from oriented_object_detection_amd import _lib
-    try:
-        t = _nchw(ops.debug_activation(name, B, h, w))
-    except _lib.ObbHipError as e:
-        if "no activation named" not in str(e):  # any other failure must not pass for "hidden" and silently merge groups
-            raise
-        return None
-    if name.endswith(".attn.qkv"):  # device order [q heads | k heads | v heads]
-        nh = m.psa_heads
-        hd = m.psa_c // nh
-        o = torch.empty_like(t)
-        o[:, fr.qkv_device_order(nh, hd // 2, hd)] = t
-        t = o
-    return t
-
-
-def _head_obs(m, head, h, w):
-    """head [B, A, >= 77] -> the nine final convs' outputs, NCHW"""
-    obs, off = {}, 0
-    for i, s in enumerate((8, 16, 32)):
-        H, W = h // s, w // s
-        t = _nchw(head[:, off:off + H * W, :77].reshape(head.shape[0], H, W, 77))
-        off += H * W
-        for n, c in zip(fr.head_names(i), ((0, 64), (64, 64 + m.nc), (64 + m.nc, 65 + m.nc))):
-            obs[n] = t[:, c[0]:c[1]]
-    assert off == head.shape[1]
-    return obs
-
-
-def _observe(ops, m, plan, head, x, B, h, w):
-    stale = _stale(plan)
-    obs = {"tile": x}
-    for name in list(m.convs) + [f"model.10.m.{i}.attn" for i in range(m.psa_n)]:
-        t = _read(ops, m, name, B, h, w)
-        if t is None:
-            continue
-        if name == "model.10.cv1":
-            obs["model.10.a"] = t[:, :m.psa_c]
-        if name not in stale:
-            obs[name] = t
-    obs.update(_head_obs(m, head.cpu(), h, w))
-    return obs
 
 
 def _assert_fused_forms(plan, h, w):
