@@ -143,3 +143,16 @@ def sppf_case(B, H, W, c1, c2):
     x = torch.randn(B, H, W, c1, generator=g).to(torch.bfloat16)
     da = (torch.randn(B, H, W, c2, generator=g) * 0.1).to(torch.bfloat16)
     return cv1, cv2, x, da
+
+
+# ---------------------------------------------------------------------------------------------- the block tests' bounds
+BF, U = 2.0 ** -8, 2.0 ** -24
+# A figure of (nearly) zero gives no bound by itself: the bound is then the reference's own grain -- one flipped bf16 rounding of the largest element
+# for the bf16 tensors, the fp32 reference's summation error (16 roundings of 2^-24) for the fp32 gradients and statistics.
+FLOOR = {"out": BF, "dx": BF, "dskip": BF, "dW": 16 * U, "dgamma": 16 * U, "dbeta": 16 * U, "rmean": 16 * U, "rvar": 16 * U}
+# measured (MI355X), max |d| / max |ref| of every compared quantity, per SPPF case (B, H, W, c1, c2); asserted at 2.5 x its own figure
+SPPF_MEASURED = {
+    (2, 13, 13, 256, 256): {"out": 3.09e-3, "dx": 6.87e-3, "cv1.dW": 5.91e-3, "cv1.dgamma": 1.09e-2, "cv1.dbeta": 1.54e-2, "cv1.rmean": 6.89e-7,
+                            "cv1.rvar": 7.81e-8, "cv2.dW": 4.84e-3, "cv2.dgamma": 1.80e-5, "cv2.dbeta": 1.35e-5, "cv2.rmean": 3.48e-6, "cv2.rvar": 1.62e-7},
+    (2, 4, 4, 128, 128): {"out": 0.0, "dx": 4.96e-3, "cv1.dW": 4.01e-3, "cv1.dgamma": 1.01e-2, "cv1.dbeta": 1.28e-2, "cv1.rmean": 0.0, "cv1.rvar": 8.29e-8,
+                          "cv2.dW": 4.46e-3, "cv2.dgamma": 1.21e-7, "cv2.dbeta": 1.61e-7, "cv2.rmean": 0.0, "cv2.rvar": 0.0}}

@@ -274,6 +274,7 @@ def test_assembled_box_branch_step_matches_autograd(B, H, W):
     import torch.nn.functional as F
     import oriented_object_detection_amd  # noqa: F401
     import oriented_object_detection_amd.train as TR
+    import train_steps_ref as TS  # the tolerances, shared with the step tests
     g = torch.Generator().manual_seed(B * 100 + H)
     ws = [torch.randn(64, 64, 3, 3, generator=g) * 0.06, torch.randn(64, 64, 3, 3, generator=g) * 0.06, torch.randn(64, 64, 1, 1, generator=g) * 0.15]
     bs = [torch.randn(64, generator=g) * 0.1 for _ in range(3)]
@@ -299,17 +300,17 @@ def test_assembled_box_branch_step_matches_autograd(B, H, W):
     loss, dx = st.forward_backward(x.cuda(), tgt.cuda(), wgt.cuda(), tss)
     torch.cuda.synchronize()
     ref_l = float(ref_loss.detach())
-    assert abs(float(loss) - ref_l) <= 2e-3 * abs(ref_l), (float(loss), ref_l)
+    assert abs(float(loss) - ref_l) <= TS.BOXBRANCH_TOL["loss"] * abs(ref_l), (float(loss), ref_l)
     for i in range(3):
         dw, db = st.dw[i].cpu(), st.db[i].cpu()
         ew, eb = float((dw - pw[i].grad).abs().max()), float((db - pb[i].grad).abs().max())
         sw, sb = float(pw[i].grad.abs().max()), float(pb[i].grad.abs().max())
         print(f"layer {i}: dW max |d| / max {ew / sw:.2e}, db {eb / sb:.2e}")
-        assert ew <= 8e-3 * sw and eb <= 2e-3 * sb, (i, ew / sw, eb / sb)  # measured: dW <= 3.1e-3, db <= 6.5e-4 of the largest entry
+        assert ew <= TS.BOXBRANCH_TOL["dW"] * sw and eb <= TS.BOXBRANCH_TOL["db"] * sb, (i, ew / sw, eb / sb)  # measured: dW <= 3.1e-3, db <= 6.5e-4 of the largest entry
     edx = float((dx.float().cpu().permute(0, 3, 1, 2) - xr.grad).abs().max())
     sx = float(xr.grad.abs().max())
     print(f"dx max |d| / max {edx / sx:.2e}")
-    assert edx <= 1.2e-2 * sx  # measured 5.3e-3: three bf16 roundings of the gradient on the way down
+    assert edx <= TS.BOXBRANCH_TOL["dx"] * sx  # measured 5.3e-3: three bf16 roundings of the gradient on the way down
     # the optimiser step on top: SGD(nesterov, momentum 0.9), decay on the weights only, against torch.optim on the autograd gradients
     opt = torch.optim.SGD([{"params": pw, "weight_decay": 5e-4}, {"params": pb, "weight_decay": 0.0}], lr=0.01, momentum=0.9, nesterov=True)
     opt.step()

@@ -7,6 +7,7 @@ import torch
 
 import attn_ref as AR
 import dw_ref as DR
+import train_steps_ref as TS  # the fold and optimiser-step tolerances, shared with the step tests
 from bounds import Guarded, _check, _same_thrice
 
 pytestmark = pytest.mark.gpu
@@ -274,8 +275,8 @@ def test_blocks_match_torch_modules_sgd_and_fold(kind, B, H, W, C):
                                 (d.w, d.gamma, d.beta, d.running_mean, d.running_var)):
                 dst.copy_(ck(src).double().cpu())
         wf, bf = AR.fold_ref(r)
-        assert float((folded[t][0].double().cpu() - wf).abs().max()) <= 4e-7 * float(wf.abs().max()), t
-        assert float((folded[t][1].double().cpu() - bf).abs().max()) <= 4e-7 * max(1.0, float(bf.abs().max())), t
+        assert float((folded[t][0].double().cpu() - wf).abs().max()) <= TS.FOLD_TOL * float(wf.abs().max()), t
+        assert float((folded[t][1].double().cpu() - bf).abs().max()) <= TS.FOLD_TOL * max(1.0, float(bf.abs().max())), t
 
     # one SGD step against torch.optim.SGD fed the device's gradients (device order: the optimiser is element-wise)
     params, grads = [[], [], []], [[], [], []]
@@ -295,4 +296,4 @@ def test_blocks_match_torch_modules_sgd_and_fold(kind, B, H, W, C):
         for k, dvp in enumerate((dev[t].w, dev[t].gamma, dev[t].beta)):
             p = params[k][i[k]].detach()
             i[k] += 1
-            assert float((dvp.cpu() - p).abs().max()) <= 2e-6 * max(1.0, float(p.abs().max())), (t, k)
+            assert float((dvp.cpu() - p).abs().max()) <= TS.PARAM_TOL * max(1.0, float(p.abs().max())), (t, k)
