@@ -425,6 +425,24 @@ int obb_dfl_loss(obb_ctx *ctx, const float *pred_dist, const float *target_ltrb,
 int obb_bce_loss(obb_ctx *ctx, const float *logits, const float *targets, int64_t n, float target_scores_sum, float *loss, float *grad_logits,
                  obb_stream_t s);
 
+/* f1 (criterion chain): ultralytics v8OBBLoss.__call__ (restated from recall, parity unpinned) around the assigner, on the head's own outputs.
+ * Three levels (strides 8, 16, 32; maps H[i] x W[i]; anchors row-major, levels concatenated, A = sum H[i] W[i]).  box, cls, angle, H, W (and
+ * d_box, d_cls, d_angle, gains below) are HOST arrays of three; their elements are device pointers: box[i] [B][H][W][64] DFL logits, bf16
+ * (box_bf16 != 0) or float, 16-byte aligned; cls[i] float [B][H][W][nc]; angle[i] float [B][H][W][1].  1 <= nc <= 64, B A nc <= 2^24.
+ * obb_crit_decode: the assigner's inputs -- pd_scores float[B][A][nc] = sigmoid(cls), pd_bboxes float[B][A][5] = the decoded (x, y, w, h) in
+ * pixels and theta (DFL expectation, dist2rbox, theta = (sigmoid(angle) - 0.25) pi), anc_points float[A][2] in pixels, stride float[A]. */
+int obb_crit_decode(obb_ctx *ctx, const void *const *box, int32_t box_bf16, const float *const *cls, const float *const *angle, const int32_t *H,
+                    const int32_t *W, int32_t B, int32_t nc, float *pd_scores, float *pd_bboxes, float *anc_points, float *stride, obb_stream_t s);
+/* obb_crit_loss: given the assigner's target_bboxes float[B][A][5] (pixels), target_scores float[B][A][nc] and fg_mask uint8[B][A]:
+ * tss[0] = max(sum target_scores, 1) (device); items[3] (device) = (g_box L_box, g_cls L_cls, g_dfl L_dfl), gains = (g_box, g_cls, g_dfl), with
+ * L_box the ProbIoU term and L_dfl the DFL term over the foreground anchors (weight = sum_c target_scores, targets over the stride, ltrb clamped
+ * to [0, 14.99]) and L_cls the BCE term over every anchor, each over tss; and the gradient of B * sum(items) with respect to every logit, in the
+ * logits' layouts: d_box[i] bf16 (16-byte aligned), d_cls[i], d_angle[i] float.  Every element is written (background anchors: zeros in d_box and
+ * d_angle); the decode is recomputed from the logits.  No host read: stream-ordered and capturable. */
+int obb_crit_loss(obb_ctx *ctx, const void *const *box, int32_t box_bf16, const float *const *cls, const float *const *angle, const int32_t *H,
+                  const int32_t *W, int32_t B, int32_t nc, const float *target_bboxes, const float *target_scores, const uint8_t *fg_mask,
+                  const float *gains, void *const *d_box, float *const *d_cls, float *const *d_angle, float *items, float *tss, obb_stream_t s);
+
 /* f1 (optimiser step): the update behind `model.train(...)` (Train_OBB.py:796-841; ultralytics `build_optimizer`: torch.optim.SGD with
  * nesterov momentum or torch.optim.AdamW, three parameter groups).  A group = flat fp32 device buffers of n elements, 16-byte aligned.
  * obb_sgd_step: d = grad + weight_decay * param; buf = first_step ? d : momentum * buf + d; d = nesterov ? d + momentum * buf : buf;

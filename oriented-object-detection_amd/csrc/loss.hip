@@ -10,6 +10,7 @@
 // atomics).  Gradients match torch.autograd on the same formula (tests/test_gpu_loss.py); clamps pass gradient inside their range and
 // block it outside, like torch.clamp.
 #include "ctx.h"
+#include "loss_device.h"
 
 namespace obb {
 
@@ -17,51 +18,12 @@ __global__ __launch_bounds__(256) void k_probiou_loss(const float *__restrict__ 
                                                      int64_t n, float inv_tss, float *__restrict__ loss_elem, float *__restrict__ grad) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float eps = 1e-7f;
-    const float x1 = pred[i * 5], y1 = pred[i * 5 + 1], w1 = pred[i * 5 + 2], h1 = pred[i * 5 + 3], t1a = pred[i * 5 + 4];
-    const float x2 = target[i * 5], y2 = target[i * 5 + 1], w2 = target[i * 5 + 2], h2 = target[i * 5 + 3], t2a = target[i * 5 + 4];
     const float wt = weight ? weight[i] : 1.0f;
-    // covariance terms (_get_covariance_matrix)
-    const float a1 = w1 * w1 / 12.0f, b1 = h1 * h1 / 12.0f, c1 = cosf(t1a), s1 = sinf(t1a);
-    const float a2 = w2 * w2 / 12.0f, b2 = h2 * h2 / 12.0f, c2 = cosf(t2a), s2 = sinf(t2a);
-    const float A1 = a1 * c1 * c1 + b1 * s1 * s1, B1 = a1 * s1 * s1 + b1 * c1 * c1, C1 = (a1 - b1) * c1 * s1;
-    const float A2 = a2 * c2 * c2 + b2 * s2 * s2, B2 = a2 * s2 * s2 + b2 * c2 * c2, C2 = (a2 - b2) * c2 * s2;
-    const float A = A1 + A2, B = B1 + B2, C = C1 + C2;
-    const float dx = x1 - x2, dy = y1 - y2;
-    const float D = A * B - C * C, den = D + eps;
-    const float N1 = A * dy * dy + B * dx * dx, N2 = C * dx * dy;
-    const float T1 = 0.25f * N1 / den, T2 = -0.5f * N2 / den;
-    const float d1raw = A1 * B1 - C1 * C1, d2raw = A2 * B2 - C2 * C2;
-    const float d1 = fmaxf(d1raw, 0.0f), d2 = fmaxf(d2raw, 0.0f);
-    const float r = sqrtf(d1 * d2), g = 4.0f * r + eps;
-    const float u = D / g;
-    const float T3 = 0.5f * logf(u + eps);
-    const float braw = T1 + T2 + T3;
-    const float bd = fminf(fmaxf(braw, eps), 100.0f);
-    const float ex = expf(-bd);
-    const float hd = sqrtf(1.0f - ex + eps);
-    loss_elem[i] = hd * wt;  // (1 - iou) * weight with iou = 1 - hd
-    // ---- backward: dL/dbd, then the chain down to (x, y, w, h, theta) of the prediction
-    float gb = (braw >= eps && braw <= 100.0f) ? wt * inv_tss * ex / (2.0f * hd) : 0.0f;
-    const float iden = 1.0f / den, iden2 = iden * iden;
-    // d(bd) / d(A, B, C, dx, dy)
-    float gA = 0.25f * (dy * dy * iden - N1 * B * iden2) + 0.5f * N2 * B * iden2;
-    float gB = 0.25f * (dx * dx * iden - N1 * A * iden2) + 0.5f * N2 * A * iden2;
-    float gC = 0.5f * N1 * C * iden2 - 0.5f * dx * dy * iden - N2 * C * iden2;
-    const float gdx = 0.5f * B * dx * iden - 0.5f * C * dy * iden;
-    const float gdy = 0.5f * A * dy * iden - 0.5f * C * dx * iden;
-    const float k3 = 0.5f / (u + eps);
-    const float gD = k3 / g, gg = -k3 * D / (g * g);
-    gA += gD * B; gB += gD * A; gC += gD * (-2.0f * C);
-    // g = 4 sqrt(d1 d2) + eps: only det1 belongs to the prediction
-    const float gdet1 = (d1raw >= 0.0f && r > 0.0f) ? gg * 2.0f * d2 / r : 0.0f;
-    const float gA1 = gA + gdet1 * B1, gB1 = gB + gdet1 * A1, gC1 = gC + gdet1 * (-2.0f * C1);
-    const float cs = c1 * s1;
-    const float ga = gA1 * c1 * c1 + gB1 * s1 * s1 + gC1 * cs;
-    const float gbb = gA1 * s1 * s1 + gB1 * c1 * c1 - gC1 * cs;
-    const float gt = gA1 * (-2.0f * C1) + gB1 * (2.0f * C1) + gC1 * (a1 - b1) * (c1 * c1 - s1 * s1);
+    float g[5];
+    loss_elem[i] = probiou_pair(pred[i * 5], pred[i * 5 + 1], pred[i * 5 + 2], pred[i * 5 + 3], pred[i * 5 + 4], target[i * 5], target[i * 5 + 1],
+                                target[i * 5 + 2], target[i * 5 + 3], target[i * 5 + 4], wt, inv_tss, g);  // (csrc/loss_device.h)
     float *go = grad + i * 5;
-    go[0] = gb * gdx; go[1] = gb * gdy; go[2] = gb * ga * (w1 / 6.0f); go[3] = gb * gbb * (h1 / 6.0f); go[4] = gb * gt;
+    go[0] = g[0]; go[1] = g[1]; go[2] = g[2]; go[3] = g[3]; go[4] = g[4];
 }
 
 // deterministic sum: each block reduces 4096 consecutive values in a fixed tree, a second pass (same kernel, one block) reduces the partials
@@ -96,29 +58,12 @@ __global__ __launch_bounds__(256) void k_dfl_loss(const float *__restrict__ logi
         const float4 v = *reinterpret_cast<const float4 *>(logits + i * R + k);
         x[k] = v.x; x[k + 1] = v.y; x[k + 2] = v.z; x[k + 3] = v.w;
     }
-    float m = x[0];
-#pragma unroll
-    for (int k = 1; k < R; ++k) m = fmaxf(m, x[k]);
-    float e[R], se = 0.f;
-#pragma unroll
-    for (int k = 0; k < R; ++k) { e[k] = expf(x[k] - m); se += e[k]; }
-    const float lse = m + logf(se);
-    const float t = fminf(fmaxf(target[i], 0.0f), (float)(R - 1) - 0.01f);
-    const int tl = (int)t, tr = tl + 1;
-    const float wl = (float)tr - t, wr = 1.0f - wl;
-    float xl = 0.f, xr = 0.f;
-#pragma unroll
-    for (int k = 0; k < R; ++k) { xl = k == tl ? x[k] : xl; xr = k == tr ? x[k] : xr; }
+    float e[R], g[R], m, se;
+    softmax_parts<R>(x, e, m, se);
     const float wt = (weight ? weight[i >> 2] : 1.0f) * 0.25f;
-    loss_elem[i] = ((lse - xl) * wl + (lse - xr) * wr) * wt;
-    const float gs = wt * inv_tss, inv_se = 1.0f / se;
+    loss_elem[i] = dfl_side<R>(x, e, m, se, target[i], wt, wt * inv_tss, g);  // (csrc/loss_device.h)
 #pragma unroll
-    for (int k = 0; k < R; k += 4) {
-        float g[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g[j] = (e[k + j] * inv_se - (k + j == tl ? wl : 0.f) - (k + j == tr ? wr : 0.f)) * gs;
-        *reinterpret_cast<float4 *>(grad + i * R + k) = make_float4(g[0], g[1], g[2], g[3]);
-    }
+    for (int k = 0; k < R; k += 4) *reinterpret_cast<float4 *>(grad + i * R + k) = make_float4(g[k], g[k + 1], g[k + 2], g[k + 3]);
 }
 
 // ---- classification term: BCEWithLogitsLoss(reduction="none")(logits, targets).sum() / target_scores_sum (v8OBBLoss), element-wise:
@@ -127,10 +72,9 @@ __global__ __launch_bounds__(256) void k_bce_loss(const float *__restrict__ logi
                                                  float *__restrict__ loss_elem, float *__restrict__ grad) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = logits[i], t = target[i];
-    const float ea = expf(-fabsf(x));
-    loss_elem[i] = fmaxf(x, 0.0f) - x * t + log1pf(ea);
-    const float sig = x >= 0.0f ? 1.0f / (1.0f + ea) : ea / (1.0f + ea);
+    const float t = target[i];
+    float sig;
+    loss_elem[i] = bce_elem(logits[i], t, sig);  // (csrc/loss_device.h)
     grad[i] = (sig - t) * inv_tss;
 }
 

@@ -350,6 +350,31 @@ def _add_bf16(a: T, b: T, out: T) -> None:
     _call("obb_add_bf16", ctx(a.device), _p(a), _p(b), a.numel(), _p(out), _stream())
 
 
+def _crit_levels(box, cls, angle):
+    """-> the host-side level arrays of obb_crit_*: (box[3], box_bf16, cls[3], angle[3], H[3], W[3], B, nc)"""
+    vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    H = (C.c_int32 * 3)(*[t.shape[1] for t in box])
+    W = (C.c_int32 * 3)(*[t.shape[2] for t in box])
+    return vp(box), int(box[0].dtype == torch.bfloat16), vp(cls), vp(angle), H, W, box[0].shape[0], cls[0].shape[-1]
+
+
+@_op("crit_decode", ("pd_scores", "pd_bboxes", "anc_points", "stride"))
+def _crit_decode(box0: T, box1: T, box2: T, cls0: T, cls1: T, cls2: T, angle0: T, angle1: T, angle2: T, pd_scores: T, pd_bboxes: T, anc_points: T,
+                 stride: T) -> None:
+    lv = _crit_levels((box0, box1, box2), (cls0, cls1, cls2), (angle0, angle1, angle2))
+    _call("obb_crit_decode", ctx(box0.device), *lv, _p(pd_scores), _p(pd_bboxes), _p(anc_points), _p(stride), _stream())
+
+
+@_op("crit_loss", ("d_box0", "d_box1", "d_box2", "d_cls0", "d_cls1", "d_cls2", "d_angle0", "d_angle1", "d_angle2", "items", "tss"))
+def _crit_loss(box0: T, box1: T, box2: T, cls0: T, cls1: T, cls2: T, angle0: T, angle1: T, angle2: T, target_bboxes: T, target_scores: T, fg_mask: T,
+               g_box: float, g_cls: float, g_dfl: float, d_box0: T, d_box1: T, d_box2: T, d_cls0: T, d_cls1: T, d_cls2: T, d_angle0: T, d_angle1: T,
+               d_angle2: T, items: T, tss: T) -> None:
+    lv = _crit_levels((box0, box1, box2), (cls0, cls1, cls2), (angle0, angle1, angle2))
+    vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    _call("obb_crit_loss", ctx(box0.device), *lv, _p(target_bboxes), _p(target_scores), _p(fg_mask), (C.c_float * 3)(g_box, g_cls, g_dfl),
+          vp((d_box0, d_box1, d_box2)), vp((d_cls0, d_cls1, d_cls2)), vp((d_angle0, d_angle1, d_angle2)), _p(items), _p(tss), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -1259,6 +1284,72 @@ def bce_loss(logits, targets, target_scores_sum=1.0):
     grad = torch.empty_like(x)
     _O.bce_loss(x, t, float(target_scores_sum), loss, grad)
     return loss, grad
+
+
+def _crit_check(box, cls, angle, fn):
+    """the head's three levels as obb_crit_* read them -> (B, nc, A); ValueError otherwise"""
+    if not (len(box) == len(cls) == len(angle) == 3):
+        raise ValueError(f"{fn}: box, cls and angle are lists of three levels (P3, P4, P5)")
+    if box[0].dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"{fn}: box logits are bf16 or fp32, got {box[0].dtype}")
+    B, nc, A = box[0].shape[0], cls[0].shape[-1], 0
+    if not 1 <= nc <= 64:
+        raise ValueError(f"{fn}: nc = {nc}: 1..64")
+    for i, (b, c, a) in enumerate(zip(box, cls, angle)):
+        _chk(b, box[0].dtype, f"box[{i}]"); _chk(c, torch.float32, f"cls[{i}]"); _chk(a, torch.float32, f"angle[{i}]")
+        if b.dim() != 4 or b.shape[0] != B or b.shape[3] != 64 or min(b.shape[1:3]) < 1:
+            raise ValueError(f"{fn}: box[{i}] must be [B,H,W,64] with H, W >= 1, got {tuple(b.shape)}")
+        if tuple(c.shape) != (*b.shape[:3], nc) or tuple(a.shape) != (*b.shape[:3], 1):
+            raise ValueError(f"{fn}: level {i}: cls {tuple(c.shape)} / angle {tuple(a.shape)} do not match box {tuple(b.shape)} with nc = {nc}")
+        A += b.shape[1] * b.shape[2]
+    if B * A * nc > 1 << 24:
+        raise ValueError(f"{fn}: B A nc = {B * A * nc} exceeds the sum tree's 2^24 elements")
+    return B, nc, A
+
+
+def crit_decode(box, cls, angle):
+    """Training-mode decode of the head (v8OBBLoss.__call__ up to the assigner; restated from recall, parity unpinned): box / cls / angle = lists
+    of the three levels' logits ([B,H,W,64] bf16 or fp32; [B,H,W,nc] fp32; [B,H,W,1] fp32) -> (pd_scores [B,A,nc] = sigmoid(cls), pd_bboxes
+    [B,A,5] xywh in pixels + theta, anc_points [A,2] in pixels, stride [A]), fp32: the inputs of `rotated_tal_assign`.  One launch."""
+    B, nc, A = _crit_check(box, cls, angle, "crit_decode")
+    d = box[0].device
+    ps = torch.empty((B, A, nc), dtype=torch.float32, device=d)
+    pb = torch.empty((B, A, 5), dtype=torch.float32, device=d)
+    ap = torch.empty((A, 2), dtype=torch.float32, device=d)
+    st = torch.empty((A,), dtype=torch.float32, device=d)
+    _O.crit_decode(*box, *cls, *angle, ps, pb, ap, st)
+    return ps, pb, ap, st
+
+
+def crit_loss(box, cls, angle, target_bboxes, target_scores, fg_mask, gains=(7.5, 0.5, 1.5), out=None):
+    """The three terms of v8OBBLoss and the gradient of every head logit, given the assignment (restated from recall, parity unpinned):
+    target_bboxes [B,A,5] (pixels), target_scores [B,A,nc], fg_mask [B,A] as `rotated_tal_assign` returns them -> (items fp32[3] = (box, cls, dfl)
+    times their gains, tss fp32[1] = max(sum target_scores, 1), d_box list (bf16, like box), d_cls list, d_angle list (fp32)): the gradients of
+    B * sum(items), every element written.  `out` = (d_box, d_cls, d_angle) writes into the caller's buffers.  Nothing is read back to the host."""
+    B, nc, A = _crit_check(box, cls, angle, "crit_loss")
+    tb = _chk(target_bboxes, torch.float32, "target_bboxes")
+    ts = _chk(target_scores, torch.float32, "target_scores")
+    fg = fg_mask.view(torch.uint8) if fg_mask.dtype == torch.bool else fg_mask
+    fg = _chk(fg, torch.uint8, "fg_mask")
+    if tuple(tb.shape) != (B, A, 5) or tuple(ts.shape) != (B, A, nc) or tuple(fg.shape) != (B, A):
+        raise ValueError(f"crit_loss: targets {tuple(tb.shape)}, {tuple(ts.shape)}, {tuple(fg.shape)} do not match B = {B}, A = {A}, nc = {nc}")
+    if len(gains) != 3:
+        raise ValueError("crit_loss: gains = (box, cls, dfl)")
+    d = box[0].device
+    if out is None:
+        d_box = [torch.empty(b.shape, dtype=torch.bfloat16, device=d) for b in box]
+        d_cls = [torch.empty_like(c) for c in cls]
+        d_angle = [torch.empty_like(a) for a in angle]
+    else:
+        d_box, d_cls, d_angle = out
+        for i in range(3):
+            _chk(d_box[i], torch.bfloat16, f"d_box[{i}]"); _chk(d_cls[i], torch.float32, f"d_cls[{i}]"); _chk(d_angle[i], torch.float32, f"d_angle[{i}]")
+            if d_box[i].shape != box[i].shape or d_cls[i].shape != cls[i].shape or d_angle[i].shape != angle[i].shape:
+                raise ValueError(f"crit_loss: out buffers of level {i} do not match the logits' shapes")
+    items = torch.empty(3, dtype=torch.float32, device=d)
+    tss = torch.empty(1, dtype=torch.float32, device=d)
+    _O.crit_loss(*box, *cls, *angle, tb, ts, fg, float(gains[0]), float(gains[1]), float(gains[2]), *d_box, *d_cls, *d_angle, items, tss)
+    return items, tss, list(d_box), list(d_cls), list(d_angle)
 
 
 def sgd_step(param, grad, momentum_buf, lr, momentum=0.9, weight_decay=0.0, nesterov=True, first_step=False):

@@ -26,7 +26,10 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     one `DWConv 3x3 -> Conv 1x1` pair of the head's class branch built from it and ConvBN;
   * `Attention` / `PSABlock`: C2PSA's attention (csrc/attngrad.hip: the softmax core with its backward) and one PSA block of model 10 around it --
     qkv / proj / ffn as ConvBN (with `act=False` where the reference has none), pe as DWConvBN, the residual adds and the gradient sums at their
-    fan-outs as ops.add_bf16."""
+    fan-outs as ops.add_bf16;
+  * `pad_targets` / `OBBCriterion` / `DetectHead`: the criterion chain (csrc/criterion.hip) -- the host-side padding of the labels, v8OBBLoss from the
+    head's logits to loss items and logit gradients without a host read (decode -> assigner -> fused loss), and the three levels of Detect / OBB
+    (box, class and angle branches over one ParamGroups) trained under it."""
 import math
 
 import torch
@@ -671,3 +674,153 @@ class DetectAngleBranch:
         for blk in reversed(self.blocks):
             d = blk.backward(d)
         return d
+
+
+def pad_targets(rows, B, imgsz, device=None):
+    """The host-side `preprocess` of v8OBBLoss (Ultralytics 8.3.x, restated from recall: the package is not installed, so this is UNPINNED like
+    `optimizer_config`): rows [n,7] = (batch_idx, cls, x, y, w, h, theta) with x, y, w, h normalised to the image -> (gt_labels int32 [B,n_max],
+    gt_bboxes fp32 [B,n_max,5] in pixels, mask_gt bool [B,n_max]), each image's boxes first in their input order, zero rows behind them.  Boxes whose
+    width or height is under 2 px are dropped.  imgsz = (H, W) or one int; n_max is at least 1, so an empty batch still has a (masked-out) row."""
+    H, W = (imgsz, imgsz) if isinstance(imgsz, int) else imgsz
+    r = torch.as_tensor(rows, dtype=torch.float32).reshape(-1, 7).cpu()
+    px = r[:, 2:6] * torch.tensor([W, H, W, H], dtype=torch.float32)
+    keep = (px[:, 2] >= 2) & (px[:, 3] >= 2)
+    r, px = r[keep], px[keep]
+    idx = r[:, 0].long()
+    counts = torch.bincount(idx, minlength=B) if r.shape[0] else torch.zeros(B, dtype=torch.long)
+    if counts.shape[0] > B:
+        raise ValueError(f"pad_targets: batch index {int(idx.max())} with B = {B}")
+    n_max = max(int(counts.max()), 1)
+    gl = torch.zeros((B, n_max), dtype=torch.int32)
+    gb = torch.zeros((B, n_max, 5), dtype=torch.float32)
+    mk = torch.zeros((B, n_max), dtype=torch.bool)
+    for j in range(B):
+        sel = idx == j
+        n = int(sel.sum())
+        gl[j, :n] = r[sel, 1].to(torch.int32)
+        gb[j, :n, :4] = px[sel]
+        gb[j, :n, 4] = r[sel, 6]
+        mk[j, :n] = True
+    if device is not None:
+        gl, gb, mk = gl.to(device), gb.to(device), mk.to(device)
+    return gl, gb, mk
+
+
+class OBBCriterion:
+    """v8OBBLoss.__call__ on the head's own outputs (Ultralytics 8.3.x, restated from recall: UNPINNED, like `optimizer_config`; pinned by the tests against this
+    repository's fp64 decode, loss terms and anchor grid): ops.crit_decode -> ops.rotated_tal_assign
+    (topk 10, alpha 0.5, beta 6) -> ops.crit_loss.  __call__(box, cls, angle, gt_labels, gt_bboxes, mask_gt) with box / cls / angle the lists of the
+    three levels' logits and the padded ground truth of `pad_targets` (on the device) -> (items fp32[3] = (box, cls, dfl) losses times their gains,
+    (d_box, d_cls, d_angle)): the gradients of batch_size * sum(items) in the logits' layouts.  Everything stays on the device and on the current
+    stream: no host read, so a whole call can be captured in a graph.  `last` keeps the assignment and tss of the latest call."""
+
+    def __init__(self, nc, gains=(7.5, 0.5, 1.5), topk=10, alpha=0.5, beta=6.0):
+        if not 1 <= nc <= 64:
+            raise ValueError(f"OBBCriterion: nc = {nc}: 1..64")
+        self.nc, self.gains, self.topk, self.alpha, self.beta = int(nc), tuple(float(g) for g in gains), topk, alpha, beta
+        self.last = None
+
+    def __call__(self, box, cls, angle, gt_labels, gt_bboxes, mask_gt):
+        if cls[0].shape[-1] != self.nc:
+            raise ValueError(f"OBBCriterion: class logits have {cls[0].shape[-1]} channels, nc = {self.nc}")
+        pd_scores, pd_bboxes, anc_points, _ = ops.crit_decode(box, cls, angle)
+        tl, tb, ts, fg, ti = ops.rotated_tal_assign(pd_scores, pd_bboxes, anc_points, gt_labels, gt_bboxes, mask_gt, self.topk, self.alpha, self.beta)
+        items, tss, d_box, d_cls, d_angle = ops.crit_loss(box, cls, angle, tb, ts, fg, self.gains)
+        self.last = {"target_labels": tl, "target_bboxes": tb, "target_scores": ts, "fg_mask": fg, "target_gt_idx": ti, "tss": tss}
+        return items, (d_box, d_cls, d_angle)
+
+
+class _DetectBoxBranch:
+    """Detect.cv2[i] inside DetectHead: ConvBN 3x3 -> ConvBN 3x3 -> Conv2d 1x1 (+bias) -> bf16 [B,H,W,64] DFL logits; DetectBoxBranchStep's layers
+    without its loss, registered in the head's `groups` (blocks, then w3 in group 0 and b3 in group 2)."""
+
+    def __init__(self, groups, convs, w3, b3, eps, momentum):
+        self.groups = groups
+        self.blocks = [ConvBN(groups, w, g, b, eps=eps, momentum=momentum) for (w, g, b) in convs]
+        self._i3, self._ib3 = groups.add(0, w3), groups.add(2, b3)
+        self.cout3, self.saved = w3.shape[0], None
+
+    w3 = property(lambda self: self.groups.param[self._i3])
+    b3 = property(lambda self: self.groups.param[self._ib3])
+    dw3 = property(lambda self: self.groups.grad[self._i3])
+    db3 = property(lambda self: self.groups.grad[self._ib3])
+
+    def forward(self, x):
+        a = x
+        for blk in self.blocks:
+            a = blk.forward(a)
+        self.saved = a
+        return ops.conv_fwd_bf16(a, ops.conv_pack_bf16(self.w3, a.shape[1], a.shape[2]), self.b3, self.cout3, 1)
+
+    def backward(self, d3):
+        a = self.saved
+        conv_wgrad(a, d3, 1, out=self.dw3)
+        ops.bias_grad_bf16(d3, self.db3)
+        d = ops.conv_fwd_bf16(d3, ops.conv_pack_bf16(self.w3, a.shape[1], a.shape[2], dgrad_form=True), None, self.w3.shape[1], 1)
+        for blk in reversed(self.blocks):
+            d = blk.backward(d)
+        return d
+
+
+class _DetectClassBranch:
+    """Detect.cv3[i] inside DetectHead: two ClassBranchPairs -> HeadOut(nc); DetectClassBranchStep's layers without its loss."""
+
+    def __init__(self, groups, pairs, w3, b3, eps, momentum):
+        self.pairs = [ClassBranchPair(groups, dw, pw, eps, momentum) for (dw, pw) in pairs]
+        self.out = HeadOut(groups, w3, b3)
+
+    def forward(self, x):
+        a = x
+        for p in self.pairs:
+            a = p.forward(a)
+        return self.out.forward(a)
+
+    def backward(self, dy):
+        d = self.out.backward(dy)
+        for p in reversed(self.pairs):
+            d = p.backward(d)
+        return d
+
+
+class DetectHead:
+    """The three levels of Ultralytics `Detect` / `OBB` (model.23: cv2 box, cv3 class, cv4 angle branches on P3, P4, P5) in training mode over ONE
+    `ParamGroups`, trained under `OBBCriterion`.  levels: three dicts {"box": (convs, w3, b3), "cls": (pairs, w3, b3), "angle": (convs, w3, b3)} with
+    convs / pairs as DetectBoxBranchStep / DetectClassBranchStep / DetectAngleBranch take them; per level the parameters are registered in the order
+    box, cls, angle.  forward(feats) -> (box, cls, angle) lists (bf16 [B,H,W,64], fp32 [B,H,W,nc], fp32 [B,H,W,1]); backward(d_box, d_cls, d_angle) ->
+    one dx per level, the sum of the three branches' input gradients through ops.add_bf16 in the fixed order (box + class) + angle;
+    step(feats, gt_labels, gt_bboxes, mask_gt) = forward, criterion, backward, DDP gradient average, optimiser step -> (items, dx list)."""
+
+    def __init__(self, levels, nc, gains=(7.5, 0.5, 1.5), optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3,
+                 bn_momentum=0.03):
+        if len(levels) != 3:
+            raise ValueError("DetectHead: three levels (P3, P4, P5)")
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        self.box, self.cls, self.angle = [], [], []
+        for lv in levels:
+            self.box.append(_DetectBoxBranch(self.groups, *lv["box"], eps, bn_momentum))
+            self.cls.append(_DetectClassBranch(self.groups, *lv["cls"], eps, bn_momentum))
+            self.angle.append(DetectAngleBranch(self.groups, *lv["angle"], eps=eps, momentum=bn_momentum))
+            if self.box[-1].cout3 != 64 or self.cls[-1].out.c2 != nc or self.angle[-1].out.c2 != 1:
+                raise ValueError(f"DetectHead: a level's branches end in 64, nc = {nc} and 1 channels, got {self.box[-1].cout3}, "
+                                 f"{self.cls[-1].out.c2}, {self.angle[-1].out.c2}")
+        self.groups.build()
+        self.criterion = OBBCriterion(nc, gains)
+
+    def forward(self, feats):
+        return ([b.forward(x) for b, x in zip(self.box, feats)], [c.forward(x) for c, x in zip(self.cls, feats)],
+                [a.forward(x) for a, x in zip(self.angle, feats)])
+
+    def backward(self, d_box, d_cls, d_angle):
+        return [ops.add_bf16(ops.add_bf16(self.box[i].backward(d_box[i]), self.cls[i].backward(d_cls[i])), self.angle[i].backward(d_angle[i]))
+                for i in range(3)]
+
+    def forward_backward(self, feats, gt_labels, gt_bboxes, mask_gt):
+        box, cls, angle = self.forward(feats)
+        items, (d_box, d_cls, d_angle) = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
+        return items, self.backward(d_box, d_cls, d_angle)
+
+    def step(self, feats, gt_labels, gt_bboxes, mask_gt, group=None):
+        items, dx = self.forward_backward(feats, gt_labels, gt_bboxes, mask_gt)
+        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
+        self.groups.step()
+        return items, dx
