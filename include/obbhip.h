@@ -344,6 +344,17 @@ int obb_attn_fwd_bf16(obb_ctx *ctx, const uint16_t *qkv, int32_t B, int32_t N, i
 int obb_attn_bwd_bf16(obb_ctx *ctx, const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *dout, const uint16_t *dv_add,
                       int32_t B, int32_t N, int32_t nh, uint16_t *dqkv, obb_stream_t s);
 int obb_add_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int64_t n, uint16_t *out, obb_stream_t s);
+/* Channel-window routing of the composite blocks in training mode (`model.train(...)`, Train_OBB.py:796-841 -> `Tensor.chunk` / `split` /
+ * `torch.cat` inside Ultralytics C3k2 (models 2, 4, 6, 8, 13, 16, 19, 22) and C2PSA (model 10), forward and backward).  src [npix][Cs], add
+ * [npix][Ca], dst [npix][Cd]: bf16 NHWC tensors on the device with their leading dims flattened to npix pixels.
+ * obb_chanwin_bf16: dst[p][d0 + j] = src[p][s0 + j] for p < npix, j < n; with add (may be NULL):
+ *   dst[p][d0 + j] = bf16(fp32(src[p][s0 + j]) + fp32(add[p][a0 + j])), one rounding, obb_add_bf16's.  Every other channel of dst is left as it
+ *   is.  Without add the 16-byte chunks are copied as bits (NaN payloads and -0 survive).  No LDS, no atomics, no workspace.
+ *   Refused (nothing launched): n, Cs, Cd (Ca with add) not positive multiples of 8; s0, d0 (a0) not non-negative multiples of 8; a window
+ *   past its tensor; npix < 1; a NULL src or dst; a pointer that is not 16-byte aligned; dst's bytes [dst, dst + npix Cd) overlapping src's or
+ *   add's. */
+int obb_chanwin_bf16(obb_ctx *ctx, const uint16_t *src, int32_t Cs, int32_t s0, const uint16_t *add, int32_t Ca, int32_t a0, int64_t npix, int32_t n,
+                     uint16_t *dst, int32_t Cd, int32_t d0, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S1: model(...) -> results[0].obb  (Detect_OBB.py:26,81-83,228-231) */
 /* Weight blob ("OBBW" format, produced by the Python side from BN-folded conv weights) for a

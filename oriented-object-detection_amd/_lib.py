@@ -73,6 +73,7 @@ SIGNATURES = {
     "obb_attn_fwd_bf16": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V],
     "obb_attn_bwd_bf16": [_V, _V, _V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_add_bf16": [_V, _V, _V, C.c_int64, _V, _V],
+    "obb_chanwin_bf16": [_V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _V, C.c_int32, C.c_int32, _V],
     "obb_gather_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, _V, _V],
     "obb_letterbox": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V,
                       C.c_int32, C.c_int32, _V],

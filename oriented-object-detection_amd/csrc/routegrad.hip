@@ -18,6 +18,10 @@
 //                   db = the b slice; accum: the existing bf16 value is the first term of the fp32 sum.  One rounding per result.
 //   add             out = bf16(fp32(a) + fp32(b)) over n elements, n % 8 == 0; out may alias a (a chunk is read before it is written, by the
 //                   same lane): the residual adds of a PSA block and the gradient sum at their fan-outs.
+//   chanwin         dst[p, d0:d0+n] = src[p, s0:s0+n] (+ add[p, a0:a0+n]) over npix pixels: a channel window of one NHWC tensor into a channel
+//                   window of another -- `Tensor.chunk` / `split` / `torch.cat` inside C3k2 and C2PSA, and the sum of a concat member's gradient
+//                   with the gradient that arrives from the chain.  Without add the chunk is copied as bits (never unpacked); with add one fp32
+//                   add and one rounding, k_add_bf16's.  The other channels of dst are not touched.  dst may not overlap src or add.
 #include <algorithm>
 
 #include "ctx.h"
@@ -244,6 +248,25 @@ __global__ __launch_bounds__(256) void k_add_bf16(const unsigned short *a, const
     }
 }
 
+// one 16-byte chunk of the window per thread and step: chunk c of pixel p is src chunk p * Cs8 + s8 + c
+__global__ __launch_bounds__(256) void k_chanwin(const unsigned short *__restrict__ src, int Cs8, int s8, const unsigned short *__restrict__ add, int Ca8, int a8,
+                                                 int64_t nchunk, int n8, unsigned short *__restrict__ dst, int Cd8, int d8) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * 256) {
+        const int64_t pix = i / n8;
+        const int c = (int)(i - pix * n8);
+        uint4 v = reinterpret_cast<const uint4 *>(src)[pix * Cs8 + s8 + c];
+        if (add) {
+            float x[8], y[8];
+            rg_unpack8(v, x);
+            rg_unpack8(reinterpret_cast<const uint4 *>(add)[pix * Ca8 + a8 + c], y);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) x[j] += y[j];
+            v = rg_pack8(x);
+        }
+        reinterpret_cast<uint4 *>(dst)[pix * Cd8 + d8 + c] = v;
+    }
+}
+
 namespace {
 unsigned route_grid(int64_t nchunk) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nchunk, 256), 4096)); }
 
@@ -322,6 +345,35 @@ int obb_add_bf16(obb_ctx *ctx, const uint16_t *a, const uint16_t *b, int64_t n, 
     OBB_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0,
                 "obb_add_bf16: a, b and out must be 16-byte aligned");
     hipLaunchKernelGGL(k_add_bf16, dim3(route_grid(n / 8)), dim3(256), 0, (hipStream_t)s, a, b, n / 8, out);
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
+}
+
+int obb_chanwin_bf16(obb_ctx *ctx, const uint16_t *src, int32_t Cs, int32_t s0, const uint16_t *add, int32_t Ca, int32_t a0, int64_t npix, int32_t n,
+                     uint16_t *dst, int32_t Cd, int32_t d0, obb_stream_t s) {
+    const char *fn = "obb_chanwin_bf16";
+    OBB_REQUIRE(ctx, ctx && n >= 8 && n % 8 == 0, "%s: n = %d must be a positive multiple of 8", fn, (int)n);
+    OBB_REQUIRE(ctx, Cs >= 8 && Cs % 8 == 0 && Cd >= 8 && Cd % 8 == 0, "%s: Cs = %d, Cd = %d must be positive multiples of 8", fn, (int)Cs, (int)Cd);
+    OBB_REQUIRE(ctx, s0 >= 0 && s0 % 8 == 0 && d0 >= 0 && d0 % 8 == 0, "%s: s0 = %d, d0 = %d must be multiples of 8, at least 0", fn, (int)s0, (int)d0);
+    OBB_REQUIRE(ctx, (int64_t)s0 + n <= Cs, "%s: the window %d + %d runs past src's %d channels", fn, (int)s0, (int)n, (int)Cs);
+    OBB_REQUIRE(ctx, (int64_t)d0 + n <= Cd, "%s: the window %d + %d runs past dst's %d channels", fn, (int)d0, (int)n, (int)Cd);
+    OBB_REQUIRE(ctx, npix >= 1 && npix < (1ll << 40), "%s: npix = %lld must be at least 1 (and below 2^40)", fn, (long long)npix);
+    OBB_REQUIRE(ctx, src && dst, "%s: NULL buffer", fn);
+    OBB_REQUIRE(ctx, ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(add) | reinterpret_cast<uintptr_t>(dst)) & 15u) == 0,
+                "%s: src, add and dst must be 16-byte aligned", fn);
+    const uintptr_t d_lo = reinterpret_cast<uintptr_t>(dst), d_hi = d_lo + (uintptr_t)npix * Cd * 2;
+    const uintptr_t s_lo = reinterpret_cast<uintptr_t>(src), s_hi = s_lo + (uintptr_t)npix * Cs * 2;
+    OBB_REQUIRE(ctx, d_hi <= s_lo || s_hi <= d_lo, "%s: dst overlaps src", fn);
+    if (add) {
+        OBB_REQUIRE(ctx, Ca >= 8 && Ca % 8 == 0 && a0 >= 0 && a0 % 8 == 0, "%s: Ca = %d, a0 = %d must be multiples of 8, Ca at least 8, a0 at least 0", fn, (int)Ca,
+                    (int)a0);
+        OBB_REQUIRE(ctx, (int64_t)a0 + n <= Ca, "%s: the window %d + %d runs past add's %d channels", fn, (int)a0, (int)n, (int)Ca);
+        const uintptr_t a_lo = reinterpret_cast<uintptr_t>(add), a_hi = a_lo + (uintptr_t)npix * Ca * 2;
+        OBB_REQUIRE(ctx, d_hi <= a_lo || a_hi <= d_lo, "%s: dst overlaps add", fn);
+    }
+    const int64_t nchunk = npix * (n / 8);
+    hipLaunchKernelGGL(k_chanwin, dim3(route_grid(nchunk)), dim3(256), 0, (hipStream_t)s, src, (int)(Cs / 8), (int)(s0 / 8), add, (int)(add ? Ca / 8 : 0),
+                       (int)(add ? a0 / 8 : 0), nchunk, (int)(n / 8), dst, (int)(Cd / 8), (int)(d0 / 8));
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }

@@ -350,6 +350,12 @@ def _add_bf16(a: T, b: T, out: T) -> None:
     _call("obb_add_bf16", ctx(a.device), _p(a), _p(b), a.numel(), _p(out), _stream())
 
 
+@_op("chanwin", ("dst",))
+def _chanwin(src: T, s0: int, add: Optional[T], a0: int, n: int, dst: T, d0: int) -> None:
+    _call("obb_chanwin_bf16", ctx(src.device), _p(src), src.shape[-1], int(s0), _p(add), add.shape[-1] if add is not None else 0, int(a0),
+          src.numel() // src.shape[-1], int(n), _p(dst), dst.shape[-1], int(d0), _stream())
+
+
 def _crit_levels(box, cls, angle):
     """-> the host-side level arrays of obb_crit_*: (box[3], box_bf16, cls[3], angle[3], H[3], W[3], B, nc)"""
     vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
@@ -978,6 +984,29 @@ def add_bf16(a, b, out=None):
         raise ValueError("add_bf16: out must have the shape of a")
     _O.add_bf16(aa, bb, out)
     return out
+
+
+def chanwin_bf16(src, s0, n, dst=None, d0=0, add=None, a0=0):
+    """dst[..., d0:d0+n] = src[..., s0:s0+n] (+ add[..., a0:a0+n]: fp32 add, one rounding) over bf16 tensors that share their leading dims; the
+    other channels of dst stay as they are.  dst None allocates a dense [..., n] tensor (then d0 must be 0).  Without add the values are copied as
+    bits.  The chunk / split / cat of C3k2 and C2PSA and the gradient sums at their concat members; offsets and widths in multiples of 8."""
+    ss = _chk(src, torch.bfloat16, "src")
+    if ss.dim() < 2:
+        raise ValueError("chanwin_bf16: src must be [..., C]")
+    if add is not None:
+        add = _chk(add, torch.bfloat16, "add")
+        if add.shape[:-1] != ss.shape[:-1]:
+            raise ValueError(f"chanwin_bf16: add {tuple(add.shape)} and src {tuple(ss.shape)} differ in their leading dims")
+    if dst is None:
+        if d0 != 0 or int(n) < 1:
+            raise ValueError(f"chanwin_bf16: without dst the result is dense: d0 = {d0} must be 0 and n = {n} positive")
+        dst = torch.empty((*ss.shape[:-1], int(n)), dtype=torch.bfloat16, device=ss.device)
+    else:
+        dst = _chk(dst, torch.bfloat16, "dst")
+        if dst.shape[:-1] != ss.shape[:-1]:
+            raise ValueError(f"chanwin_bf16: dst {tuple(dst.shape)} and src {tuple(ss.shape)} differ in their leading dims")
+    _O.chanwin(ss, int(s0), add, int(a0), int(n), dst, int(d0))
+    return dst
 
 
 def silu_bf16(z):

@@ -27,6 +27,8 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
   * `Attention` / `PSABlock`: C2PSA's attention (csrc/attngrad.hip: the softmax core with its backward) and one PSA block of model 10 around it --
     qkv / proj / ffn as ConvBN (with `act=False` where the reference has none), pe as DWConvBN, the residual adds and the gradient sums at their
     fan-outs as ops.add_bf16;
+  * `Bottleneck` / `C3k` / `C3k2` / `C2PSA`: the composite blocks of the trunk (models 2, 4, 6, 8, 10, 13, 16, 19, 22) assembled from the blocks above;
+    `chunk` / `split` / `cat` and the gradient sums at the concat members are channel-window copies and adds (ops.chanwin_bf16, csrc/routegrad.hip);
   * `pad_targets` / `OBBCriterion` / `DetectHead`: the criterion chain (csrc/criterion.hip) -- the host-side padding of the labels, v8OBBLoss from the
     head's logits to loss items and logit gradients without a host read (decode -> assigner -> fused loss), and the three levels of Detect / OBB
     (box, class and angle branches over one ParamGroups) trained under it."""
@@ -393,8 +395,8 @@ class Attention:
     pe = depthwise Conv 3x3 (no act), proj = Conv 1x1 (no act).  qkv / proj / pe: (w, gamma, beta[, running_mean, running_var]) of the three
     blocks in CHECKPOINT channel order, registered in `groups` in that order.  The qkv block is HELD in device order (`qkv_device_order`: its
     rows of w, gamma, beta and the running statistics are permuted once, here), so its parameters, gradients and running statistics in `groups`
-    are in device order; `fold()` hands every block back in checkpoint order.  The v slice of qkv that pe reads is a torch copy (index
-    bookkeeping).  bf16 [B,H,W,dim] in and out, H W <= 192."""
+    are in device order; `fold()` hands every block back in checkpoint order.  The v slice of qkv that pe reads is a channel-window copy
+    (ops.chanwin_bf16).  bf16 [B,H,W,dim] in and out, H W <= 192."""
 
     def __init__(self, groups, qkv, proj, pe, nh, eps=1e-3, momentum=0.03):
         opt = lambda t, i: t[i] if len(t) > i else None
@@ -415,7 +417,7 @@ class Attention:
         """x bf16 [B,H,W,dim] -> bf16 [B,H,W,dim]; keeps (qkv, out, lse) for the backward."""
         qkv = self.qkv.forward(x)
         out, lse = ops.attn_fwd_bf16(qkv, self.nh)
-        v = qkv[..., self.nh * 64:].contiguous()
+        v = ops.chanwin_bf16(qkv, self.nh * 64, self.nh * 64)
         self.saved = (qkv, out, lse)
         return self.proj.forward(ops.add_bf16(out, self.pe.forward(v)))
 
@@ -504,6 +506,178 @@ class UpCat:
 
     def backward(self, dout, da=None, db=None):
         return ops.upcat_bwd_bf16(dout, self.ca, self.up, da=da, db=db)
+
+
+def _convbn(groups, t, eps, momentum):
+    """(w, gamma, beta[, running_mean, running_var]) -> ConvBN with SiLU, stride 1"""
+    opt = lambda i: t[i] if len(t) > i else None
+    return ConvBN(groups, t[0], opt(1), opt(2), 1, opt(3), opt(4), eps, momentum)
+
+
+class Bottleneck:
+    """Ultralytics `Bottleneck(c1, c2, shortcut=True, k=(3, 3), e)` with c1 == c2 (every use in YOLO11) in training mode: out = x + cv2(cv1(x)), two
+    3x3 ConvBN.  cv1 / cv2: (w, gamma, beta[, running_mean, running_var]), registered in `groups` in that order.  The residual add and the gradient
+    sum at x's fan-out are ops.add_bf16 (fp32 add, one rounding).  ConvBN's contract: bf16 NHWC in and out, `forward` / `backward` / `fold`."""
+
+    def __init__(self, groups, cv1, cv2, eps=1e-3, momentum=0.03):
+        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        if (self.cv1.k, self.cv2.k) != (3, 3) or self.cv2.c1 != self.cv1.c2 or self.cv2.c2 != self.cv1.c1:
+            raise ValueError(f"Bottleneck: cv1 and cv2 are 3x3 convs c -> c_ -> c (the shortcut is always taken), got {tuple(cv1[0].shape)}, "
+                             f"{tuple(cv2[0].shape)}")
+        self.c1 = self.c2 = self.cv1.c1
+
+    def named_blocks(self):
+        """[(checkpoint-relative name, ConvBN)] in registration order"""
+        return [("cv1", self.cv1), ("cv2", self.cv2)]
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c] -> bf16 [B,H,W,c]."""
+        return ops.add_bf16(x, self.cv2.forward(self.cv1.forward(x)))
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
+        return ops.add_bf16(dy, self.cv1.backward(self.cv2.backward(dy)))
+
+    def fold(self):
+        """-> {"cv1": (w, b), "cv2": (w, b)}: eval-mode BN folded into each conv, fp32."""
+        return {n: b.fold() for n, b in self.named_blocks()}
+
+
+class C3k:
+    """Ultralytics `C3k(c1, c2, n, e=0.5, k=3)` (the members of the deeper C3k2 blocks) in training mode: cv3(cat(m(cv1(x)), cv2(x))), cv1 / cv2 =
+    Conv 1x1 (c1 -> c_), m = n Bottlenecks c_ -> c_ -> c_ (e = 1.0), cv3 = Conv 1x1 (2 c_ -> c2).  cv1 / cv2 / cv3: parameter tuples as for
+    Bottleneck; m: a list of (cv1, cv2) pairs.  Registered in `groups` in the order cv1, cv2, cv3, m.0.cv1, m.0.cv2, m.1.cv1, ...  The concat and
+    its backward are the upcat ops with up = 1; the two gradients of x are summed by ops.add_bf16."""
+
+    def __init__(self, groups, cv1, cv2, cv3, m, eps=1e-3, momentum=0.03):
+        self.cv1, self.cv2, self.cv3 = (_convbn(groups, t, eps, momentum) for t in (cv1, cv2, cv3))
+        self.m = [Bottleneck(groups, a, b, eps, momentum) for (a, b) in m]
+        c_ = self.cv1.c2
+        if (self.cv1.k, self.cv2.k, self.cv3.k) != (1, 1, 1) or self.cv2.c1 != self.cv1.c1 or self.cv2.c2 != c_ or self.cv3.c1 != 2 * c_:
+            raise ValueError(f"C3k: cv1, cv2 are 1x1 convs c1 -> c_ and cv3 a 1x1 conv 2 c_ -> c2, got {tuple(cv1[0].shape)}, {tuple(cv2[0].shape)}, "
+                             f"{tuple(cv3[0].shape)}")
+        if not self.m or any(b.c1 != c_ for b in self.m):
+            raise ValueError(f"C3k: m is at least one Bottleneck on cv1's {c_} channels, got {[b.c1 for b in self.m]}")
+        self.c1, self.c2, self.c_ = self.cv1.c1, self.cv3.c2, c_
+
+    def named_blocks(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2), ("cv3", self.cv3)] + [(f"m.{i}.{n}", b) for i, m in enumerate(self.m) for n, b in m.named_blocks()]
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
+        a = self.cv1.forward(x)
+        for m in self.m:
+            a = m.forward(a)
+        return self.cv3.forward(ops.upcat_fwd_bf16(a, self.cv2.forward(x), 1))
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; every parameter gradient goes into the groups' gradient buffers."""
+        da, db = ops.upcat_bwd_bf16(self.cv3.backward(dy), self.c_, 1)
+        for m in reversed(self.m):
+            da = m.backward(da)
+        return ops.add_bf16(self.cv1.backward(da), self.cv2.backward(db))
+
+    def fold(self):
+        """-> {"cv1": (w, b), "cv2": ..., "cv3": ..., "m.0.cv1": ..., "m.0.cv2": ..., ...}"""
+        return {n: b.fold() for n, b in self.named_blocks()}
+
+
+class C3k2:
+    """Ultralytics `C3k2(c1, c2, n, c3k, e)` (yolo11 models 2, 4, 6, 8, 13, 16, 19, 22) in training mode, any n >= 1:
+        t = cv1(x) (2 c channels);  y0, y1 = t.chunk(2);  y_{i+2} = m_i(y_{i+1});  out = cv2(cat(y0, y1, y2, ..., y_{n+1})),
+    cv1 = Conv 1x1 (c1 -> 2 c), cv2 = Conv 1x1 ((2 + n) c -> c2), m_i = Bottleneck c -> c/2 -> c (c3k False; m: a list of (cv1, cv2) pairs) or
+    C3k c -> c (c3k True; m: a list of (cv1, cv2, cv3, [(cv1, cv2), ...])).  Registered in `groups` in the order cv1, cv2, then the members.
+    `cat` is allocated once and every member is written into its channel window (ops.chanwin_bf16: bit copies); in the backward the gradient of
+    y_i is dcat's window i plus the gradient that comes back through m_i, one window add (fp32, one rounding) per member."""
+
+    def __init__(self, groups, cv1, cv2, m, c3k=False, eps=1e-3, momentum=0.03):
+        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        self.m = [C3k(groups, *t, eps, momentum) if c3k else Bottleneck(groups, *t, eps, momentum) for t in m]
+        n, c = len(self.m), self.cv1.c2 // 2
+        if (self.cv1.k, self.cv2.k) != (1, 1) or self.cv1.c2 % 16 or n < 1 or self.cv2.c1 != (2 + n) * c:
+            raise ValueError(f"C3k2: cv1 is a 1x1 conv c1 -> 2 c (c a multiple of 8) and cv2 a 1x1 conv (2 + n) c -> c2 over n = {n} members, got "
+                             f"{tuple(cv1[0].shape)}, {tuple(cv2[0].shape)}")
+        if any(b.c1 != c or b.c2 != c for b in self.m):
+            raise ValueError(f"C3k2: every member maps c = {c} channels to c, got {[(b.c1, b.c2) for b in self.m]}")
+        self.c1, self.c2, self.c = self.cv1.c1, self.cv2.c2, c
+
+    def named_blocks(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}.{n}", b) for i, m in enumerate(self.m) for n, b in m.named_blocks()]
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
+        c, n = self.c, len(self.m)
+        t = self.cv1.forward(x)
+        cat = torch.empty((*t.shape[:-1], (2 + n) * c), dtype=torch.bfloat16, device=t.device)
+        ops.chanwin_bf16(t, 0, 2 * c, dst=cat, d0=0)
+        y = ops.chanwin_bf16(t, c, c)
+        for i, m in enumerate(self.m):
+            y = m.forward(y)
+            ops.chanwin_bf16(y, 0, c, dst=cat, d0=(2 + i) * c)
+        return self.cv2.forward(cat)
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; every parameter gradient goes into the groups' gradient buffers."""
+        c, n = self.c, len(self.m)
+        dcat = self.cv2.backward(dy)
+        g = ops.chanwin_bf16(dcat, (1 + n) * c, c)
+        for i in range(n, 0, -1):
+            g = ops.chanwin_bf16(dcat, i * c, c, add=self.m[i - 1].backward(g))
+        dt = torch.empty((*dcat.shape[:-1], 2 * c), dtype=torch.bfloat16, device=dcat.device)
+        ops.chanwin_bf16(dcat, 0, c, dst=dt, d0=0)
+        ops.chanwin_bf16(g, 0, c, dst=dt, d0=c)
+        return self.cv1.backward(dt)
+
+    def fold(self):
+        """-> {"cv1": (w, b), "cv2": ..., "m.0.cv1": ..., ...} (C3k members: "m.0.cv1", "m.0.cv3", "m.0.m.1.cv2", ...)"""
+        return {n: b.fold() for n, b in self.named_blocks()}
+
+
+class C2PSA:
+    """Ultralytics `C2PSA(c1, c1, n, e=0.5)` (yolo11 model 10) in training mode: a, b = cv1(x).split((c, c));  b = m(b);  out = cv2(cat(a, b)),
+    cv1 = Conv 1x1 (c1 -> 2 c), cv2 = Conv 1x1 (2 c -> c1), m = n PSABlocks on c = 64 nh channels.  cv1 / cv2: parameter tuples as for Bottleneck;
+    blocks: a list of (qkv, proj, pe, ffn0, ffn1) as `PSABlock` takes them.  Registered in `groups` in the order cv1, cv2, then the blocks.  The
+    split is two channel-window copies, the concat and its backward the upcat ops with up = 1; dt = cat(da, db') again by upcat."""
+
+    def __init__(self, groups, cv1, cv2, blocks, nh, eps=1e-3, momentum=0.03):
+        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        self.m = [PSABlock(groups, *t, nh, eps, momentum) for t in blocks]
+        c = int(nh) * 64
+        if (self.cv1.k, self.cv2.k) != (1, 1) or self.cv1.c2 != 2 * c or self.cv2.c1 != 2 * c or not self.m:
+            raise ValueError(f"C2PSA: nh = {nh} heads of 64 channels: cv1 is a 1x1 conv c1 -> {2 * c}, cv2 a 1x1 conv {2 * c} -> c2 around at least one "
+                             f"PSABlock, got {tuple(cv1[0].shape)}, {tuple(cv2[0].shape)}, {len(self.m)} blocks")
+        self.c1, self.c2, self.c = self.cv1.c1, self.cv2.c2, c
+
+    def named_blocks(self):
+        out = [("cv1", self.cv1), ("cv2", self.cv2)]
+        for i, m in enumerate(self.m):
+            out += [(f"m.{i}.attn.qkv", m.attn.qkv), (f"m.{i}.attn.proj", m.attn.proj), (f"m.{i}.attn.pe", m.attn.pe), (f"m.{i}.ffn.0", m.ffn0),
+                    (f"m.{i}.ffn.1", m.ffn1)]
+        return out
+
+    def forward(self, x):
+        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]; H W <= 192 (the attention core)."""
+        t = self.cv1.forward(x)
+        a, b = ops.chanwin_bf16(t, 0, self.c), ops.chanwin_bf16(t, self.c, self.c)
+        for m in self.m:
+            b = m.forward(b)
+        return self.cv2.forward(ops.upcat_fwd_bf16(a, b, 1))
+
+    def backward(self, dy):
+        """dy bf16 like the forward's output -> dx bf16 like its input; every parameter gradient goes into the groups' gradient buffers."""
+        da, db = ops.upcat_bwd_bf16(self.cv2.backward(dy), self.c, 1)
+        for m in reversed(self.m):
+            db = m.backward(db)
+        return self.cv1.backward(ops.upcat_fwd_bf16(da, db, 1))
+
+    def fold(self):
+        """-> {"cv1": (w, b), "cv2": ..., "m.0.attn.qkv": ..., "m.0.attn.proj": ..., "m.0.attn.pe": ..., "m.0.ffn.0": ..., "m.0.ffn.1": ...}, the qkv
+        block in checkpoint channel order (PSABlock.fold)."""
+        out = {"cv1": self.cv1.fold(), "cv2": self.cv2.fold()}
+        for i, m in enumerate(self.m):
+            f = m.fold()
+            out.update({f"m.{i}.attn.qkv": f["qkv"], f"m.{i}.attn.proj": f["proj"], f"m.{i}.attn.pe": f["pe"], f"m.{i}.ffn.0": f["ffn0"], f"m.{i}.ffn.1": f["ffn1"]})
+        return out
 
 
 class DetectBoxBranchStep:
