@@ -1026,11 +1026,13 @@ __global__ __launch_bounds__(256) void k_gather_tiles(const uint8_t *__restrict_
     const uint8_t *src = img + ((int64_t)(y0 + row) * W + x0) * C;
     uint8_t *dst = out + ((int64_t)t * tile + row) * rowbytes;
     int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i + 3 < rowbytes) {
+    // the 4-byte store needs every row of `out` 4-aligned: a row pitch that is no multiple of 4 (tile 5 x 3 channels) takes the byte path
+    bool words = (rowbytes & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    if (words && i + 3 < rowbytes) {
         uint32_t v = (uint32_t)src[i] | ((uint32_t)src[i + 1] << 8) | ((uint32_t)src[i + 2] << 16) | ((uint32_t)src[i + 3] << 24);
         *reinterpret_cast<uint32_t *>(dst + i) = v;
     } else {
-        for (int k = i; k < rowbytes; ++k) dst[k] = src[k];
+        for (int k = i; k < min(i + 4, rowbytes); ++k) dst[k] = src[k];
     }
 }
 

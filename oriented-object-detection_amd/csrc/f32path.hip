@@ -177,7 +177,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void k_conv_f32(const C32Params P)
         // valid pixels of this tile (edge tiles are clipped): fragments past them are not computed
         const int vh = min(P.TH, P.Hout - T.oy0), vw = min(P.TW, P.Wout - T.ox0);
         const int nfrag = ((P.NI > 1 ? T.nimg * tpi : (vh == P.TH ? tpi : vh * P.TW)) + 15) >> 4;  // whole rows: a clipped tile loses its trailing rows (1-D: TH = 1, all kept)
-        T.nfrag1 = (P.TH == 1) ? ((vw + 15) >> 4) : nfrag;
+        T.nfrag1 = (P.TH == 1 && P.NI == 1) ? ((vw + 15) >> 4) : nfrag;  // (a one-row map in NI whole-image tiles is NOT the 1-D form: all its images count)
         T.lastv = wp + WP * (MFM - 1) < T.nfrag1;  // (wave-uniform) the last fragment of this wave exists
         if constexpr (!IN_U8) {
             in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)((const float *)P.in + (int64_t)T.b * P.in_bs + P.in_co), 0, (int)P.in_span_bytes, 0x00020000);
@@ -662,12 +662,18 @@ static Conv32Tiling plan_conv32_nc(int ks, int stride, int cin, int cout, int Ho
     }
     const int PST = t.CK * 4 + 16;
     t.TW = std::min(Wout, maxpix);
+    const auto fits = [&](int th, int tw) {  // the staged input tile of th x tw outputs within the LDS and the staging plan
+        const int64_t in_px = (int64_t)((th - 1) * stride + ks) * ((tw - 1) * stride + ks);
+        return !(in_px * PST + t.WC * NC * c32_wfloats(ks, t.CK) * 4 > 78 * 1024 || in_px * (in_u8 ? 1 : t.CK / 4) > chunk_cap);
+    };
+    // (rows wider than one row's tile budget -- the uint8 input layer of a 1280-px side, stride 2: 3 x 1025 staged pixels: narrower
+    //  column tiles of whole fragments; a row that fits keeps its width, so no 416- / 128-px plan moves)
+    while (t.TW > 16 && !fits(1, t.TW)) t.TW = (t.TW - 1) / 16 * 16;
     const int tiles_x = (Wout + t.TW - 1) / t.TW;
     int best_th = 1;
     int64_t best_cost = -1;
     for (int th = 1; th <= std::min(Hout, maxpix / t.TW); ++th) {
-        const int64_t in_px = (int64_t)((th - 1) * stride + ks) * ((t.TW - 1) * stride + ks);
-        if (in_px * PST + t.WC * NC * c32_wfloats(ks, t.CK) * 4 > 78 * 1024 || in_px * (in_u8 ? 1 : t.CK / 4) > chunk_cap) break;
+        if (!fits(th, t.TW)) break;
         // time ~ tiles x (fragments of the busiest wave + the fixed cost of a stage: barriers + LDS commit, about one fragment's MFMAs)
         const int mfm = std::max(((th * t.TW + 15) / 16 + WP - 1) / WP, MFMN);
         const int64_t cost = (int64_t)((Hout + th - 1) / th) * tiles_x * (mfm * NC + 1);

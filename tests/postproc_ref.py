@@ -468,8 +468,24 @@ def mask_case(nc):
     return _case(f"mask nc {nc}", lambda at: Synth(128, 128, nc, (60, 300), 0.25, seed=50 + nc, ang_logit=50.0, attempts=at), MASK_THR)
 
 
+# Thin tiles (LetterBox(auto=True) turns a 10-px border crop into a 32 x 416 / 416 x 32 network input): 273 anchors in levels of 4 x 52,
+# 2 x 26 and 1 x 13 with kCandCap's 256 | 257 hand-over INSIDE such an image and every anchor a candidate; 32 x 32: 21 anchors (16 + 4 + 1).
+THIN_TILES = {(32, 416): (0, 1, 40, 256, 257, 273), (416, 32): (0, 1, 40, 256, 257, 273), (32, 32): (0, 1, 20, 21)}
+THIN_CONF = (0.25, 0.001)
+
+
+def thin_case(h, w, conf):
+    """-> (Synth, [Case per image]) of the thin batch (h, w) at nc 12, decided at all five thresholds; tie blocks as in the matrix
+    (two per image at 273 anchors, one at 21).  Objects are 0.12 .. 0.4 of the SHORT side: 4 .. 13 px boxes, many anchors per object."""
+    ties = 2 if h * w > 32 * 32 else 1
+    return _case(f"thin {h}x{w} conf {conf}", lambda at: Synth(h, w, 12, THIN_TILES[h, w], conf, seed=2000 + h + 3 * w, ties=ties, attempts=at), THRESHOLDS)
+
+
 def all_cases():
     """every committed case, for make_postproc_attempts.py"""
+    for (h, w) in THIN_TILES:
+        for conf in THIN_CONF:
+            thin_case(h, w, conf)
     for nc in NMS_NC:
         for conf in NMS_CONF:
             nms_matrix_case(nc, conf)

@@ -25,13 +25,10 @@ C3k of c3kimg.hip 30 .. 35 -- that is 1.1 % / 1.5 .. 1.7 % of the median magnitu
 resolution the per-layer comparison stays with the tail=False cases here (same packing routines, separate kernels) and with the
 device-versus-device tests of test_gpu_forward.py.  group_bound refuses (assertion) any group whose median bound exceeds half the median
 magnitude, so a group whose bound says nothing cannot count towards the 96."""
-import numpy as np
 import pytest
 import torch
 
-import bounds
-import forward_ref as fr
-from forward_obs import _head_obs, _observe, _read, _stale
+from forward_obs import check_every_group
 from oracle.yolo11_obb import Yolo11OBB
 
 pytestmark = pytest.mark.gpu
@@ -75,59 +72,9 @@ CASES = [(p, True, "n", 3, h, w, B) for p in ("f16", "bf16") for (h, w, B) in ((
 
 @pytest.mark.parametrize("prec,tail,scale,ch,h,w,B", CASES, ids=lambda v: str(v))
 def test_every_group_per_element(ops, prec, tail, scale, ch, h, w, B):
-    m = _model(scale, ch)
-    ops.model_load(m.to_blob(), precision=prec, tail=tail)
-    try:
-        plan = ops.debug_plan(h, w)
-        label = f"{prec} {'default' if tail else 'tail=False'} {scale} ch{ch} {h}x{w} B{B}: "
+    def plan_check(plan):
         if tail and scale == "n" and ch == 3 and prec != "f32":
             _assert_fused_forms(plan, h, w)
         if tail and prec != "f32" and scale == "n" and h % 52 == 0 and w % 52 == 0:
             assert any(l.startswith("front model.0+model.1+model.2.cv1") for l in plan), plan
-        if not tail:
-            assert not any(l.startswith(("bneck ", "c3kimg ", "dwpw ", "front ")) or "+model." in l for l in plan), plan
-        x = np.random.default_rng(1000 + h + w + B).integers(0, 256, (B, h, w, ch), dtype=np.uint8)
-        xd = torch.as_tensor(x).cuda()
-        info = ops.model_info(h, w)
-        g = bounds.Guarded((B, info["anchors"], 80), torch.float32)
-        ops.forward(xd, out=g.out)
-        torch.cuda.synchronize()
-        assert g.guards_intact(), label + "write outside the head tensor"
-        head = g.out.clone()
-        assert bool(torch.isfinite(head[..., :77]).all()), label + "head element not written or not finite"
-
-        obs = _observe(ops, m, plan, head, x, B, h, w)
-        ev = fr.Evaluator(m, prec, obs)
-        outputs = [k for k in obs if k != "tile"]
-        ratios, covered = fr.check_all(ev, outputs, label=label)
-        # coverage is asserted, not assumed
-        assert len(m.convs) == 96 and {c for c in covered if c in m.convs} == set(m.convs), set(m.convs) - covered
-        assert {"attn:model.10.m.0.attn", "up:up13", "up:up16", "pool:model.9.pool0", "pool:model.9.pool1", "pool:model.9.pool2"} <= covered, covered
-        assert all(n in ratios for i in range(3) for n in fr.head_names(i))
-        if not tail:  # every layer observable: nothing but the tabled in-place tensors is missing
-            assert set(m.convs) - set(obs) == _stale(plan), set(m.convs) - set(obs)
-        worst = max(ratios, key=ratios.get)
-        print(f"{label}{len(outputs)} groups, worst ratio {ratios[worst]:.3f} at {worst}", flush=True)
-
-        # replay: the second sighting of (batch, tiles, head) on a side stream is where the engine captures a hipGraph and launches it.
-        # (NOT verified here that the graph path was taken: the engine falls back to eager launches silently if capture or instantiation
-        #  fails and exposes no counter; test_hipgraph_capture_and_replay has the same limit.  Either way the head must be identical.)
-        g.raw.fill_(0xFF)
-        st = torch.cuda.Stream()
-        st.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(st):
-            ops.forward(xd, out=g.out)
-        st.synchronize()
-        torch.cuda.synchronize()
-        assert g.guards_intact(), label + "replay: write outside the head tensor"
-        assert torch.equal(g.out.view(torch.int32), head.view(torch.int32)), label + "replay: head not bit-identical"
-        if fr.is_head(worst):
-            again = _head_obs(m, g.out.cpu(), h, w)[worst]
-        elif worst == "model.10.a":
-            again = _read(ops, m, "model.10.cv1", B, h, w)[:, :m.psa_c]
-        else:
-            again = _read(ops, m, worst, B, h, w)
-        ref, E, _ = ev.node(worst)
-        fr.check_group(label + "replay " + worst, again, ref, E)
-    finally:
-        ops.model_load(m.to_blob())
+    check_every_group(ops, _model(scale, ch), prec, tail, scale, ch, h, w, B, plan_check)

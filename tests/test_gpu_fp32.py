@@ -297,6 +297,63 @@ def test_fp32_detect_symbols_end_to_end(ood, nets):
     _same_dets(got, exp, 2e-4, 0.1, "fp32 detect_symbols 807x895")
 
 
+def _thin_tile_rows(img, om, tile, overlap):
+    """rows the oracle's own model call gives on the thin crops (<= 10 px) of the grid: -> (from wide-and-low crops, from tall-and-narrow ones)"""
+    H, W = img.shape[:2]
+    hz = vt = 0
+    for (x, y, x2, y2) in og.tile_grid(H, W, tile, overlap):
+        if (y2 - y <= 10) != (x2 - x <= 10):
+            n = len(om.predict_rows(np.ascontiguousarray(img[y:y2, x:x2]), 0.25)[1])
+            hz, vt = hz + (n if y2 - y <= 10 else 0), vt + (n if x2 - x <= 10 else 0)
+    return hz, vt
+
+
+@pytest.mark.parametrize("key,H,W,tile,overlap,border", [(416, 642, 640, 416, 100, False), (416, 642, 640, 416, 100, True), (128, 206, 204, 128, 30, False)])
+def test_fp32_detect_symbols_end_to_end_with_thin_border_tiles(ood, nets, key, H, W, tile, overlap, border):
+    """An image whose grid ends in border crops 10 px tall, 8 px wide and the 10 x 8 corner (642 x 640 at 416 / 100, 206 x 204 at 128 / 30):
+    LetterBox(auto=True) makes them 32 x 416, 416 x 32 and 416 x 352 (32 x 128, 128 x 32, 128 x 128) network inputs.  Nothing injected;
+    comparison and allowances of test_fp32_detect_symbols_end_to_end.  With the reference's border filter (margin 20 / 10 px on every
+    side) no detection of a crop below 40 / 20 px can survive, so the thin tiles reach the result only with the filter off: that is the
+    configuration in which the oracle's own result is asserted to hold detections of a thin tile of each orientation (the per-tile merge
+    keeps at least one of a tile's rows); the default configuration must agree too.
+    The 10 x 8 corner has its contrast reduced to 114 +- 24: upscaled 41 times, full-contrast noise puts more than max_det = 300 rows of
+    saturated confidence (0.99999 +- 1e-7) into that one tile, and WHICH 300 survive the cap is then decided between bit-identical
+    confidences -- measured on MI355X with the full-contrast corner: 822 detections on both sides, all matched but one row displaced at
+    the cap (device-only conf 0.9999985, oracle-only conf 0.99977, heads within 2.1e-4, letterbox byte-identical).  The oracle's own row
+    count of every thin tile and of the corner is asserted to stay below the cap."""
+    img = np.random.default_rng(20).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    img[H - 10:, W - 8:] = (114 + (img[H - 10:, W - 8:].astype(np.int32) - 128) * 24 // 128).astype(np.uint8)
+    shapes = {(int(y2 - y), int(x2 - x)) for (x, y, x2, y2) in og.tile_grid(H, W, tile, overlap)}
+    assert {(10, tile), (tile, 8), (10, 8)} <= shapes, shapes
+    om = opl.OracleModel(nets[key], tile, "fp32")
+    model = ood.model.YOLO(nets[key], imgsz=tile, precision="f32")
+    exp = opl.detect_symbols(img, om, tile, overlap, apply_border=border)
+    got = ood.detect.detect_symbols(img, model, tile, overlap, ood.detect.Config(APPLY_BORDER_FILTER=border))
+    for (x, y, x2, y2) in og.tile_grid(H, W, tile, overlap):
+        if y2 - y <= 10 or x2 - x <= 10:
+            assert len(om.predict_rows(np.ascontiguousarray(img[y:y2, x:x2]), 0.25)[1]) < om.max_det, (x, y, x2, y2)
+    if not border:
+        hz, vt = _thin_tile_rows(img, om, tile, overlap)
+        print(f"oracle rows from thin tiles: {hz} from 10-px-tall crops, {vt} from 8-px-wide crops; {len(exp)} detections in all")
+        assert hz > 0 and vt > 0
+    assert len(exp) > 5
+    _same_dets(got, exp, 2e-4, 0.1, f"fp32 detect_symbols {H}x{W} tile {tile} border filter {border}")
+
+
+def test_fp32_four_channel_end_to_end_with_thin_border_tiles(ood):
+    """the same 642 x 640 image through a 4-channel checkpoint: the DT-edge channel is built on crops 10 px tall and 8 px wide (above
+    build_multich's documented minimum of 2 px) before the letterbox; allowances of test_fp32_four_channel_end_to_end_no_injection"""
+    net = Yolo11OBB("n", nc=12, ch=4, seed=2)
+    model = ood.model.YOLO(net, imgsz=416, precision="f32")
+    img = np.random.default_rng(20).integers(0, 256, (642, 640, 3), dtype=np.uint8)
+    om = opl.OracleModel(net, 416, "fp32")
+    exp = opl.detect_symbols(img, om, 416, 100, apply_border=False)
+    got = ood.detect.detect_symbols(img, model, 416, 100, ood.detect.Config(APPLY_BORDER_FILTER=False))
+    hz, vt = _thin_tile_rows(img, om, 416, 100)
+    assert hz > 0 and vt > 0 and len(exp) > 5
+    _same_dets(got, exp, 2e-4, 0.1, "fp32 4-channel detect_symbols 642x640, border filter off", max_subst=2)
+
+
 def test_fp32_process_image_dual_scale_end_to_end(ood, nets):
     img = np.random.default_rng(9).integers(0, 256, (500, 640, 3), dtype=np.uint8)
     m128 = ood.model.YOLO(nets[128], imgsz=128, precision="f32")

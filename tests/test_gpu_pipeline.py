@@ -232,6 +232,42 @@ def test_tile_survivors_equals_the_glued_kernels(ood, nets, conf, md, lbox):
         assert torch.equal(a.boxes, b.boxes) and torch.equal(a.cls, b.cls) and torch.equal(a.conf, b.conf) and torch.equal(a.angle, b.angle)
 
 
+@pytest.mark.parametrize("conf,border", [(0.25, False), (0.001, False), (0.25, True)])
+def test_tile_survivors_equals_the_glued_kernels_on_thin_tiles(ood, nets, conf, border):
+    """the same comparison on a letterboxed 32 x 416 batch: the 10 x 416 bottom-border crops of a 642-px-tall image (LetterBox(auto=True)
+    pads them by 11 rows, no resize), 273 anchors per tile, a zero tile among them; conf 0.001 saturates the dense tiles.  With the
+    border filter on (margin 20 px on every side of a 10-px crop) every tile must come out empty on both sides."""
+    D, ops = ood.detect, ood.ops
+    m = nets["m416"]
+    p = ops.letterbox_shape(10, 416, 416)
+    assert (p["out_h"], p["out_w"], p["gain"], p["pad_x"], p["pad_y"]) == (32, 416, 1.0, 0, 11)
+    B = 7
+    tiles = torch.as_tensor(np.random.default_rng(6).integers(0, 256, (B, 32, 416, 3), dtype=np.uint8)).cuda()
+    tiles[:, :11] = 114
+    tiles[:, 21:] = 114
+    tiles[2] = 0  # a tile without candidates at the usual thresholds
+    rects = np.array([[t * 316, 632, t * 316 + 416, 642] for t in range(9)], np.int32)
+    rects_dev = torch.as_tensor(rects).cuda()
+    tile_ids = torch.tensor([0, 1, 3, 4, 5, 7, 8], dtype=torch.int32).cuda()
+    lb = torch.tensor([[p["gain"], p["pad_x"], p["pad_y"]]] * B, dtype=torch.float32).cuda()
+    cfg = D.Config(max_det=300, APPLY_BORDER_FILTER=border)
+    outs = []
+    for fused in (False, True):
+        D.USE_TILE_SURVIVORS = fused
+        try:
+            outs.append(D.predict_tile_records(m, tiles, rects_dev, tile_ids, lb, cfg, 416, conf))
+        finally:
+            D.USE_TILE_SURVIVORS = True
+    glue, fus = outs
+    assert fus.packed is not None and glue.packed is None
+    assert _records_equal(glue, fus), (len(glue), len(fus))
+    assert (len(fus) > 0) == (not border), len(fus)
+    a, b = D.records_to_detset(fus, rects_dev, cfg, 416), D.records_to_detset(glue, rects_dev, cfg, 416)
+    assert len(a) == len(b)
+    if len(a):
+        assert torch.equal(a.boxes, b.boxes) and torch.equal(a.cls, b.cls) and torch.equal(a.conf, b.conf) and torch.equal(a.angle, b.angle)
+
+
 def test_select_kept_and_lazy_counts(ood, ref_vectors):
     """merge_detections_device returns the kept rows through obb_select_kept (ordered compaction, count on the device): identical to
     indexing with the boolean mask on the host side, for the reference-generated merge cases and a 20 000-row set"""

@@ -71,7 +71,8 @@ def _pad(head, nc, value):
 def test_decode_every_element_within_the_derived_bound(ops, nc):
     worst = 0.0
     with _model(ops, nc):
-        for h, w in ((64, 96), (128, 128), (416, 288), (832, 416)):
+        thin = ((32, 32), (32, 416), (416, 32)) if nc in (12, 17) else ()  # 21 / 273 anchors: a stride-32 level of one pixel / one row / one column
+        for h, w in ((64, 96), (128, 128), (416, 288), (832, 416)) + thin:
             head = R.decode_inputs(h, w, nc, seed=h + nc)
             assert ops.model_info(h, w)["anchors"] == head.shape[1] and head.shape[2] == R.no_of(nc)
             ref, E = R.decode_bounds(head, h, w, nc)
@@ -157,6 +158,17 @@ def test_decode_nms_rows_equal_the_reference(ops, nc, conf):
     ncand = _nms_against_reference(ops, syn, cases, R.THRESHOLDS, R.NMS_MAX_DET)
     assert ncand == list(R.NMS_TILES) and 256 in ncand and 257 in ncand and max(ncand) > 257
     assert len(R.nms_run(cases[-1], 0.7, 300)[1]) > 40
+
+
+@pytest.mark.parametrize("conf", R.THIN_CONF)
+@pytest.mark.parametrize("h,w", list(R.THIN_TILES))
+def test_decode_nms_rows_equal_the_reference_at_thin_tiles(ops, h, w, conf):
+    """32 x 416 / 416 x 32 (273 anchors in levels of one to four rows or columns; kCandCap's 256 | 257 hand-over inside such an image, and
+    every anchor a candidate) and 32 x 32 (21 anchors, a stride-32 level of one): default, full and gate form"""
+    syn, cases = R.thin_case(h, w, conf)
+    assert syn.A == (h // 8) * (w // 8) + (h // 16) * (w // 16) + (h // 32) * (w // 32) == max(R.THIN_TILES[h, w])
+    ncand = _nms_against_reference(ops, syn, cases, R.THRESHOLDS, R.NMS_MAX_DET)
+    assert ncand == list(R.THIN_TILES[h, w])
 
 
 def test_decode_nms_three_kernel_form_640(ops):

@@ -68,6 +68,28 @@ def test_matrix_case_is_decided_populated_and_agrees_with_the_fp32_oracle(nc, co
     _agree(syn, cases, R.THRESHOLDS, R.NMS_MAX_DET)
 
 
+@pytest.mark.parametrize("conf", R.THIN_CONF)
+@pytest.mark.parametrize("h,w", list(R.THIN_TILES))
+def test_thin_case_is_decided_populated_and_agrees_with_the_fp32_oracle(h, w, conf):
+    """the thin-tile cases (32 x 416, 416 x 32: 273 anchors; 32 x 32: 21): every row decided, none left out"""
+    syn, cases = R.thin_case(h, w, conf)
+    assert syn.A == max(R.THIN_TILES[h, w]) and len(cases) == len(R.THIN_TILES[h, w])
+    for b, c in enumerate(cases):
+        R.assert_decided(c, R.THRESHOLDS)
+        assert c.n == R.THIN_TILES[h, w][b]
+        for t in R.THRESHOLDS:
+            _, kept, nsupp = R.nms_run(c, t, 300)
+            rep = R.pair_report(c, t)
+            print(f"  thin {h}x{w} conf {conf} image {b}: candidates {c.n} thr {t} suppressed {nsupp} kept {len(kept)} margin {rep['margin']:.1f}")
+            assert rep["margin"] > R.MARGIN
+            if c.n >= 256:  # populated: suppression happens at every threshold (4 .. 13 px boxes: few pairs reach IoU 0.9)
+                assert nsupp >= (20 if t < 0.9 else 5)
+    # the largest image has every anchor a candidate, and both suppressed and surviving rows at iou 0.7
+    _, kept, nsupp = R.nms_run(cases[-1], 0.7, 300)
+    assert cases[-1].n == syn.A and nsupp > 0 and len(kept) > (40 if syn.A > 21 else 5)
+    _agree(syn, cases, R.THRESHOLDS, R.NMS_MAX_DET)
+
+
 @pytest.mark.parametrize("which", ["416", "640"])
 def test_large_cases_are_decided_and_agree_with_the_fp32_oracle(which):
     syn, cases, thr = R.big_case(which)
