@@ -596,6 +596,16 @@ def conv_wgrad_c8_bf16(x, dy, ks, stride=1, out=None):
     return _conv_wgrad("conv_wgrad_c8_bf16", x, dy, ks, stride, out)
 
 
+def _packed_elems(device, cout, cin, ks, H, W, stride, dgrad_form):
+    """Elements of the packed weights of a conv layer on H x W input maps: the stride-2 forward form has a layout (and a query) of its own."""
+    n = C.c_int64(0)
+    if stride == 2 and not dgrad_form:
+        _call("obb_conv_s2_packed_elems", ctx(device), cout, cin, int(H), int(W), C.byref(n))
+    else:
+        _call("obb_conv_packed_elems", ctx(device), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), C.byref(n))
+    return n.value
+
+
 def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
     """fp32 OIHW master weights (device) -> the bf16 MFMA fragment order of the conv kernel for H x W input maps, packed ON THE DEVICE (no
     host repack, no synchronisation); dgrad_form: the flipped / channel-transposed weights whose forward convolution is the input gradient.
@@ -603,29 +613,20 @@ def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
     ww = _chk(w, torch.float32, "w")
     cout, cin, ks, _ = ww.shape
     _stride_ok(ks, stride)
-    n = C.c_int64(0)
-    out_of = lambda n: torch.empty(n.value, dtype=torch.bfloat16, device=ww.device)
+    out = torch.empty(_packed_elems(ww.device, cout, cin, ks, H, W, stride, dgrad_form), dtype=torch.bfloat16, device=ww.device)
     if stride == 2 and not dgrad_form:
-        _call("obb_conv_s2_packed_elems", ctx(ww.device), cout, cin, int(H), int(W), C.byref(n))
-        out = out_of(n)
         _call("obb_conv_s2_pack_bf16", ctx(ww.device), _p(ww), cout, cin, int(H), int(W), _p(out), _stream())
-        return out
-    _call("obb_conv_packed_elems", ctx(ww.device), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), C.byref(n))
-    out = out_of(n)
-    _call("obb_conv_pack_bf16", ctx(ww.device), _p(ww), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), _p(out), _stream())
+    else:
+        _call("obb_conv_pack_bf16", ctx(ww.device), _p(ww), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), _p(out), _stream())
     return out
 
 
 def _check_packed(pk, fn, cout, cin, ks, H, W, stride=1, dgrad_form=False):
     """plan_conv picks the packed layout from the map size (13-multiple maps: single-stage WRES, CK = cin; others CK = 16): a blob packed for
     another H x W would be read in the wrong layout.  Its length tells the layouts apart."""
-    n = C.c_int64(0)
-    if stride == 2 and not dgrad_form:
-        _call("obb_conv_s2_packed_elems", ctx(pk.device), cout, cin, int(H), int(W), C.byref(n))
-    else:
-        _call("obb_conv_packed_elems", ctx(pk.device), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), C.byref(n))
-    if pk.numel() != n.value:
-        raise ValueError(f"{fn}: packed weights hold {pk.numel()} elements, {n.value} expected for {cin} -> {cout}, k {ks}, stride {stride} at {H} x {W}: "
+    n = _packed_elems(pk.device, cout, cin, ks, H, W, stride, dgrad_form)
+    if pk.numel() != n:
+        raise ValueError(f"{fn}: packed weights hold {pk.numel()} elements, {n} expected for {cin} -> {cout}, k {ks}, stride {stride} at {H} x {W}: "
                          "packed for another map size or layer?")
 
 
@@ -662,68 +663,58 @@ def conv_dgrad_s2_bf16(dy, packed_dgrad, cin, H, W):
     return dx
 
 
-def bn_silu_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, momentum=0.03):
-    """Training-mode BatchNorm2d + SiLU over the rows of z bf16 [..., C] (NHWC): -> (a bf16 like z, batch mean fp32 [C], invstd fp32 [C]);
-    running_mean / running_var (fp32 [C]) are updated in place with `momentum`, the running variance unbiased (torch's rule)."""
+def _bn_fwd_body(fn, op, z, gamma, beta, running_mean, running_var, eps, momentum, *act):
+    """The body of bn_silu_fwd_bf16 / bn_fwd_bf16 (`fn`: the public name; `op`: its registered op, the second one with `act` as last argument)."""
     zz = _chk(z, torch.bfloat16, "z")
     Cn = zz.shape[-1]
     vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var"))]
     if any(t.numel() != Cn for t in vecs):
-        raise ValueError("bn_silu_fwd_bf16: per-channel vectors must have C entries")
+        raise ValueError(f"{fn}: per-channel vectors must have C entries")
     a = torch.empty_like(zz)
     mean = torch.empty(Cn, dtype=torch.float32, device=zz.device)
     invstd = torch.empty_like(mean)
-    _O.bn_silu_fwd(zz, vecs[0], vecs[1], float(eps), float(momentum), vecs[2], vecs[3], mean, invstd, a)
+    op(zz, vecs[0], vecs[1], float(eps), float(momentum), vecs[2], vecs[3], mean, invstd, a, *act)
     return a, mean, invstd
+
+
+def bn_silu_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, momentum=0.03):
+    """Training-mode BatchNorm2d + SiLU over the rows of z bf16 [..., C] (NHWC): -> (a bf16 like z, batch mean fp32 [C], invstd fp32 [C]);
+    running_mean / running_var (fp32 [C]) are updated in place with `momentum`, the running variance unbiased (torch's rule)."""
+    return _bn_fwd_body("bn_silu_fwd_bf16", _O.bn_silu_fwd, z, gamma, beta, running_mean, running_var, eps, momentum)
 
 
 def bn_fwd_bf16(z, gamma, beta, running_mean, running_var, eps=1e-3, momentum=0.03, act=True):
     """bn_silu_fwd_bf16 with the activation as an argument: act=True is that function (bit-identical), act=False the training-mode BatchNorm2d
     alone (Conv(act=False)) -> (a bf16 like z, batch mean fp32 [C], invstd fp32 [C])."""
-    zz = _chk(z, torch.bfloat16, "z")
+    return _bn_fwd_body("bn_fwd_bf16", _O.bn_fwd, z, gamma, beta, running_mean, running_var, eps, momentum, bool(act))
+
+
+def _bn_bwd_body(fn, op, z, da, gamma, beta, mean, invstd, dgamma, dbeta, *act):
+    """The body of bn_silu_bwd_bf16 / bn_bwd_bf16, as _bn_fwd_body."""
+    zz, d = _chk(z, torch.bfloat16, "z"), _chk(da, torch.bfloat16, "da")
+    if d.shape != zz.shape:
+        raise ValueError(f"{fn}: da must have the shape of z")
     Cn = zz.shape[-1]
-    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var"))]
-    if any(t.numel() != Cn for t in vecs):
-        raise ValueError("bn_fwd_bf16: per-channel vectors must have C entries")
-    a = torch.empty_like(zz)
-    mean = torch.empty(Cn, dtype=torch.float32, device=zz.device)
-    invstd = torch.empty_like(mean)
-    _O.bn_fwd(zz, vecs[0], vecs[1], float(eps), float(momentum), vecs[2], vecs[3], mean, invstd, a, bool(act))
-    return a, mean, invstd
+    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
+    dg = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dgamma is None else _chk(dgamma, torch.float32, "dgamma")
+    db = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dbeta is None else _chk(dbeta, torch.float32, "dbeta")
+    if any(t.numel() != Cn for t in vecs + [dg, db]):
+        raise ValueError(f"{fn}: per-channel vectors must have C entries")
+    dz = torch.empty_like(zz)
+    op(zz, d, *vecs, dg, db, dz, *act)
+    return dz, dg, db
 
 
 def bn_silu_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None):
     """Backward of bn_silu_fwd_bf16 (batch statistics): z, da bf16 [..., C] -> (dz bf16 like z, dgamma fp32 [C], dbeta fp32 [C]); dgamma / dbeta
     go into the given tensors (e.g. views of an optimiser group's gradient buffer) when passed."""
-    zz, d = _chk(z, torch.bfloat16, "z"), _chk(da, torch.bfloat16, "da")
-    if d.shape != zz.shape:
-        raise ValueError("bn_silu_bwd_bf16: da must have the shape of z")
-    Cn = zz.shape[-1]
-    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
-    dg = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dgamma is None else _chk(dgamma, torch.float32, "dgamma")
-    db = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dbeta is None else _chk(dbeta, torch.float32, "dbeta")
-    if any(t.numel() != Cn for t in vecs + [dg, db]):
-        raise ValueError("bn_silu_bwd_bf16: per-channel vectors must have C entries")
-    dz = torch.empty_like(zz)
-    _O.bn_silu_bwd(zz, d, *vecs, dg, db, dz)
-    return dz, dg, db
+    return _bn_bwd_body("bn_silu_bwd_bf16", _O.bn_silu_bwd, z, da, gamma, beta, mean, invstd, dgamma, dbeta)
 
 
 def bn_bwd_bf16(z, da, gamma, beta, mean, invstd, dgamma=None, dbeta=None, act=True):
     """Backward of bn_fwd_bf16 with the same `act` -> (dz bf16 like z, dgamma fp32 [C], dbeta fp32 [C]); dgamma / dbeta go into the given tensors
     when passed."""
-    zz, d = _chk(z, torch.bfloat16, "z"), _chk(da, torch.bfloat16, "da")
-    if d.shape != zz.shape:
-        raise ValueError("bn_bwd_bf16: da must have the shape of z")
-    Cn = zz.shape[-1]
-    vecs = [_chk(t, torch.float32, nm) for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd"))]
-    dg = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dgamma is None else _chk(dgamma, torch.float32, "dgamma")
-    db = torch.empty(Cn, dtype=torch.float32, device=zz.device) if dbeta is None else _chk(dbeta, torch.float32, "dbeta")
-    if any(t.numel() != Cn for t in vecs + [dg, db]):
-        raise ValueError("bn_bwd_bf16: per-channel vectors must have C entries")
-    dz = torch.empty_like(zz)
-    _O.bn_bwd(zz, d, *vecs, dg, db, dz, bool(act))
-    return dz, dg, db
+    return _bn_bwd_body("bn_bwd_bf16", _O.bn_bwd, z, da, gamma, beta, mean, invstd, dgamma, dbeta, bool(act))
 
 
 def _dw_weights(w, Cn, fn):

@@ -16,10 +16,13 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     `wgrad_route` names the block class a layer's weight gradient runs in (csrc/convgrad.hip's k_conv_wgrad: 64 x 64 blocks of dW, or blocks at
     their live width for the other multiples of 8), so ConvBN trains at every dense conv shape of YOLO11 n / s with channels in multiples of 8;
     `train_kernel_of` names the kernel family of ANY conv of the model ("dense" / "depthwise" / "stem" / "head_out");
+  * `_BNBlock`: what the three BatchNorm blocks `ConvBN`, `DWConvBN` and `StemConvBN` are made of -- the registration of w / gamma / beta in groups
+    0 / 1 / 2, the running statistics, the parameter and gradient views, `fold()`, and `forward` / `backward` as a conv half around
+    ops.bn_fwd_bf16 / ops.bn_bwd_bf16 (`act`: with or without SiLU).  A subclass is its shape check and its two conv halves.  `_bn_block` builds
+    one from a parameter tuple (w, gamma, beta[, running_mean, running_var]): every composite below takes its blocks as such tuples;
   * `StemConvBN` / `HeadOut`: the two layer kinds outside the multiples of 8 (csrc/narrowgrad.hip) -- model.0 on the 3- or 4-channel uint8 tile under
     ConvBN's contract, and the head's plain `Conv2d` 1x1 + bias outputs (nc class logits, 1 angle logit) with fp32 logits and a fused dx + dW + db
-    backward; `DetectClassBranchStep` (Detect.cv3[i] under the BCE term, the counterpart of DetectBoxBranchStep) and `DetectAngleBranch`
-    (OBB.cv4[i], no loss of its own) are built from them;
+    backward; `BoxOut` is the box branch's 64-channel output under the same contract, on the dense kernels and with bf16 logits;
   * `SPPF` / `UpCat`: the joins between Conv blocks that are not convs -- SPPF's chained max pools, Upsample + Concat of the FPN, Concat of
     the PAN, and the gradient sum of a tensor with two consumers (csrc/routegrad.hip);
   * `DWConvBN` / `ClassBranchPair`: the depthwise 3x3 Conv block (csrc/dwgrad.hip: fused dx + dW backward; BatchNorm with or without SiLU) and
@@ -29,6 +32,11 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     fan-outs as ops.add_bf16;
   * `Bottleneck` / `C3k` / `C3k2` / `C2PSA`: the composite blocks of the trunk (models 2, 4, 6, 8, 10, 13, 16, 19, 22) assembled from the blocks above;
     `chunk` / `split` / `cat` and the gradient sums at the concat members are channel-window copies and adds (ops.chanwin_bf16, csrc/routegrad.hip);
+  * `_Chain`: layers in a row, forward in order and backward reversed -- `ClassBranchPair` and the head's three branches `_DetectBoxBranch`
+    (Detect.cv2[i]: two ConvBN, BoxOut), `_DetectClassBranch` (Detect.cv3[i]: two ClassBranchPairs, HeadOut) and `DetectAngleBranch` (OBB.cv4[i]: two
+    ConvBN, HeadOut; no loss of its own);
+  * `DetectBoxBranchStep` / `DetectClassBranchStep`: thin wrappers -- a box / class branch on parameter groups of its own under the DFL / BCE term
+    (`_BranchStep`), with the one `step()` (`_Step`: forward_backward, DDP gradient average, optimiser step) that `DetectHead` uses too;
   * `pad_targets` / `OBBCriterion` / `DetectHead`: the criterion chain (csrc/criterion.hip) -- the host-side padding of the labels, v8OBBLoss from the
     head's logits to loss items and logit gradients without a host read (decode -> assigner -> fused loss), and the three levels of Detect / OBB
     (box, class and angle branches over one ParamGroups) trained under it."""
@@ -248,18 +256,14 @@ def train_kernel_of(k, s, g, c1, c2):
     raise ValueError(f"train_kernel_of: no training kernel for a {k}x{k} conv, stride {s}, groups {g}, {c1} -> {c2}")
 
 
-class ConvBN:
-    """ONE Ultralytics `Conv(c1, c2, k, s)` block in training mode -- Conv2d(bias=False) -> BatchNorm2d (batch statistics, running statistics
-    updated) -> SiLU (act=False: no SiLU, Ultralytics' `Conv(..., act=False)`) -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
-    k = 1 or 3; s = 2 with k = 3 only (the downsampling convs).  Ultralytics' initialize_weights sets eps = 1e-3, momentum = 0.03 (recalled:
-    the package is not installed here, so these defaults are unpinned like optimizer_config; both are arguments).  Every arithmetic step on
-    the device is a libobbhip kernel; running statistics are buffers of the block, not parameters."""
+class _BNBlock:
+    """What ConvBN, DWConvBN and StemConvBN share: a conv without bias -> BatchNorm2d (batch statistics, running statistics updated) [-> SiLU] over
+    fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2; running statistics are buffers of the block, not
+    parameters).  `forward` is the subclass's `_conv_fwd`, then ops.bn_fwd_bf16; `backward` is ops.bn_bwd_bf16, then the subclass's `_conv_bwd`,
+    which writes dW and returns dx.  A subclass checks its weight's shape, names (c1, c2, k, s, act) and supplies the two conv halves."""
 
-    def __init__(self, groups, w, gamma=None, beta=None, s=1, running_mean=None, running_var=None, eps=1e-3, momentum=0.03, act=True):
-        c2, c1, k, k2 = w.shape
-        if k != k2 or k not in (1, 3) or s not in (1, 2) or (s == 2 and k != 3):
-            raise ValueError(f"ConvBN: k = {k}, s = {s}: k 1 or 3 at stride 1, k 3 at stride 2")
-        self.c1, self.c2, self.k, self.s, self.eps, self.momentum, self.act = c1, c2, k, s, eps, momentum, bool(act)
+    def __init__(self, groups, w, gamma, beta, c1, c2, k, s, act, running_mean, running_var, eps, momentum):
+        self.c1, self.c2, self.k, self.s, self.act, self.eps, self.momentum = c1, c2, k, s, bool(act), eps, momentum
         dev = w.device
         self.groups = groups
         self._iw = groups.add(0, w)
@@ -277,29 +281,18 @@ class ConvBN:
     dbeta = property(lambda self: self.groups.grad[self._ib])
 
     def forward(self, x):
-        """x bf16 [B,H,W,c1] -> a bf16 [B,Ho,Wo,c2]; keeps (x, z, mean, invstd) for the backward."""
-        H, W = x.shape[1], x.shape[2]
-        z = ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, H, W, stride=self.s), None, self.c2, self.k, stride=self.s)
-        if self.act:
-            a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
-        else:  # Conv(act=False): BatchNorm alone
-            a, mean, invstd = ops.bn_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum, act=False)
+        """x [B,H,W,c1] -> a bf16 [B,Ho,Wo,c2]; keeps (x, z, mean, invstd) for the backward."""
+        z = self._conv_fwd(x)
+        a, mean, invstd = ops.bn_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum, act=self.act)
         self.saved = (x, z, mean, invstd)
         return a
 
-    def backward(self, da):
-        """da bf16 like the forward's output -> dx bf16 like its input; dW, dgamma, dbeta are written into the groups' gradient buffers."""
+    def backward(self, da, **conv_args):
+        """da bf16 like the forward's output -> dx bf16 like its input (or None: `_conv_bwd`); dW, dgamma, dbeta are written into the groups'
+        gradient buffers."""
         x, z, mean, invstd = self.saved
-        H, W = x.shape[1], x.shape[2]
-        if self.act:
-            dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
-        else:
-            dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=False)
-        conv_wgrad(x, dz, self.k, self.s, out=self.dw)
-        bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
-        if self.s == 2:
-            return ops.conv_dgrad_s2_bf16(dz, bw, self.c1, H, W)
-        return ops.conv_fwd_bf16(dz, bw, None, self.c1, self.k)
+        dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=self.act)
+        return self._conv_bwd(x, dz, **conv_args)
 
     def fold(self):
         """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32."""
@@ -307,75 +300,84 @@ class ConvBN:
         return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
 
 
-class DWConvBN:
+class ConvBN(_BNBlock):
+    """ONE Ultralytics `Conv(c1, c2, k, s)` block in training mode -- Conv2d(bias=False) -> BatchNorm2d (batch statistics, running statistics
+    updated) -> SiLU (act=False: no SiLU, Ultralytics' `Conv(..., act=False)`) -- on bf16 NHWC activations over fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2).
+    k = 1 or 3; s = 2 with k = 3 only (the downsampling convs).  Ultralytics' initialize_weights sets eps = 1e-3, momentum = 0.03 (recalled:
+    the package is not installed here, so these defaults are unpinned like optimizer_config; both are arguments).  Every arithmetic step on
+    the device is a libobbhip kernel; running statistics are buffers of the block, not parameters."""
+
+    def __init__(self, groups, w, gamma=None, beta=None, s=1, running_mean=None, running_var=None, eps=1e-3, momentum=0.03, act=True):
+        c2, c1, k, k2 = w.shape
+        if k != k2 or k not in (1, 3) or s not in (1, 2) or (s == 2 and k != 3):
+            raise ValueError(f"ConvBN: k = {k}, s = {s}: k 1 or 3 at stride 1, k 3 at stride 2")
+        super().__init__(groups, w, gamma, beta, c1, c2, k, s, act, running_mean, running_var, eps, momentum)
+
+    def _conv_fwd(self, x):
+        return ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2], stride=self.s), None, self.c2, self.k, stride=self.s)
+
+    def _conv_bwd(self, x, dz):
+        H, W = x.shape[1], x.shape[2]
+        conv_wgrad(x, dz, self.k, self.s, out=self.dw)
+        bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
+        if self.s == 2:
+            return ops.conv_dgrad_s2_bf16(dz, bw, self.c1, H, W)
+        return ops.conv_fwd_bf16(dz, bw, None, self.c1, self.k)
+
+
+class DWConvBN(_BNBlock):
     """ONE depthwise Ultralytics block in training mode -- `DWConv(c, c, 3)` = Conv2d(c, c, 3, 1, 1, groups=c, bias=False) -> BatchNorm2d -> SiLU
     (act=True: the head's class branch, model.23.cv3.i.{0,1}.0) or without the SiLU (act=False: `Conv(c, c, 3, g=c, act=False)`, C2PSA's
     attn.pe) -- under ConvBN's contract: bf16 NHWC activations, fp32 master parameters in `groups` (w [C,1,3,3] in group 0, gamma in 1, beta in
     2), `forward` / `backward` / `fold`.  The kernels read the master weights directly (rounded to bf16 as they are loaded: no pack step); the
-    backward takes dx and dW from one pass over x and dz, dW written straight into the group's gradient view."""
+    backward takes dx and dW from one pass over x and dz, dW written straight into the group's gradient view (`backward(da, need_dx=False)`:
+    dW alone, None returned)."""
 
     def __init__(self, groups, w, gamma=None, beta=None, act=True, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
         if w.dim() != 4 or tuple(w.shape[1:]) != (1, 3, 3):
             raise ValueError(f"DWConvBN: w must be the depthwise 3x3 weights [C,1,3,3], got {tuple(w.shape)}")
-        c = w.shape[0]
-        self.c1 = self.c2 = c
-        self.k, self.s, self.act, self.eps, self.momentum = 3, 1, bool(act), eps, momentum
-        dev = w.device
-        self.groups = groups
-        self._iw = groups.add(0, w)
-        self._ig = groups.add(1, gamma if gamma is not None else torch.ones(c, device=dev))
-        self._ib = groups.add(2, beta if beta is not None else torch.zeros(c, device=dev))
-        self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c, device=dev)).float().contiguous()
-        self.running_var = (running_var.clone() if running_var is not None else torch.ones(c, device=dev)).float().contiguous()
-        self.saved = None
+        super().__init__(groups, w, gamma, beta, w.shape[0], w.shape[0], 3, 1, act, running_mean, running_var, eps, momentum)
 
-    w = property(lambda self: self.groups.param[self._iw])
-    gamma = property(lambda self: self.groups.param[self._ig])
-    beta = property(lambda self: self.groups.param[self._ib])
-    dw = property(lambda self: self.groups.grad[self._iw])
-    dgamma = property(lambda self: self.groups.grad[self._ig])
-    dbeta = property(lambda self: self.groups.grad[self._ib])
+    def _conv_fwd(self, x):
+        return ops.dwconv3_fwd_bf16(x, self.w)
 
-    def forward(self, x):
-        """x bf16 [B,H,W,C] -> a bf16 [B,H,W,C]; keeps (x, z, mean, invstd) for the backward."""
-        z = ops.dwconv3_fwd_bf16(x, self.w)
-        a, mean, invstd = ops.bn_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum, act=self.act)
-        self.saved = (x, z, mean, invstd)
-        return a
-
-    def backward(self, da, need_dx=True):
-        """da bf16 like the forward's output -> dx bf16 like its input (None when need_dx is False); dW, dgamma, dbeta are written into the
-        groups' gradient buffers."""
-        x, z, mean, invstd = self.saved
-        dz, _, _ = ops.bn_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta, act=self.act)
+    def _conv_bwd(self, x, dz, need_dx=True):
         dx, _ = ops.dwconv3_bwd_bf16(x, dz, self.w, dw_out=self.dw, need_dx=need_dx)
         return dx
 
-    def fold(self):
-        """-> (w [C,1,3,3], b [C]): the eval-mode BN folded into the depthwise conv, fp32."""
-        f = self.gamma / torch.sqrt(self.running_var + self.eps)
-        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+
+def _bn_block(cls, groups, t, eps, momentum, **kw):
+    """t = (w, gamma, beta[, running_mean, running_var]), gamma / beta None: 1 / 0 -> cls(groups, ...), cls a _BNBlock; kw: its `s` or `act`."""
+    w, gamma, beta, running_mean, running_var = (tuple(t) + (None,) * 4)[:5]
+    return cls(groups, w, gamma, beta, running_mean=running_mean, running_var=running_var, eps=eps, momentum=momentum, **kw)
 
 
-class ClassBranchPair:
-    """One `Sequential(DWConv(c1, c1, 3), Conv(c1, c2, 1))` of the head's class branch (ultralytics Detect.cv3[i][0] and [1]; the branch is two
-    such pairs and the nc-channel logit Conv2d) in training mode: DWConvBN -> ConvBN(1x1), both with SiLU.  dw / pw: (w, gamma, beta[,
-    running_mean, running_var]) of the two blocks, registered in `groups` in that order.  `backward` chains the two blocks' backwards."""
-
-    def __init__(self, groups, dw, pw, eps=1e-3, momentum=0.03):
-        opt = lambda t, i: t[i] if len(t) > i else None
-        self.dw = DWConvBN(groups, dw[0], opt(dw, 1), opt(dw, 2), True, opt(dw, 3), opt(dw, 4), eps, momentum)
-        self.pw = ConvBN(groups, pw[0], opt(pw, 1), opt(pw, 2), 1, opt(pw, 3), opt(pw, 4), eps, momentum)
-        if self.pw.k != 1 or self.pw.c1 != self.dw.c2:
-            raise ValueError(f"ClassBranchPair: pw is a 1x1 conv reading dw's {self.dw.c2} channels, got k = {self.pw.k}, c1 = {self.pw.c1}")
+class _Chain:
+    """Layers in a row, `self.chain`: forward through them in order, backward through them reversed."""
 
     def forward(self, x):
-        """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
-        return self.pw.forward(self.dw.forward(x))
+        for m in self.chain:
+            x = m.forward(x)
+        return x
 
-    def backward(self, da):
-        """da bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
-        return self.dw.backward(self.pw.backward(da))
+    def backward(self, d):
+        for m in reversed(self.chain):
+            d = m.backward(d)
+        return d
+
+
+class ClassBranchPair(_Chain):
+    """One `Sequential(DWConv(c1, c1, 3), Conv(c1, c2, 1))` of the head's class branch (ultralytics Detect.cv3[i][0] and [1]; the branch is two
+    such pairs and the nc-channel logit Conv2d) in training mode: DWConvBN -> ConvBN(1x1), both with SiLU.  dw / pw: (w, gamma, beta[,
+    running_mean, running_var]) of the two blocks, registered in `groups` in that order.  forward(x bf16 [B,H,W,c1]) -> bf16 [B,H,W,c2];
+    backward(da) -> dx, the six parameter gradients written into the groups' gradient buffers."""
+
+    def __init__(self, groups, dw, pw, eps=1e-3, momentum=0.03):
+        self.dw = _bn_block(DWConvBN, groups, dw, eps, momentum)
+        self.pw = _bn_block(ConvBN, groups, pw, eps, momentum)
+        if self.pw.k != 1 or self.pw.c1 != self.dw.c2:
+            raise ValueError(f"ClassBranchPair: pw is a 1x1 conv reading dw's {self.dw.c2} channels, got k = {self.pw.k}, c1 = {self.pw.c1}")
+        self.chain = [self.dw, self.pw]
 
 
 def qkv_device_order(nh, kd=32, hd=64):
@@ -399,7 +401,6 @@ class Attention:
     (ops.chanwin_bf16).  bf16 [B,H,W,dim] in and out, H W <= 192."""
 
     def __init__(self, groups, qkv, proj, pe, nh, eps=1e-3, momentum=0.03):
-        opt = lambda t, i: t[i] if len(t) > i else None
         self.nh = int(nh)
         dim = self.nh * 64
         if tuple(qkv[0].shape) != (2 * dim, dim, 1, 1) or tuple(proj[0].shape) != (dim, dim, 1, 1) or tuple(pe[0].shape) != (dim, 1, 3, 3):
@@ -407,10 +408,9 @@ class Attention:
                              f"{tuple(qkv[0].shape)}, {tuple(proj[0].shape)}, {tuple(pe[0].shape)}")
         self.perm = qkv_device_order(self.nh).to(qkv[0].device)
         self.inv = torch.argsort(self.perm)
-        pq = [None if t is None else t[self.perm].contiguous() for t in (opt(qkv, i) for i in range(5))]
-        self.qkv = ConvBN(groups, pq[0], pq[1], pq[2], 1, pq[3], pq[4], eps, momentum, act=False)
-        self.proj = ConvBN(groups, proj[0], opt(proj, 1), opt(proj, 2), 1, opt(proj, 3), opt(proj, 4), eps, momentum, act=False)
-        self.pe = DWConvBN(groups, pe[0], opt(pe, 1), opt(pe, 2), False, opt(pe, 3), opt(pe, 4), eps, momentum)
+        self.qkv = _bn_block(ConvBN, groups, [None if t is None else t[self.perm].contiguous() for t in qkv], eps, momentum, act=False)
+        self.proj = _bn_block(ConvBN, groups, proj, eps, momentum, act=False)
+        self.pe = _bn_block(DWConvBN, groups, pe, eps, momentum, act=False)
         self.saved = None
 
     def forward(self, x):
@@ -442,13 +442,16 @@ class PSABlock:
     proj, pe, ffn0, ffn1.  The two residual adds and the two gradient sums at their fan-outs are ops.add_bf16 (fp32 add, one rounding)."""
 
     def __init__(self, groups, qkv, proj, pe, ffn0, ffn1, nh, eps=1e-3, momentum=0.03):
-        opt = lambda t, i: t[i] if len(t) > i else None
         self.attn = Attention(groups, qkv, proj, pe, nh, eps, momentum)
-        self.ffn0 = ConvBN(groups, ffn0[0], opt(ffn0, 1), opt(ffn0, 2), 1, opt(ffn0, 3), opt(ffn0, 4), eps, momentum)
-        self.ffn1 = ConvBN(groups, ffn1[0], opt(ffn1, 1), opt(ffn1, 2), 1, opt(ffn1, 3), opt(ffn1, 4), eps, momentum, act=False)
+        self.ffn0 = _bn_block(ConvBN, groups, ffn0, eps, momentum)
+        self.ffn1 = _bn_block(ConvBN, groups, ffn1, eps, momentum, act=False)
         c = self.attn.nh * 64
         if (self.ffn0.k, self.ffn0.c1, self.ffn1.k, self.ffn1.c1, self.ffn1.c2) != (1, c, 1, self.ffn0.c2, c):
             raise ValueError(f"PSABlock: ffn0 and ffn1 are 1x1 convs {c} -> m -> {c}, got {tuple(ffn0[0].shape)}, {tuple(ffn1[0].shape)}")
+
+    qkv = property(lambda self: self.attn.qkv)    # the five blocks under the keys of fold()
+    proj = property(lambda self: self.attn.proj)
+    pe = property(lambda self: self.attn.pe)
 
     def forward(self, x):
         """x bf16 [B,H,W,c] -> bf16 [B,H,W,c]."""
@@ -472,9 +475,7 @@ class SPPF:
     is `cat` (cv2's input, kept for its wgrad anyway): the argmax is recomputed from it (csrc/routegrad.hip).  Maps up to 32 x 32."""
 
     def __init__(self, groups, cv1, cv2, eps=1e-3, momentum=0.03):
-        mk = lambda t: ConvBN(groups, t[0], t[1] if len(t) > 1 else None, t[2] if len(t) > 2 else None, 1, t[3] if len(t) > 3 else None,
-                              t[4] if len(t) > 4 else None, eps, momentum)
-        self.cv1, self.cv2 = mk(cv1), mk(cv2)
+        self.cv1, self.cv2 = _bn_block(ConvBN, groups, cv1, eps, momentum), _bn_block(ConvBN, groups, cv2, eps, momentum)
         if self.cv1.k != 1 or self.cv2.k != 1 or self.cv2.c1 != 4 * self.cv1.c2:
             raise ValueError(f"SPPF: cv1 and cv2 are 1x1 convs with cv2 reading 4 x cv1's {self.cv1.c2} channels, got k = {self.cv1.k}, {self.cv2.k}, "
                              f"cv2 c1 = {self.cv2.c1}")
@@ -508,19 +509,13 @@ class UpCat:
         return ops.upcat_bwd_bf16(dout, self.ca, self.up, da=da, db=db)
 
 
-def _convbn(groups, t, eps, momentum):
-    """(w, gamma, beta[, running_mean, running_var]) -> ConvBN with SiLU, stride 1"""
-    opt = lambda i: t[i] if len(t) > i else None
-    return ConvBN(groups, t[0], opt(1), opt(2), 1, opt(3), opt(4), eps, momentum)
-
-
 class Bottleneck:
     """Ultralytics `Bottleneck(c1, c2, shortcut=True, k=(3, 3), e)` with c1 == c2 (every use in YOLO11) in training mode: out = x + cv2(cv1(x)), two
     3x3 ConvBN.  cv1 / cv2: (w, gamma, beta[, running_mean, running_var]), registered in `groups` in that order.  The residual add and the gradient
     sum at x's fan-out are ops.add_bf16 (fp32 add, one rounding).  ConvBN's contract: bf16 NHWC in and out, `forward` / `backward` / `fold`."""
 
     def __init__(self, groups, cv1, cv2, eps=1e-3, momentum=0.03):
-        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        self.cv1, self.cv2 = _bn_block(ConvBN, groups, cv1, eps, momentum), _bn_block(ConvBN, groups, cv2, eps, momentum)
         if (self.cv1.k, self.cv2.k) != (3, 3) or self.cv2.c1 != self.cv1.c2 or self.cv2.c2 != self.cv1.c1:
             raise ValueError(f"Bottleneck: cv1 and cv2 are 3x3 convs c -> c_ -> c (the shortcut is always taken), got {tuple(cv1[0].shape)}, "
                              f"{tuple(cv2[0].shape)}")
@@ -550,7 +545,7 @@ class C3k:
     its backward are the upcat ops with up = 1; the two gradients of x are summed by ops.add_bf16."""
 
     def __init__(self, groups, cv1, cv2, cv3, m, eps=1e-3, momentum=0.03):
-        self.cv1, self.cv2, self.cv3 = (_convbn(groups, t, eps, momentum) for t in (cv1, cv2, cv3))
+        self.cv1, self.cv2, self.cv3 = (_bn_block(ConvBN, groups, t, eps, momentum) for t in (cv1, cv2, cv3))
         self.m = [Bottleneck(groups, a, b, eps, momentum) for (a, b) in m]
         c_ = self.cv1.c2
         if (self.cv1.k, self.cv2.k, self.cv3.k) != (1, 1, 1) or self.cv2.c1 != self.cv1.c1 or self.cv2.c2 != c_ or self.cv3.c1 != 2 * c_:
@@ -591,7 +586,7 @@ class C3k2:
     y_i is dcat's window i plus the gradient that comes back through m_i, one window add (fp32, one rounding) per member."""
 
     def __init__(self, groups, cv1, cv2, m, c3k=False, eps=1e-3, momentum=0.03):
-        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        self.cv1, self.cv2 = _bn_block(ConvBN, groups, cv1, eps, momentum), _bn_block(ConvBN, groups, cv2, eps, momentum)
         self.m = [C3k(groups, *t, eps, momentum) if c3k else Bottleneck(groups, *t, eps, momentum) for t in m]
         n, c = len(self.m), self.cv1.c2 // 2
         if (self.cv1.k, self.cv2.k) != (1, 1) or self.cv1.c2 % 16 or n < 1 or self.cv2.c1 != (2 + n) * c:
@@ -640,7 +635,7 @@ class C2PSA:
     split is two channel-window copies, the concat and its backward the upcat ops with up = 1; dt = cat(da, db') again by upcat."""
 
     def __init__(self, groups, cv1, cv2, blocks, nh, eps=1e-3, momentum=0.03):
-        self.cv1, self.cv2 = _convbn(groups, cv1, eps, momentum), _convbn(groups, cv2, eps, momentum)
+        self.cv1, self.cv2 = _bn_block(ConvBN, groups, cv1, eps, momentum), _bn_block(ConvBN, groups, cv2, eps, momentum)
         self.m = [PSABlock(groups, *t, nh, eps, momentum) for t in blocks]
         c = int(nh) * 64
         if (self.cv1.k, self.cv2.k) != (1, 1) or self.cv1.c2 != 2 * c or self.cv2.c1 != 2 * c or not self.m:
@@ -648,12 +643,10 @@ class C2PSA:
                              f"PSABlock, got {tuple(cv1[0].shape)}, {tuple(cv2[0].shape)}, {len(self.m)} blocks")
         self.c1, self.c2, self.c = self.cv1.c1, self.cv2.c2, c
 
+    PSA_NAMES = (("attn.qkv", "qkv"), ("attn.proj", "proj"), ("attn.pe", "pe"), ("ffn.0", "ffn0"), ("ffn.1", "ffn1"))  # (checkpoint name, PSABlock attribute = fold() key)
+
     def named_blocks(self):
-        out = [("cv1", self.cv1), ("cv2", self.cv2)]
-        for i, m in enumerate(self.m):
-            out += [(f"m.{i}.attn.qkv", m.attn.qkv), (f"m.{i}.attn.proj", m.attn.proj), (f"m.{i}.attn.pe", m.attn.pe), (f"m.{i}.ffn.0", m.ffn0),
-                    (f"m.{i}.ffn.1", m.ffn1)]
-        return out
+        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}.{n}", getattr(m, a)) for i, m in enumerate(self.m) for n, a in self.PSA_NAMES]
 
     def forward(self, x):
         """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]; H W <= 192 (the attention core)."""
@@ -676,109 +669,35 @@ class C2PSA:
         out = {"cv1": self.cv1.fold(), "cv2": self.cv2.fold()}
         for i, m in enumerate(self.m):
             f = m.fold()
-            out.update({f"m.{i}.attn.qkv": f["qkv"], f"m.{i}.attn.proj": f["proj"], f"m.{i}.attn.pe": f["pe"], f"m.{i}.ffn.0": f["ffn0"], f"m.{i}.ffn.1": f["ffn1"]})
+            out.update({f"m.{i}.{n}": f[a] for n, a in self.PSA_NAMES})
         return out
 
 
-class DetectBoxBranchStep:
-    """Ultralytics Detect.cv2[i] trained as the reference trains it, BatchNorm UNFOLDED: ConvBN 3x3 -> ConvBN 3x3 -> Conv2d 1x1 (+bias) ->
-    4 x 16 DFL logits per anchor -> DFL loss -> backward -> DDP gradient average -> optimiser step, over the trainer's three parameter groups
-    (the unfolded counterpart of BoxBranchStep).  convs: two (w, gamma, beta) triples (gamma / beta None: 1 / 0); w3 [c_out, c, 1, 1], b3 [c_out]."""
-
-    def __init__(self, convs, w3, b3, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3, bn_momentum=0.03):
-        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
-        self.blocks = [ConvBN(self.groups, w, g, b, eps=eps, momentum=bn_momentum) for (w, g, b) in convs]
-        self._i3, self._ib3 = self.groups.add(0, w3), self.groups.add(2, b3)
-        self.groups.build()
-        self.cout3 = w3.shape[0]
-
-    w3 = property(lambda self: self.groups.param[self._i3])
-    b3 = property(lambda self: self.groups.param[self._ib3])
-    dw3 = property(lambda self: self.groups.grad[self._i3])
-    db3 = property(lambda self: self.groups.grad[self._ib3])
-
-    def forward_backward(self, x, target_ltrb, weight=None, target_scores_sum=1.0):
-        """x bf16 [B,H,W,cin]; target_ltrb fp32 [B*H*W, 4] (bins), weight fp32 [B*H*W] or None -> (loss fp32[1], dx bf16 like x); every parameter
-        gradient is left in the groups' gradient buffers."""
-        H, W = x.shape[1], x.shape[2]
-        a = x
-        for blk in self.blocks:
-            a = blk.forward(a)
-        out = ops.conv_fwd_bf16(a, ops.conv_pack_bf16(self.w3, H, W), self.b3, self.cout3, 1)
-        loss, g = ops.dfl_loss(out.float().reshape(-1, self.cout3), target_ltrb, weight, target_scores_sum)
-        d3 = g.reshape(out.shape).to(torch.bfloat16)
-        conv_wgrad(a, d3, 1, out=self.dw3)
-        ops.bias_grad_bf16(d3, self.db3)
-        d = ops.conv_fwd_bf16(d3, ops.conv_pack_bf16(self.w3, H, W, dgrad_form=True), None, self.w3.shape[1], 1)
-        for blk in reversed(self.blocks):
-            d = blk.backward(d)
-        return loss, d
-
-    def step(self, x, target_ltrb, weight=None, target_scores_sum=1.0, group=None):
-        loss, dx = self.forward_backward(x, target_ltrb, weight, target_scores_sum)
-        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
-        self.groups.step()
-        return loss, dx
-
-
-class StemConvBN:
+class StemConvBN(_BNBlock):
     """model.0 in training mode -- Conv2d(cin, c2, 3, 2, 1, bias=False) on the uint8 NHWC tile [B,H,W,cin] (cin 3 or 4, the operand is bf16(v / 255),
     channel order as stored) -> BatchNorm2d (batch statistics) -> SiLU -- under ConvBN's contract and parameter groups (w [c2,cin,3,3] in group 0,
     gamma in 1, beta in 2, running statistics as buffers).  The conv kernels read the tile and the master weights directly (csrc/narrowgrad.hip:
-    no float copy of the image, no pack step); BatchNorm and SiLU are the bn_silu_* ops.  `backward` returns None: the input is the image."""
+    no float copy of the image, no pack step).  forward(x uint8 [B,H,W,cin]) -> bf16 [B,(H+1)//2,(W+1)//2,c2]; `backward` returns None: the input is
+    the image.  `fold()`: the weights of a conv on v / 255."""
 
     def __init__(self, groups, w, gamma=None, beta=None, running_mean=None, running_var=None, eps=1e-3, momentum=0.03):
         if w.dim() != 4 or w.shape[1] not in (3, 4) or tuple(w.shape[2:]) != (3, 3) or w.shape[0] % 8 or not 8 <= w.shape[0] <= 64:
             raise ValueError(f"StemConvBN: w must be [c2,3 or 4,3,3] with c2 a multiple of 8 in [8, 64], got {tuple(w.shape)}")
-        c2, c1 = w.shape[0], w.shape[1]
-        self.c1, self.c2, self.k, self.s, self.eps, self.momentum, self.act = c1, c2, 3, 2, eps, momentum, True
-        dev = w.device
-        self.groups = groups
-        self._iw = groups.add(0, w)
-        self._ig = groups.add(1, gamma if gamma is not None else torch.ones(c2, device=dev))
-        self._ib = groups.add(2, beta if beta is not None else torch.zeros(c2, device=dev))
-        self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c2, device=dev)).float().contiguous()
-        self.running_var = (running_var.clone() if running_var is not None else torch.ones(c2, device=dev)).float().contiguous()
-        self.saved = None
+        super().__init__(groups, w, gamma, beta, w.shape[1], w.shape[0], 3, 2, True, running_mean, running_var, eps, momentum)
 
-    w = property(lambda self: self.groups.param[self._iw])
-    gamma = property(lambda self: self.groups.param[self._ig])
-    beta = property(lambda self: self.groups.param[self._ib])
-    dw = property(lambda self: self.groups.grad[self._iw])
-    dgamma = property(lambda self: self.groups.grad[self._ig])
-    dbeta = property(lambda self: self.groups.grad[self._ib])
+    def _conv_fwd(self, x):
+        return ops.stemconv_fwd_u8(x, self.w)
 
-    def forward(self, x):
-        """x uint8 [B,H,W,cin] -> a bf16 [B,(H+1)//2,(W+1)//2,c2]; keeps (x, z, mean, invstd) for the backward."""
-        z = ops.stemconv_fwd_u8(x, self.w)
-        a, mean, invstd = ops.bn_silu_fwd_bf16(z, self.gamma, self.beta, self.running_mean, self.running_var, self.eps, self.momentum)
-        self.saved = (x, z, mean, invstd)
-        return a
-
-    def backward(self, da):
-        """da bf16 like the forward's output -> None (no gradient flows into the image); dW, dgamma, dbeta go into the groups' gradient buffers."""
-        x, z, mean, invstd = self.saved
-        dz, _, _ = ops.bn_silu_bwd_bf16(z, da, self.gamma, self.beta, mean, invstd, self.dgamma, self.dbeta)
+    def _conv_bwd(self, x, dz):
         ops.stemconv_wgrad_u8(x, dz, out=self.dw)
         return None
 
-    def fold(self):
-        """-> (w, b): the eval-mode BN folded into the conv, fp32 (the weights of a conv on v / 255)."""
-        f = self.gamma / torch.sqrt(self.running_var + self.eps)
-        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
 
-
-class HeadOut:
-    """A plain `nn.Conv2d(c, cout, 1)` with bias at the end of a head branch (model.23.cv3.i.2: nc class logits; model.23.cv4.i.2: the angle logit)
-    in training mode: w [cout,c,1,1] in group 0, b [cout] in group 2.  forward(x bf16 [B,H,W,c]) -> FP32 logits [B,H,W,cout] (what the losses
-    read); backward(dy fp32) -> dx bf16, with dW and db written straight into the groups' gradient views by the same pass (csrc/narrowgrad.hip)."""
+class _ConvBias:
+    """A plain 1x1 `nn.Conv2d` with bias at the end of a head branch: w [cout,c,1,1] in group 0 of `groups`, b [cout] in group 2."""
 
     def __init__(self, groups, w, b):
-        if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or b.dim() != 1 or b.shape[0] != w.shape[0]:
-            raise ValueError(f"HeadOut: w must be [cout,c,1,1] and b [cout], got {tuple(w.shape)}, {tuple(b.shape)}")
         self.c2, self.c1 = w.shape[0], w.shape[1]
-        if self.c1 % 8 or not 8 <= self.c1 <= 512 or not 1 <= self.c2 <= 64:
-            raise ValueError(f"HeadOut: {self.c1} -> {self.c2}: c a multiple of 8 in [8, 512], 1 <= cout <= 64")
         self.groups = groups
         self._iw, self._ib = groups.add(0, w), groups.add(2, b)
         self.saved = None
@@ -787,6 +706,20 @@ class HeadOut:
     b = property(lambda self: self.groups.param[self._ib])
     dw = property(lambda self: self.groups.grad[self._iw])
     db = property(lambda self: self.groups.grad[self._ib])
+
+
+class HeadOut(_ConvBias):
+    """A plain `nn.Conv2d(c, cout, 1)` with bias at the end of a head branch (model.23.cv3.i.2: nc class logits; model.23.cv4.i.2: the angle logit)
+    in training mode: w [cout,c,1,1] in group 0, b [cout] in group 2.  forward(x bf16 [B,H,W,c]) -> FP32 logits [B,H,W,cout] (what the losses
+    read); backward(dy fp32) -> dx bf16, with dW and db written straight into the groups' gradient views by the same pass (csrc/narrowgrad.hip)."""
+
+    def __init__(self, groups, w, b):
+        if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or b.dim() != 1 or b.shape[0] != w.shape[0]:
+            raise ValueError(f"HeadOut: w must be [cout,c,1,1] and b [cout], got {tuple(w.shape)}, {tuple(b.shape)}")
+        c2, c1 = w.shape[0], w.shape[1]
+        if c1 % 8 or not 8 <= c1 <= 512 or not 1 <= c2 <= 64:
+            raise ValueError(f"HeadOut: {c1} -> {c2}: c a multiple of 8 in [8, 512], 1 <= cout <= 64")
+        super().__init__(groups, w, b)
 
     def forward(self, x):
         self.saved = x
@@ -797,57 +730,112 @@ class HeadOut:
         return dx
 
 
-class DetectClassBranchStep:
-    """Ultralytics Detect.cv3[i] trained as the reference trains it (the counterpart of DetectBoxBranchStep): two `ClassBranchPair`s (DWConv 3x3 ->
-    Conv 1x1, BatchNorm unfolded) -> HeadOut(nc) -> BCE term of the OBB loss -> backward -> DDP gradient average -> optimiser step, over the
-    trainer's three parameter groups.  pairs: two (dw, pw) with dw / pw = (w, gamma, beta[, running_mean, running_var]); w3 [nc,c,1,1], b3 [nc]."""
+class BoxOut(_ConvBias):
+    """The box branch's output (model.23.cv2.i.2: 4 x 16 DFL logits, a multiple of 8 channels) under HeadOut's contract, on the dense kernels and
+    with BF16 logits: forward(x bf16 [B,H,W,c]) -> bf16 [B,H,W,cout] = pack + conv + bias; backward(dy bf16) -> dx bf16 = weight gradient and bias
+    gradient into the groups' gradient views, then the conv on the dgrad-form pack."""
 
-    def __init__(self, pairs, w3, b3, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3, bn_momentum=0.03):
-        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
-        self.pairs = [ClassBranchPair(self.groups, dw, pw, eps, bn_momentum) for (dw, pw) in pairs]
-        self.out = HeadOut(self.groups, w3, b3)
-        self.groups.build()
+    def forward(self, x):
+        self.saved = x
+        return ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2]), self.b, self.c2, 1)
 
-    def forward_backward(self, x, targets, target_scores_sum=1.0):
-        """x bf16 [B,H,W,cin]; targets fp32 [B,H,W,nc] (or [B*H*W, nc]) -> (loss fp32[1], dx bf16 like x); every parameter gradient is left in the
-        groups' gradient buffers."""
-        a = x
-        for p in self.pairs:
-            a = p.forward(a)
-        logits = self.out.forward(a)
-        loss, g = ops.bce_loss(logits, targets.reshape(logits.shape), target_scores_sum)
-        d = self.out.backward(g)
-        for p in reversed(self.pairs):
-            d = p.backward(d)
-        return loss, d
-
-    def step(self, x, targets, target_scores_sum=1.0, group=None):
-        loss, dx = self.forward_backward(x, targets, target_scores_sum)
-        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
-        self.groups.step()
-        return loss, dx
+    def backward(self, dy):
+        x = self.saved
+        conv_wgrad(x, dy, 1, out=self.dw)
+        ops.bias_grad_bf16(dy, self.db)
+        return ops.conv_fwd_bf16(dy, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2], dgrad_form=True), None, self.c1, 1)
 
 
-class DetectAngleBranch:
+class _DetectBoxBranch(_Chain):
+    """Detect.cv2[i]: ConvBN 3x3 -> ConvBN 3x3 -> BoxOut -> bf16 [B,H,W,64] DFL logits.  convs: two (w, gamma, beta) triples (gamma / beta None:
+    1 / 0), registered in `groups` before w3 [c_out,c,1,1] (group 0) and b3 [c_out] (group 2), which read through as w3 / b3 / dw3 / db3."""
+
+    def __init__(self, groups, convs, w3, b3, eps, momentum):
+        self.blocks = [_bn_block(ConvBN, groups, t, eps, momentum) for t in convs]
+        self.out = BoxOut(groups, w3, b3)
+        self.chain = self.blocks + [self.out]
+
+    w3 = property(lambda self: self.out.w)
+    b3 = property(lambda self: self.out.b)
+    dw3 = property(lambda self: self.out.dw)
+    db3 = property(lambda self: self.out.db)
+    cout3 = property(lambda self: self.out.c2)
+
+
+class _DetectClassBranch(_Chain):
+    """Detect.cv3[i]: two ClassBranchPairs (DWConv 3x3 -> Conv 1x1, BatchNorm unfolded) -> HeadOut(nc) -> fp32 class logits.  pairs: two (dw, pw)
+    with dw / pw = (w, gamma, beta[, running_mean, running_var]), registered in `groups` before w3 [nc,c,1,1] and b3 [nc]."""
+
+    def __init__(self, groups, pairs, w3, b3, eps, momentum):
+        self.pairs = [ClassBranchPair(groups, dw, pw, eps, momentum) for (dw, pw) in pairs]
+        self.out = HeadOut(groups, w3, b3)
+        self.chain = self.pairs + [self.out]
+
+
+class DetectAngleBranch(_Chain):
     """Ultralytics OBB.cv4[i]: ConvBN 3x3 -> ConvBN 3x3 -> HeadOut(1), as forward(x bf16) -> fp32 angle logits [B,H,W,1] and backward(dangle fp32) ->
     dx bf16.  There is no loss here: the angle's gradient arrives through ProbIoU on the decoded boxes.  convs: two (w, gamma, beta) triples
     (gamma / beta None: 1 / 0), registered in `groups` before w3 [ne,c,1,1] and b3 [ne]."""
 
     def __init__(self, groups, convs, w3, b3, eps=1e-3, momentum=0.03):
-        self.blocks = [ConvBN(groups, w, g, b, eps=eps, momentum=momentum) for (w, g, b) in convs]
+        self.blocks = [_bn_block(ConvBN, groups, t, eps, momentum) for t in convs]
         self.out = HeadOut(groups, w3, b3)
+        self.chain = self.blocks + [self.out]
 
-    def forward(self, x):
-        a = x
-        for blk in self.blocks:
-            a = blk.forward(a)
-        return self.out.forward(a)
 
-    def backward(self, dangle):
-        d = self.out.backward(dangle)
-        for blk in reversed(self.blocks):
-            d = blk.backward(d)
-        return d
+class _Step:
+    """step(*inputs, group=None) of a module with `forward_backward(*inputs)` and `groups`: forward + backward, the DDP gradient average over
+    `group` (no-op on one rank), the optimiser step -> what forward_backward returned."""
+
+    def step(self, *inputs, group=None, **kw):
+        out = self.forward_backward(*inputs, **kw)
+        allreduce_gradients(self.groups.flat_grads(), group)
+        self.groups.step()
+        return out
+
+
+class _BranchStep(_Step):
+    """A head branch (`BRANCH`) on the trainer's three parameter groups of its own, trained under one term of the loss by the subclass's
+    `forward_backward`.  The branch's attributes (its layers and their parameter views) read through."""
+
+    def __init__(self, layers, w3, b3, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3, bn_momentum=0.03):
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        self.branch = self.BRANCH(self.groups, layers, w3, b3, eps, bn_momentum)
+        self.groups.build()
+
+    def __getattr__(self, name):
+        if name == "branch":  # (not built yet)
+            raise AttributeError(name)
+        return getattr(self.branch, name)
+
+
+class DetectBoxBranchStep(_BranchStep):
+    """Ultralytics Detect.cv2[i] trained as the reference trains it, BatchNorm UNFOLDED: ConvBN 3x3 -> ConvBN 3x3 -> Conv2d 1x1 (+bias) ->
+    4 x 16 DFL logits per anchor -> DFL loss -> backward -> DDP gradient average -> optimiser step, over the trainer's three parameter groups
+    (the unfolded counterpart of BoxBranchStep).  DetectBoxBranchStep(convs, w3, b3, ...) as _DetectBoxBranch takes them; `blocks`, `w3`, `b3`,
+    `dw3`, `db3`, `cout3` are the branch's."""
+    BRANCH = _DetectBoxBranch
+
+    def forward_backward(self, x, target_ltrb, weight=None, target_scores_sum=1.0):
+        """x bf16 [B,H,W,cin]; target_ltrb fp32 [B*H*W, 4] (bins), weight fp32 [B*H*W] or None -> (loss fp32[1], dx bf16 like x); every parameter
+        gradient is left in the groups' gradient buffers."""
+        out = self.branch.forward(x)
+        loss, g = ops.dfl_loss(out.float().reshape(-1, self.cout3), target_ltrb, weight, target_scores_sum)
+        return loss, self.branch.backward(g.reshape(out.shape).to(torch.bfloat16))
+
+
+class DetectClassBranchStep(_BranchStep):
+    """Ultralytics Detect.cv3[i] trained as the reference trains it (the counterpart of DetectBoxBranchStep): two `ClassBranchPair`s -> HeadOut(nc)
+    -> BCE term of the OBB loss -> backward -> DDP gradient average -> optimiser step, over the trainer's three parameter groups.
+    DetectClassBranchStep(pairs, w3, b3, ...) as _DetectClassBranch takes them; `pairs` and `out` are the branch's."""
+    BRANCH = _DetectClassBranch
+
+    def forward_backward(self, x, targets, target_scores_sum=1.0):
+        """x bf16 [B,H,W,cin]; targets fp32 [B,H,W,nc] (or [B*H*W, nc]) -> (loss fp32[1], dx bf16 like x); every parameter gradient is left in the
+        groups' gradient buffers."""
+        logits = self.branch.forward(x)
+        loss, g = ops.bce_loss(logits, targets.reshape(logits.shape), target_scores_sum)
+        return loss, self.branch.backward(g)
 
 
 def pad_targets(rows, B, imgsz, device=None):
@@ -904,59 +892,7 @@ class OBBCriterion:
         return items, (d_box, d_cls, d_angle)
 
 
-class _DetectBoxBranch:
-    """Detect.cv2[i] inside DetectHead: ConvBN 3x3 -> ConvBN 3x3 -> Conv2d 1x1 (+bias) -> bf16 [B,H,W,64] DFL logits; DetectBoxBranchStep's layers
-    without its loss, registered in the head's `groups` (blocks, then w3 in group 0 and b3 in group 2)."""
-
-    def __init__(self, groups, convs, w3, b3, eps, momentum):
-        self.groups = groups
-        self.blocks = [ConvBN(groups, w, g, b, eps=eps, momentum=momentum) for (w, g, b) in convs]
-        self._i3, self._ib3 = groups.add(0, w3), groups.add(2, b3)
-        self.cout3, self.saved = w3.shape[0], None
-
-    w3 = property(lambda self: self.groups.param[self._i3])
-    b3 = property(lambda self: self.groups.param[self._ib3])
-    dw3 = property(lambda self: self.groups.grad[self._i3])
-    db3 = property(lambda self: self.groups.grad[self._ib3])
-
-    def forward(self, x):
-        a = x
-        for blk in self.blocks:
-            a = blk.forward(a)
-        self.saved = a
-        return ops.conv_fwd_bf16(a, ops.conv_pack_bf16(self.w3, a.shape[1], a.shape[2]), self.b3, self.cout3, 1)
-
-    def backward(self, d3):
-        a = self.saved
-        conv_wgrad(a, d3, 1, out=self.dw3)
-        ops.bias_grad_bf16(d3, self.db3)
-        d = ops.conv_fwd_bf16(d3, ops.conv_pack_bf16(self.w3, a.shape[1], a.shape[2], dgrad_form=True), None, self.w3.shape[1], 1)
-        for blk in reversed(self.blocks):
-            d = blk.backward(d)
-        return d
-
-
-class _DetectClassBranch:
-    """Detect.cv3[i] inside DetectHead: two ClassBranchPairs -> HeadOut(nc); DetectClassBranchStep's layers without its loss."""
-
-    def __init__(self, groups, pairs, w3, b3, eps, momentum):
-        self.pairs = [ClassBranchPair(groups, dw, pw, eps, momentum) for (dw, pw) in pairs]
-        self.out = HeadOut(groups, w3, b3)
-
-    def forward(self, x):
-        a = x
-        for p in self.pairs:
-            a = p.forward(a)
-        return self.out.forward(a)
-
-    def backward(self, dy):
-        d = self.out.backward(dy)
-        for p in reversed(self.pairs):
-            d = p.backward(d)
-        return d
-
-
-class DetectHead:
+class DetectHead(_Step):
     """The three levels of Ultralytics `Detect` / `OBB` (model.23: cv2 box, cv3 class, cv4 angle branches on P3, P4, P5) in training mode over ONE
     `ParamGroups`, trained under `OBBCriterion`.  levels: three dicts {"box": (convs, w3, b3), "cls": (pairs, w3, b3), "angle": (convs, w3, b3)} with
     convs / pairs as DetectBoxBranchStep / DetectClassBranchStep / DetectAngleBranch take them; per level the parameters are registered in the order
@@ -992,9 +928,3 @@ class DetectHead:
         box, cls, angle = self.forward(feats)
         items, (d_box, d_cls, d_angle) = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
         return items, self.backward(d_box, d_cls, d_angle)
-
-    def step(self, feats, gt_labels, gt_bboxes, mask_gt, group=None):
-        items, dx = self.forward_backward(feats, gt_labels, gt_bboxes, mask_gt)
-        allreduce_gradients(self.groups.flat_grads(), group)  # DDP: the gradient average (no-op on one rank)
-        self.groups.step()
-        return items, dx
