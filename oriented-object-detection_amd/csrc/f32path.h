@@ -9,9 +9,11 @@
 #include <cstdint>
 #include <vector>
 
-#include "conv.h"
+#include "tensorref.h"
 
 namespace obb {
+
+struct Conv32Tiling { int TH, TW, CK, WC, MFM, NI, NC; };  // (NC 0 / 1: one cout fragment per wave)
 
 // out[b, oy, ox, co] = epilogue( sum in[b, oy*s+ky-p, ox*s+kx-p, ci] * W[co][ci][ky][kx] ); TensorRef offsets count fp32 elements
 // (in: bytes of the uint8 tile when in_u8).  Plain NHWC slices only.
@@ -50,9 +52,9 @@ struct Conv32Launch {
     int tiles_y = 1, tiles_x = 1;
     int NC = 1;  // cout fragments per wave: 2 = WC waves x 32 couts, MFM <= 4 pixel fragments (plain / VCAT forms; wpk packed for it)
     int xtile = 1;  // resident workgroups that walk several tiles, the next tile's first stage fetched under this tile's last k loop (plain / VCAT forms)
+    void set_tiling(const Conv32Tiling &t) { TH = t.TH; TW = t.TW; CK = t.CK; WC = t.WC; MFM = t.MFM; NI = t.NI; NC = t.NC; }
 };
 
-struct Conv32Tiling { int TH, TW, CK, WC, MFM, NI, NC; };  // (NC 0 / 1: one cout fragment per wave)
 // vcat: the input is a virtual [upsample | skip] concat; nc2: the layer may take the two-fragments-per-wave form (no tail, no depthwise prologue)
 Conv32Tiling plan_conv32(int ks, int stride, int cin, int cout, int Hout, int Wout, bool in_u8, bool vcat = false, bool nc2 = false);
 // true if the 1x1 conv (cout1 -> cout2) can run as the fused tail of a layer tiled as `t`

@@ -282,7 +282,7 @@ struct Builder {
         Conv32Launch &L = op.c32;
         const Conv32Tiling t = plan_conv32(1, 1, sk, r->c2, op.Ho, op.Wo, false, false, true);
         L.ks = 1; L.stride = 1; L.cin = sk; L.cout = r->c2; L.act = r->act;
-        L.TH = t.TH; L.TW = t.TW; L.CK = t.CK; L.WC = t.WC; L.MFM = t.MFM; L.NI = t.NI; L.NC = t.NC;
+        L.set_tiling(t);
         L.Hin = L.Hout = op.H; L.Win = L.Wout = op.W; L.tiles_y = 1; L.tiles_x = 1;  // (1-D: bound per sub-batch)
         L.wpk = upload(pack_conv32_weights(split_cols(r->w, r->c2, r->c1, up_c, sk).data(), r->c2, sk, 1, t, nullptr, false));
         L.bias = bias_padded(r);
@@ -296,7 +296,7 @@ struct Builder {
         Conv32Launch &L = op.c32;
         const Conv32Tiling t = plan_conv32(r->k, r->s, r->c1, r->c2, op.Ho, op.Wo, in_u8, op.vin, M.o.nc2 && !tail_name);
         L.ks = r->k; L.stride = r->s; L.cin = r->c1; L.cout = r->c2; L.act = r->act; L.in_u8 = in_u8; L.flip_bgr = (in_u8 && M.ch == 3);
-        L.TH = t.TH; L.TW = t.TW; L.CK = t.CK; L.WC = t.WC; L.MFM = t.MFM; L.NI = t.NI; L.NC = std::max(1, t.NC);
+        L.set_tiling(t); L.NC = std::max(1, t.NC);
         L.Hin = op.H; L.Win = op.W; L.Hout = op.Ho; L.Wout = op.Wo;
         L.tiles_y = (op.Ho + t.TH - 1) / t.TH; L.tiles_x = (op.Wo + t.TW - 1) / t.TW;
         if (op.vin && (P.bufs[op.in.buf].va_C % t.CK || (t.WC != 4 && t.NC != 2))) { err = set_error(ctx, OBB_ERR_STATE, "layer %s cannot read the virtual concat in fp32 mode", op.name.c_str()); return; }
@@ -407,7 +407,7 @@ struct Builder {
         op.type = OP_CONV32;
         Conv32Launch &L = op.c32;
         L.ks = 1; L.stride = 1; L.cin = C; L.cout = rp->c2; L.act = rp->act; L.dw = 1; L.dw_act = rd->act;
-        L.TH = t.TH; L.TW = t.TW; L.CK = t.CK; L.WC = t.WC; L.MFM = t.MFM; L.NI = 1;
+        L.set_tiling(t);
         L.Hin = L.Hout = H; L.Win = L.Wout = W;
         L.tiles_y = (H + t.TH - 1) / t.TH; L.tiles_x = 1;
         L.wpk = upload(pack_dwpw32_weights(rp->w, rp->c2, C, rd->w, rd->b, t));
