@@ -464,6 +464,37 @@ int obb_sgd_step(obb_ctx *ctx, float *param, const float *grad, float *momentum_
 int obb_adamw_step(obb_ctx *ctx, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, int64_t step, float lr, double beta1,
                    double beta2, float eps, float weight_decay, obb_stream_t s);
 
+/* f1 (trainer update): what ultralytics `BaseTrainer.optimizer_step` and `ModelEMA.update` do around that step inside `model.train(...)`
+ * (Train_OBB.py:796-841), over SEGMENTS: a segment is one flat fp32 device buffer (a parameter group, or the buffer of BatchNorm running
+ * statistics) of n[k] elements, 16-byte aligned; 0 <= nseg <= 8; the pointer and length arrays are HOST arrays of nseg entries.  n[k] = 0 is legal
+ * (the segment is skipped, its pointers are not looked at).  Each call is one launch over all segments (none when every segment is empty); none
+ * reads back to the host, and none uses atomics, so every result is reproducible bit for bit.
+ * obb_grad_sumsq: replaces the per-tensor norms of `torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10.0)`.  partials[j] = the sum of
+ * squares (each square and each sum in double) of slab j: the 4096-element slabs of segment 0, then those of segment 1, ...;
+ * obb_grad_sumsq_partials (host only) gives their count, sum_k ceil(n[k] / 4096); partials_cap = the workspace's capacity in doubles.
+ * obb_clip_coef: the rest of clip_grad_norm_ without its host read.  total = sqrt(partials summed in index order, in double); clip[0] = total_norm =
+ * (float)total; clip[1] = coef = (float)min(1, max_norm / (total + 1e-6)) (NaN for a NaN total, 0 for an infinite one: error_if_nonfinite=False);
+ * clip[2] = 1.0f when total is finite, else 0.0f.  clip: device float[3]. */
+int obb_grad_sumsq_partials(const int64_t *n, int32_t nseg, int64_t *count);
+int obb_grad_sumsq(obb_ctx *ctx, const float *const *grad, const int64_t *n, int32_t nseg, double *partials, int64_t partials_cap, obb_stream_t s);
+int obb_clip_coef(obb_ctx *ctx, const double *partials, int64_t npartials, double max_norm, float *clip, obb_stream_t s);
+/* obb_sgd_step_multi / obb_adamw_step_multi: replace the in-place gradient scaling of clip_grad_norm_ and `optimizer.step()` over all parameter
+ * groups: obb_sgd_step / obb_adamw_step of every segment with its own lr[k] and weight_decay[k] (host float[nseg]) on the gradient g * clip[1] (one
+ * fp32 multiply; clip == NULL: the gradient as it is).  With clip[1] == 1.0f or clip == NULL the results are bit-identical to the single-group
+ * entry points.  The gradient buffers are only read.  clip: the device float[3] of obb_clip_coef. */
+int obb_sgd_step_multi(obb_ctx *ctx, float *const *param, const float *const *grad, float *const *momentum_buf, const int64_t *n, const float *lr,
+                       const float *weight_decay, int32_t nseg, float momentum, int32_t nesterov, int32_t first_step, const float *clip, obb_stream_t s);
+int obb_adamw_step_multi(obb_ctx *ctx, float *const *param, const float *const *grad, float *const *exp_avg, float *const *exp_avg_sq, const int64_t *n,
+                         const float *lr, const float *weight_decay, int32_t nseg, int64_t step, double beta1, double beta2, float eps, const float *clip,
+                         obb_stream_t s);
+/* obb_grad_accumulate: replaces autograd's accumulation into `.grad` over the `accumulate` iterations between two optimiser steps (the kernels
+ * here write gradients, they do not add to them): acc = first ? grad : acc + grad (first: acc is not read).
+ * obb_ema_update: replaces the per-entry loop of `ModelEMA.update` over the state dict (weights AND BatchNorm running statistics):
+ * ema = ema * d + (1 - d) * src in torch's order (v.mul_(d); v.add_((1 - d) * src): three fp32 roundings), d = (float)decay and 1 - d =
+ * (float)(1 - decay) each rounded from double (1.0f - (float)0.9999 is 6e-4 off 1e-4 in relative terms). */
+int obb_grad_accumulate(obb_ctx *ctx, float *const *acc, const float *const *grad, const int64_t *n, int32_t nseg, int32_t first, obb_stream_t s);
+int obb_ema_update(obb_ctx *ctx, float *const *ema, const float *const *src, const int64_t *n, int32_t nseg, double decay, obb_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -99,6 +99,13 @@ SIGNATURES = {
     "obb_crit_loss": [_V, _V, C.c_int32, _V, _V, c_ip, c_ip, C.c_int32, C.c_int32, _V, _V, _V, c_fp, _V, _V, _V, _V, _V, _V],
     "obb_sgd_step": [_V, _V, _V, _V, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _V],
     "obb_adamw_step": [_V, _V, _V, _V, _V, C.c_int64, C.c_int64, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, _V],
+    "obb_grad_sumsq_partials": [c_lp, C.c_int32, c_lp],
+    "obb_grad_sumsq": [_V, _V, c_lp, C.c_int32, _V, C.c_int64, _V],
+    "obb_clip_coef": [_V, _V, C.c_int64, C.c_double, _V, _V],
+    "obb_sgd_step_multi": [_V, _V, _V, _V, c_lp, c_fp, c_fp, C.c_int32, C.c_float, C.c_int32, C.c_int32, _V, _V],
+    "obb_adamw_step_multi": [_V, _V, _V, _V, _V, c_lp, c_fp, c_fp, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_float, _V, _V],
+    "obb_grad_accumulate": [_V, _V, _V, c_lp, C.c_int32, C.c_int32, _V],
+    "obb_ema_update": [_V, _V, _V, c_lp, C.c_int32, C.c_double, _V],
 }
 _RESTYPE = {"obb_last_error": C.c_char_p}
 

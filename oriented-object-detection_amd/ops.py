@@ -381,6 +381,57 @@ def _crit_loss(box0: T, box1: T, box2: T, cls0: T, cls1: T, cls2: T, angle0: T, 
           vp((d_box0, d_box1, d_box2)), vp((d_cls0, d_cls1, d_cls2)), vp((d_angle0, d_angle1, d_angle2)), _p(items), _p(tss), _stream())
 
 
+# ---------------------------------------------------------------- trainer update over flat segments (csrc/trainupd.hip)
+def _segs(*lists):
+    """-> the host-side segment arrays of obb_*_multi and friends: one void*[nseg] per list of flat tensors, then n int64[nseg] and nseg"""
+    k = len(lists[0])
+    vp = lambda ts: (C.c_void_p * k)(*[t.data_ptr() if t.numel() else 0 for t in ts])
+    return (*[vp(ts) for ts in lists], (C.c_int64 * k)(*[t.numel() for t in lists[0]]), k)
+
+
+def _floats(v):
+    return (C.c_float * len(v))(*[float(x) for x in v])
+
+
+@_op("grad_sumsq", ("partials",))
+def _grad_sumsq(grads: List[T], partials: T) -> None:
+    g, n, k = _segs(grads)
+    _call("obb_grad_sumsq", ctx(partials.device), g, n, k, _p(partials), partials.numel(), _stream())
+
+
+@_op("clip_coef", ("clip",))
+def _clip_coef(partials: T, max_norm: float, clip: T) -> None:
+    _call("obb_clip_coef", ctx(clip.device), _p(partials), partials.numel(), float(max_norm), _p(clip), _stream())
+
+
+@_op("sgd_step_multi", ("params", "momentum_bufs"))
+def _sgd_step_multi(params: List[T], grads: List[T], momentum_bufs: List[T], lrs: List[float], weight_decays: List[float], momentum: float, nesterov: bool,
+                    first_step: bool, clip: Optional[T]) -> None:
+    p, g, b, n, k = _segs(params, grads, momentum_bufs)
+    _call("obb_sgd_step_multi", ctx(params[0].device), p, g, b, n, _floats(lrs), _floats(weight_decays), k, float(momentum), int(bool(nesterov)),
+          int(bool(first_step)), _p(clip), _stream())
+
+
+@_op("adamw_step_multi", ("params", "exp_avgs", "exp_avg_sqs"))
+def _adamw_step_multi(params: List[T], grads: List[T], exp_avgs: List[T], exp_avg_sqs: List[T], lrs: List[float], weight_decays: List[float], step: int,
+                      beta1: float, beta2: float, eps: float, clip: Optional[T]) -> None:
+    p, g, m, v, n, k = _segs(params, grads, exp_avgs, exp_avg_sqs)
+    _call("obb_adamw_step_multi", ctx(params[0].device), p, g, m, v, n, _floats(lrs), _floats(weight_decays), k, int(step), float(beta1), float(beta2),
+          float(eps), _p(clip), _stream())
+
+
+@_op("grad_accumulate", ("accs",))
+def _grad_accumulate(accs: List[T], grads: List[T], first: bool) -> None:
+    a, g, n, k = _segs(accs, grads)
+    _call("obb_grad_accumulate", ctx(accs[0].device), a, g, n, k, int(bool(first)), _stream())
+
+
+@_op("ema_update", ("emas",))
+def _ema_update(emas: List[T], srcs: List[T], decay: float) -> None:
+    e, s, n, k = _segs(emas, srcs)
+    _call("obb_ema_update", ctx(emas[0].device), e, s, n, k, float(decay), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -1388,6 +1439,105 @@ def adamw_step(param, grad, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), e
     if not (p.numel() == g.numel() == m.numel() == v.numel()):
         raise ValueError("adamw_step: size mismatch")
     _O.adamw_step(p, g, m, v, int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay))
+
+
+MAX_SEGMENTS = 8  # segments per launch of the trainer-update kernels (csrc/trainupd.hip: kMaxSeg)
+
+
+def _seg_lists(name, first, *others):
+    """flat fp32 segment lists of one call: at most MAX_SEGMENTS, every list as long as the first and element for element the same size"""
+    first = [_chk(t, torch.float32, f"{name}[{i}]").reshape(-1) for i, t in enumerate(first)]
+    if not 1 <= len(first) <= MAX_SEGMENTS:
+        raise ValueError(f"{name}: 1 to {MAX_SEGMENTS} segments, got {len(first)}")
+    out = [first]
+    for o in others:
+        o = [_chk(t, torch.float32, f"{name}[{i}]").reshape(-1) for i, t in enumerate(o)]
+        if [t.numel() for t in o] != [t.numel() for t in first]:
+            raise ValueError(f"{name}: the segment lists differ in length or sizes")
+        out.append(o)
+    return out
+
+
+def _per_segment(v, k, name):
+    v = [float(v)] * k if isinstance(v, (int, float)) else [float(x) for x in v]
+    if len(v) != k:
+        raise ValueError(f"{name}: one value or one per segment ({k}), got {len(v)}")
+    return v
+
+
+def sumsq_partials(sizes):
+    """How many double partials `grad_sumsq` writes for segments of these sizes (one per 4096-element slab of each)."""
+    n = (C.c_int64 * len(sizes))(*[int(s) for s in sizes])
+    count = C.c_int64(0)
+    if _lib.lib().obb_grad_sumsq_partials(n, len(sizes), C.byref(count)) != 0:
+        raise ValueError(f"sumsq_partials: at most {MAX_SEGMENTS} segments of non-negative size")
+    return count.value
+
+
+def grad_sumsq(grads, partials=None):
+    """One launch over a list of flat fp32 gradient buffers -> partials fp64[sumsq_partials(sizes)]: the sum of squares of every 4096-element slab,
+    squares and sums in double (exact per square; 1e20 and 1e-25 neither overflow nor vanish), reduced in a fixed order: reproducible."""
+    (g,) = _seg_lists("grad_sumsq", grads)
+    need = sumsq_partials([t.numel() for t in g])
+    if partials is None:
+        partials = torch.empty(need, dtype=torch.float64, device=g[0].device)
+    elif _chk(partials, torch.float64, "partials").numel() != need:
+        raise ValueError(f"grad_sumsq: partials must hold {need} doubles")
+    _O.grad_sumsq(g, partials)
+    return partials
+
+
+def clip_coef(partials, max_norm=10.0, clip=None):
+    """One launch, one workgroup: the partials of `grad_sumsq` -> clip fp32[3] ON THE DEVICE = (total_norm, coef = min(1, max_norm / (total_norm + 1e-6)),
+    finite) -- torch.nn.utils.clip_grad_norm_'s coefficient (NaN norm: NaN; infinite norm: 0) without its host read."""
+    pt = _chk(partials, torch.float64, "partials")
+    if clip is None:
+        clip = torch.empty(3, dtype=torch.float32, device=pt.device)
+    elif _chk(clip, torch.float32, "clip").numel() != 3:
+        raise ValueError("clip_coef: clip is fp32[3]")
+    _O.clip_coef(pt, float(max_norm), clip)
+    return clip
+
+
+def clip_grad_norm(grads, max_norm=10.0):
+    """torch.nn.utils.clip_grad_norm_ over flat gradient buffers in two launches, WITHOUT touching the gradients and without a host read: -> clip
+    fp32[3] on the device (see `clip_coef`); `sgd_step_multi` / `adamw_step_multi` apply clip[1] as they read the gradients."""
+    return clip_coef(grad_sumsq(grads), max_norm)
+
+
+def _clip_arg(clip):
+    if clip is not None and _chk(clip, torch.float32, "clip").numel() != 3:
+        raise ValueError("clip is the fp32[3] device tensor of clip_coef")
+    return clip
+
+
+def sgd_step_multi(params, grads, momentum_bufs, lr, momentum=0.9, weight_decay=0.0, nesterov=True, first_step=False, clip=None):
+    """In place, ONE launch for all groups: `sgd_step` of every (param, grad, momentum_buf) with its own lr and weight_decay (a number, or one per
+    group) on the gradient times clip[1] (clip = None: as it is).  Bit-identical to `sgd_step` per group when clip[1] == 1 or clip is None."""
+    p, g, b = _seg_lists("sgd_step_multi", params, grads, momentum_bufs)
+    _O.sgd_step_multi(p, g, b, _per_segment(lr, len(p), "lr"), _per_segment(weight_decay, len(p), "weight_decay"), float(momentum), bool(nesterov),
+                      bool(first_step), _clip_arg(clip))
+
+
+def adamw_step_multi(params, grads, exp_avgs, exp_avg_sqs, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip=None):
+    """In place, ONE launch for all groups: `adamw_step` of every group with its own lr and weight_decay on the gradient times clip[1]; `step` counts
+    from 1.  Bit-identical to `adamw_step` per group when clip[1] == 1 or clip is None."""
+    p, g, m, v = _seg_lists("adamw_step_multi", params, grads, exp_avgs, exp_avg_sqs)
+    _O.adamw_step_multi(p, g, m, v, _per_segment(lr, len(p), "lr"), _per_segment(weight_decay, len(p), "weight_decay"), int(step), float(betas[0]),
+                        float(betas[1]), float(eps), _clip_arg(clip))
+
+
+def grad_accumulate(accs, grads, first=False):
+    """In place, one launch: acc = first ? grad : acc + grad for every pair of flat buffers (`first`: acc is not read)."""
+    a, g = _seg_lists("grad_accumulate", accs, grads)
+    _O.grad_accumulate(a, g, bool(first))
+
+
+def ema_update(emas, srcs, decay):
+    """In place, one launch: ema = ema * d + (1 - d) * src for every pair of flat buffers, in the operation order of ultralytics ModelEMA.update
+    (mul_, then add_ of the scaled source); d and 1 - d are each rounded to fp32 from the double `decay`."""
+    e, s = _seg_lists("ema_update", emas, srcs)
+    _O.ema_update(e, s, float(decay))
 
 
 def probiou_loss(pred, target, weight=None, target_scores_sum=1.0):

@@ -39,7 +39,13 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     (`_BranchStep`), with the one `step()` (`_Step`: forward_backward, DDP gradient average, optimiser step) that `DetectHead` uses too;
   * `pad_targets` / `OBBCriterion` / `DetectHead`: the criterion chain (csrc/criterion.hip) -- the host-side padding of the labels, v8OBBLoss from the
     head's logits to loss items and logit gradients without a host read (decode -> assigner -> fused loss), and the three levels of Detect / OBB
-    (box, class and angle branches over one ParamGroups) trained under it."""
+    (box, class and angle branches over one ParamGroups) trained under it;
+  * `clip_grad_norm` / `Schedule` / `ModelEMA` / `TrainerUpdate`: the update half of the trainer's iteration (csrc/trainupd.hip) -- the global
+    gradient-norm clip (max_norm 10) whose coefficient is produced and consumed on the device, the warm-up ramps of learning rate and momentum (the
+    bias group ramping DOWN from warmup_bias_lr) followed by the linear or cosine `lrf` decay, gradient accumulation up to the nominal batch size,
+    and the EMA of the weights AND the BatchNorm running statistics (`ParamGroups.buffers`), the model the trainer validates and saves.  One update
+    is a fixed handful of launches over the flat group buffers whatever the number of layers (accumulate, sum of squares, coefficient, step of all
+    three groups, EMA), none of which reads back to the host; `_Step.step(..., ni=, epoch=)` runs it when the module's `update` is set."""
 import math
 
 import torch
@@ -185,12 +191,24 @@ class BoxBranchStep:
 class ParamGroups:
     """The trainer's three optimiser groups (`param_group_of`: 0 = weights with decay, 1 = norm weights, 2 = biases; no decay in 1 and 2) as
     FlatOptimizers.  Layers `add` their initial tensors before `build()` allocates the flat buffers; afterwards `param[i]` / `grad[i]` are
-    views of them, so the layers' kernels write gradients straight into the groups' gradient buffers."""
+    views of them, so the layers' kernels write gradients straight into the groups' gradient buffers.  A fourth flat buffer, `buffers`, holds the
+    state that is no parameter (the BatchNorm running statistics, `add_buffer`): the EMA averages it with the weights, as the trainer's does."""
 
     def __init__(self, optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, betas=None):
         self.cfg = dict(name=optimizer, lr=lr, momentum=momentum, nesterov=nesterov, betas=betas)
         self.weight_decay = weight_decay
         self.items, self.opts, self.param, self.grad = [], None, None, None
+        self.buffer_items, self.buffers = [], None
+
+    def add_buffer(self, t, owner, attr):
+        """Register the fp32 tensor `t` = `owner.attr` as non-parameter state: `build()` moves its then-current value into the flat `buffers` and
+        rebinds `owner.attr` to the view, so whatever reads or `copy_`s `owner.attr` before or after `build()` keeps working."""
+        if self.opts is not None:
+            raise RuntimeError("ParamGroups.add_buffer after build()")
+        if getattr(owner, attr) is not t or t.dtype != torch.float32:
+            raise ValueError("ParamGroups.add_buffer: t must be the fp32 tensor owner.attr")
+        self.buffer_items.append((owner, attr))
+        return len(self.buffer_items) - 1
 
     def add(self, group, init):
         if self.opts is not None:
@@ -210,15 +228,42 @@ class ParamGroups:
             self.param.append(pv[g][nxt[g]]); self.grad.append(gv[g][nxt[g]])
             self.param[-1].copy_(t)
             nxt[g] += 1
+        cur = [getattr(owner, attr) for owner, attr in self.buffer_items]
+        self.buffers = torch.zeros(sum(t.numel() for t in cur), dtype=torch.float32, device=dev)
+        for (owner, attr), t, v in zip(self.buffer_items, cur, FlatOptimizer.views(self.buffers, [tuple(t.shape) for t in cur])):
+            v.copy_(t)
+            setattr(owner, attr, v)
         return self
 
     def flat_grads(self):
         return [o.grad for o in self.opts if o.n]
 
-    def step(self, lr=None):
-        for o in self.opts:
-            if o.n:
-                o.step(lr)
+    def step(self, lr=None, momentum=None, clip=None, grads=None):
+        """The optimiser step of all three groups in ONE launch (ops.sgd_step_multi / adamw_step_multi; bit-identical to `FlatOptimizer.step` per
+        group).  lr: None (each group's own), a number, or one per group (weights, norm weights, biases); momentum: None or this step's momentum
+        (AdamW: betas[0]), as the warm-up sets them; clip: the fp32[3] device tensor of `clip_grad_norm` (the gradients are read times clip[1]) or
+        None; grads: three flat buffers to step from in place of the groups' own (the accumulated gradients)."""
+        opts = self.opts
+        live = [o for o in opts if o.n]
+        if not live:
+            return
+        if len({o.steps for o in live}) != 1:
+            raise RuntimeError("ParamGroups.step: the groups' step counts differ (a group was stepped on its own)")
+        lrs = [o.lr for o in opts] if lr is None else [lr] * 3 if isinstance(lr, (int, float)) else list(lr)
+        if len(lrs) != 3:
+            raise ValueError("ParamGroups.step: lr is a number or one per group (3)")
+        grads = [o.grad for o in opts] if grads is None else list(grads)
+        for o in live:
+            o.steps += 1
+        o0 = live[0]
+        mu = o0.momentum if momentum is None else momentum
+        wds = [o.weight_decay for o in opts]
+        if o0.name == "SGD":
+            ops.sgd_step_multi([o.param for o in opts], grads, [o.state[0] for o in opts], lrs, mu, wds, o0.nesterov, first_step=o0.steps == 1, clip=clip)
+        else:
+            betas = o0.betas if momentum is None else (momentum, o0.betas[1])
+            ops.adamw_step_multi([o.param for o in opts], grads, [o.state[0] for o in opts], [o.state[1] for o in opts], o0.steps, lrs, betas, o0.eps, wds,
+                                 clip=clip)
 
 
 def wgrad_route(c1, c2):
@@ -259,7 +304,7 @@ def train_kernel_of(k, s, g, c1, c2):
 class _BNBlock:
     """What ConvBN, DWConvBN and StemConvBN share: a conv without bias -> BatchNorm2d (batch statistics, running statistics updated) [-> SiLU] over
     fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2; running statistics are buffers of the block, not
-    parameters).  `forward` is the subclass's `_conv_fwd`, then ops.bn_fwd_bf16; `backward` is ops.bn_bwd_bf16, then the subclass's `_conv_bwd`,
+    parameters: `groups.add_buffer`).  `forward` is the subclass's `_conv_fwd`, then ops.bn_fwd_bf16; `backward` is ops.bn_bwd_bf16, then the subclass's `_conv_bwd`,
     which writes dW and returns dx.  A subclass checks its weight's shape, names (c1, c2, k, s, act) and supplies the two conv halves."""
 
     def __init__(self, groups, w, gamma, beta, c1, c2, k, s, act, running_mean, running_var, eps, momentum):
@@ -271,6 +316,8 @@ class _BNBlock:
         self._ib = groups.add(2, beta if beta is not None else torch.zeros(c2, device=dev))
         self.running_mean = (running_mean.clone() if running_mean is not None else torch.zeros(c2, device=dev)).float().contiguous()
         self.running_var = (running_var.clone() if running_var is not None else torch.ones(c2, device=dev)).float().contiguous()
+        groups.add_buffer(self.running_mean, self, "running_mean")  # (after build(): views of groups.buffers)
+        groups.add_buffer(self.running_var, self, "running_var")
         self.saved = None
 
     w = property(lambda self: self.groups.param[self._iw])
@@ -785,12 +832,23 @@ class DetectAngleBranch(_Chain):
 
 class _Step:
     """step(*inputs, group=None) of a module with `forward_backward(*inputs)` and `groups`: forward + backward, the DDP gradient average over
-    `group` (no-op on one rank), the optimiser step -> what forward_backward returned."""
+    `group` (no-op on one rank), the optimiser step -> what forward_backward returned.  With `update` set (a `TrainerUpdate` over the same groups)
+    everything after the backward is the trainer's: step(*inputs, ni=, epoch=) hands it the iteration and epoch numbers, and `last_clip` keeps what
+    it returned (the clip tensor, or None between two optimiser steps of an accumulation)."""
+    update = None
 
-    def step(self, *inputs, group=None, **kw):
+    def step(self, *inputs, group=None, ni=None, epoch=None, **kw):
+        if self.update is None:
+            if ni is not None or epoch is not None:
+                raise TypeError("step: ni / epoch are the iteration and epoch of a TrainerUpdate, and `update` is not set")
+            out = self.forward_backward(*inputs, **kw)
+            allreduce_gradients(self.groups.flat_grads(), group)
+            self.groups.step()
+            return out
+        if ni is None or epoch is None:
+            raise TypeError("step: with `update` set, pass ni= and epoch= (the schedule needs them)")
         out = self.forward_backward(*inputs, **kw)
-        allreduce_gradients(self.groups.flat_grads(), group)
-        self.groups.step()
+        self.last_clip = self.update(ni, epoch, group=group)
         return out
 
 
@@ -928,3 +986,126 @@ class DetectHead(_Step):
         box, cls, angle = self.forward(feats)
         items, (d_box, d_cls, d_angle) = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
         return items, self.backward(d_box, d_cls, d_angle)
+
+
+def clip_grad_norm(groups_or_flat_grads, max_norm=10.0):
+    """`torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10.0)` of the trainer's optimizer_step over the flat gradient buffers (a
+    ParamGroups, or a list of flat fp32 tensors) in two launches -> clip fp32[3] ON THE DEVICE = (total_norm, coef, finite).  The gradients are
+    not scaled here: `ParamGroups.step(..., clip=clip)` multiplies by coef as it reads them.  Nothing is read back to the host."""
+    g = groups_or_flat_grads
+    return ops.clip_grad_norm(g.flat_grads() if hasattr(g, "flat_grads") else list(g), max_norm)
+
+
+class Schedule:
+    """The trainer's per-iteration learning rate, momentum and accumulation count (Ultralytics 8.3.x `BaseTrainer._setup_scheduler` and the
+    warm-up block of `_do_train`, restated from recall: the package is not installed, so this is UNPINNED like `optimizer_config`).  Host only,
+    in double.  nb = batches per epoch; ni = the global iteration (epoch * nb + batch index).
+        nw = max(round(warmup_epochs * nb), 100) warm-up iterations;  lf(x) = max(1 - x / epochs, 0) (1 - lrf) + lrf  (linear), or
+        lf(x) = lrf + (1 - lrf) (1 + cos(x pi / epochs)) / 2  (cos_lr; the trainer's ((1 - cos(x pi / epochs)) / 2) (lrf - 1) + 1 written so
+        that both end points are exact: lf(0) = 1, lf(epochs) = lrf);
+        ni <= nw:  lr = interp(ni, [0, nw], [warmup_bias_lr for the bias group else 0, lr0 lf(epoch)]), momentum = interp(ni, [0, nw],
+                   [warmup_momentum, momentum]), accumulate = max(1, round(interp(ni, [0, nw], [1, nbs / batch])));
+        after:     lr = lr0 lf(epoch) for every group, `momentum`, accumulate = max(1, round(nbs / batch)).
+    `at(ni, epoch)` -> {"lr": (weights, norm weights, biases) in ParamGroups' group order, "momentum", "accumulate"}; for AdamW the scheduled
+    momentum is betas[0] (`ParamGroups.step(momentum=)`).  Train_OBB.py:792-841 trains with lr0 = 0.003, lrf = 0.05."""
+
+    def __init__(self, epochs, nb, lr0, lrf=0.01, momentum=0.937, cos_lr=False, warmup_epochs=3.0, warmup_momentum=0.8, warmup_bias_lr=0.1, batch=16,
+                 nbs=64):
+        if epochs < 1 or nb < 1 or batch < 1:
+            raise ValueError("Schedule: epochs, nb and batch are at least 1")
+        self.epochs, self.nb, self.lr0, self.lrf, self.momentum, self.cos_lr = int(epochs), int(nb), float(lr0), float(lrf), float(momentum), bool(cos_lr)
+        self.warmup_momentum, self.warmup_bias_lr, self.batch, self.nbs = float(warmup_momentum), float(warmup_bias_lr), int(batch), int(nbs)
+        self.nw = max(round(warmup_epochs * nb), 100)
+
+    def lf(self, x):
+        if self.cos_lr:
+            return self.lrf + (1.0 - self.lrf) * ((1.0 + math.cos(x * math.pi / self.epochs)) / 2.0)
+        return max(1.0 - x / self.epochs, 0.0) * (1.0 - self.lrf) + self.lrf
+
+    def at(self, ni, epoch):
+        import numpy as np
+        base = self.lr0 * self.lf(epoch)
+        full = self.nbs / self.batch
+        if ni > self.nw:
+            return {"lr": (base, base, base), "momentum": self.momentum, "accumulate": max(1, round(full))}
+        xi = [0, self.nw]
+        lr = float(np.interp(ni, xi, [0.0, base]))
+        return {"lr": (lr, lr, float(np.interp(ni, xi, [self.warmup_bias_lr, base]))),
+                "momentum": float(np.interp(ni, xi, [self.warmup_momentum, self.momentum])),
+                "accumulate": max(1, round(float(np.interp(ni, xi, [1, full]))))}
+
+
+class ModelEMA:
+    """Ultralytics `ModelEMA(model, decay=0.9999, tau=2000)` over a built ParamGroups: flat copies of the three parameter buffers AND of `buffers`
+    (the BatchNorm running statistics: the trainer's EMA runs over the whole float state dict), averaged by ONE launch per `update()`
+    (ops.ema_update) with d = decay (1 - exp(-updates / tau)).  The EMA model is the one the trainer validates and saves: `with ema.applied():`
+    puts its values into the groups (and takes them out again), so every block's `fold()` inside the context is the EMA model's."""
+
+    def __init__(self, groups, decay=0.9999, tau=2000):
+        if groups.opts is None:
+            raise RuntimeError("ModelEMA: groups.build() first")
+        self.groups, self.decay, self.tau, self.updates = groups, float(decay), float(tau), 0
+        self.ema = [t.clone() for t in self.live()]
+
+    def live(self):
+        """the four flat buffers the EMA follows"""
+        return [o.param for o in self.groups.opts] + [self.groups.buffers]
+
+    def decay_at(self, updates):
+        return self.decay * (1.0 - math.exp(-updates / self.tau))
+
+    def update(self):
+        self.updates += 1
+        ops.ema_update(self.ema, self.live(), self.decay_at(self.updates))
+
+    def applied(self):
+        import contextlib
+
+        @contextlib.contextmanager
+        def swap():
+            live = self.live()
+            scratch = [t.clone() for t in live]
+            for t, e in zip(live, self.ema):
+                t.copy_(e)
+            try:
+                yield self
+            finally:
+                for t, s in zip(live, scratch):
+                    t.copy_(s)
+        return swap()
+
+
+class TrainerUpdate:
+    """Everything the trainer does between `loss.backward()` and the next forward (Ultralytics 8.3.x `_do_train` / `optimizer_step`, restated from
+    recall, UNPINNED like `Schedule`), on a built ParamGroups whose gradient buffers the backward has just written:
+        the schedule's lr / momentum / accumulate at (ni, epoch);  accumulate > 1: the gradients are added into accumulation buffers;
+        when ni - last_opt_step >= accumulate:  DDP gradient average of the buffers being stepped -> `clip_grad_norm` (max_norm 10) ->
+        `groups.step(lr, momentum, clip)` -> `ema.update()`.
+    __call__(ni, epoch, group=None) -> the clip tensor (fp32[3] on the device) at an optimiser step, None between two.  A fixed number of launches
+    per update whatever the number of layers (accumulate 1, sumsq 1, coefficient 1, step 1, EMA 1), and no host read.  `last_opt_step` starts at -1
+    as the trainer's; set it when resuming."""
+
+    def __init__(self, groups, schedule, max_norm=10.0, ema=None):
+        if groups.opts is None:
+            raise RuntimeError("TrainerUpdate: groups.build() first")
+        self.groups, self.schedule, self.max_norm, self.ema = groups, schedule, float(max_norm), ema
+        self.last_opt_step, self.acc, self.n_acc = -1, None, 0
+
+    def __call__(self, ni, epoch, group=None):
+        s = self.schedule.at(ni, epoch)
+        grads = [o.grad for o in self.groups.opts]
+        if s["accumulate"] > 1 or self.n_acc:
+            if self.acc is None:
+                self.acc = [torch.empty_like(g) for g in grads]
+            ops.grad_accumulate(self.acc, grads, first=self.n_acc == 0)
+            self.n_acc += 1
+            grads = self.acc
+        if ni - self.last_opt_step < s["accumulate"]:
+            return None
+        allreduce_gradients([g for g in grads if g.numel()], group)
+        clip = clip_grad_norm(grads, self.max_norm)
+        self.groups.step(s["lr"], s["momentum"], clip, grads=grads)
+        if self.ema is not None:
+            self.ema.update()
+        self.last_opt_step, self.n_acc = ni, 0
+        return clip
