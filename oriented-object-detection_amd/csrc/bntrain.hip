@@ -7,53 +7,29 @@
 //   backward  xhat = (z - mean) invstd, y = gamma xhat + beta recomputed from z (no normalised tensor is stored);  g = da silu'(y)
 //             dbeta = sum g,  dgamma = sum g xhat,  dz = gamma invstd (g - dbeta / N - xhat dgamma / N), rounded to bf16 once
 //
-// Reductions (deterministic, no float atomics -- the rule of convgrad.hip): the pixel dimension is split into nbx contiguous blocks, one
+// Reductions (deterministic, no float atomics -- the two passes of traindev.h): the pixel dimension is split into nbx contiguous blocks, one
 // workgroup per (pixel block, 256-channel group); a thread owns 8 channels (one 16-byte load per pixel) and every RP-th pixel of the block,
-// its partial sums meet in LDS and are added in a fixed pairwise tree over the rows.  The per-block results go to an fp32 slab [nbx][C]; a second kernel combines the
-// slab in a fixed order (64 strided walkers per channel, then a pairwise tree: walker w takes in walker w + s for s = 32, 16, .., 1).
+// its partial sums meet in LDS in lds_row_tree.  The per-block results go to an fp32 slab [nbx][C]; a second kernel combines the slab in
+// slab_combine's order (64 strided walkers per channel, then their pairwise tree).
 // The forward's slab holds (mean, M2) pairs of each block -- the block's mean first, then the sum of squares about it, read back from
 // cache -- combined with Chan's parallel formula, so the variance never comes from E[z^2] - E[z]^2 (which cancels catastrophically when
 // |mean| >> std).  Every statistic is taken of z - z[pixel 0] (per channel; exact in fp32): the block means and the deviations between them
 // that Chan's formula squares are then of the size of std, not of |mean| -- without the shift, the fp32 spacing of a mean of 8 (4.8e-7) made
-// the variance of a std-0.05 channel wrong by 3e-6 relative.  The backward's slab holds plain sums.  Both directions share the geometry (bn_geo) and the LDS reduction (block_reduce8).
+// the variance of a std-0.05 channel wrong by 3e-6 relative (k_bn_stats_final: slab_combine's walkers and tree with chan_add as the operator,
+// written out).  The backward's slab holds plain sums.  Both directions share the geometry (bn_geo) and the LDS reduction (block_reduce8).
 #include <algorithm>
 
 #include "ctx.h"
+#include "traindev.h"
 
 namespace obb {
 namespace {  // helpers; the kernels below keep plain obb:: names for the traces
 
-__device__ __forceinline__ float bn_from_bf16(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short bn_to_bf16(float f) {  // round to nearest even (host_to_bf16's bit arithmetic)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ void unpack8(const uint4 v, float f[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(w[j] << 16); f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 pack8(const float f[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (unsigned)bn_to_bf16(f[2 * j]) | ((unsigned)bn_to_bf16(f[2 * j + 1]) << 16);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-__device__ __forceinline__ float silu_f(float y) { return y / (1.0f + expf(-y)); }
-
-constexpr int kGroupChunks = 32;  // 16-byte channel chunks per workgroup column group (256 channels)
-constexpr int kWalkers = 64;      // strided walkers per channel in the slab-combining kernels (x 4 channels = 256 threads)
-constexpr int kWalkCh = 256 / kWalkers;
-
 // Work split of the partial-sum kernels: CW chunk columns x RP pixel rows of threads, nbx pixel blocks of PB pixels
-struct BnGeo { int C8, CW, RP, ny, nbx; int64_t PB; };
+struct BnGeo : RowSplit { int nbx; int64_t PB; };
 BnGeo bn_geo(int64_t npix, int C) {
     BnGeo g;
-    g.C8 = C / 8;
-    g.CW = std::min(g.C8, kGroupChunks);
-    g.RP = 256 / g.CW;
-    g.ny = (g.C8 + kGroupChunks - 1) / kGroupChunks;
+    static_cast<RowSplit &>(g) = row_split(C);
     const int64_t want = std::max(1, 1024 / g.ny);  // ~1024 workgroups: four per CU
     const int64_t nbx = std::min<int64_t>(cdiv(npix, g.RP), want);
     g.PB = cdiv(cdiv(npix, nbx), g.RP) * g.RP;
@@ -61,28 +37,16 @@ BnGeo bn_geo(int64_t npix, int C) {
     return g;
 }
 
-// Sums the 8 per-thread values s[] over the RP rows of the workgroup in a fixed pairwise tree (row r takes in row r + st for st = 128, .., 1;
-// RP need not be a power of two); thread t < CW*8 gets channel chunk t / 8, lane t % 8.  (A serial walk over the rows was a 256-term fp32 chain
-// at C = 8: 2e-6 of the variance of a mean-8, std-0.05 channel.)  red: 256 * 8 floats of LDS.  Returns the sum for threads t < CW*8 (0
-// elsewhere).  Ends with every thread past a barrier.
+// Sums the 8 per-thread values s[] over the RP rows of the workgroup in the fixed pairwise tree (lds_row_tree); thread t < CW*8 gets channel
+// chunk t / 8, lane t % 8.  (A serial walk over the rows was a 256-term fp32 chain at C = 8: 2e-6 of the variance of a mean-8, std-0.05
+// channel.)  red: 256 * 8 floats of LDS.  Returns the sum for threads t < CW*8 (0 elsewhere).  Ends with every thread past a barrier.
 __device__ __forceinline__ float block_reduce8(float *red, const float s[8], int row, int col, int CW, int RP) {
     float4 *r4 = reinterpret_cast<float4 *>(red + (row * CW + col) * 8);
     if (row < RP) {
         r4[0] = make_float4(s[0], s[1], s[2], s[3]);
         r4[1] = make_float4(s[4], s[5], s[6], s[7]);
     }
-    int st = 1;
-    while (st < RP) st <<= 1;
-    for (st >>= 1; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (row < st && row + st < RP) {
-            const float4 *o4 = reinterpret_cast<const float4 *>(red + ((row + st) * CW + col) * 8);
-            const float4 a0 = r4[0], a1 = r4[1], b0 = o4[0], b1 = o4[1];
-            r4[0] = make_float4(a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w);
-            r4[1] = make_float4(a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w);
-        }
-    }
-    __syncthreads();
+    lds_row_tree<8>(red, 0, row, col, CW, RP);
     const float t = (int)threadIdx.x < CW * 8 ? red[threadIdx.x] : 0.f;
     __syncthreads();
     return t;
@@ -111,10 +75,10 @@ __global__ __launch_bounds__(256) void k_bn_stats_part(const unsigned short *__r
     const int64_t p0 = (int64_t)blockIdx.x * PB, p1 = min(p0 + PB, npix);
     const float inv_n = 1.0f / (float)(p1 - p0);
     float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8], k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (act) unpack8(*reinterpret_cast<const uint4 *>(z + c8 * 8), k);  // the shift: pixel 0's value
+    if (act) unpack8_bf16(*reinterpret_cast<const uint4 *>(z + c8 * 8), k);  // the shift: pixel 0's value
     if (act)
         for (int64_t p = p0 + row; p < p1; p += RP) {
-            unpack8(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
+            unpack8_bf16(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) s[j] += v[j] - k[j];
         }
@@ -126,7 +90,7 @@ __global__ __launch_bounds__(256) void k_bn_stats_part(const unsigned short *__r
     for (int j = 0; j < 8; ++j) { m[j] = bmean[col * 8 + j]; s[j] = 0.f; }
     if (act)  // the block was just read: this pass is served by the caches
         for (int64_t p = p0 + row; p < p1; p += RP) {
-            unpack8(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
+            unpack8_bf16(*reinterpret_cast<const uint4 *>(z + p * C + c8 * 8), v);
 #pragma unroll
             for (int j = 0; j < 8; ++j) { const float d = (v[j] - k[j]) - m[j]; s[j] += d * d; }
         }
@@ -139,14 +103,14 @@ __global__ __launch_bounds__(256) void k_bn_stats_part(const unsigned short *__r
 __global__ __launch_bounds__(256) void k_bn_stats_final(const unsigned short *__restrict__ z, const float *__restrict__ slab_mean, const float *__restrict__ slab_m2, int nbx,
                                                         int64_t PB, int64_t npix, int C, float eps, float momentum, float *__restrict__ running_mean, float *__restrict__ running_var,
                                                         float *__restrict__ mean, float *__restrict__ invstd) {
-    __shared__ float sn[kWalkers][kWalkCh], smu[kWalkers][kWalkCh], sm2[kWalkers][kWalkCh];
-    const int cl = threadIdx.x % kWalkCh, w = threadIdx.x / kWalkCh, c = blockIdx.x * kWalkCh + cl;
+    __shared__ float sn[kSlabWalkers][kSlabWalkEl], smu[kSlabWalkers][kSlabWalkEl], sm2[kSlabWalkers][kSlabWalkEl];
+    const int cl = threadIdx.x % kSlabWalkEl, w = threadIdx.x / kSlabWalkEl, c = blockIdx.x * kSlabWalkEl + cl;
     float n = 0.f, mu = 0.f, m2 = 0.f;
     if (c < C)
-        for (int b = w; b < nbx; b += kWalkers)
+        for (int b = w; b < nbx; b += kSlabWalkers)
             chan_add(n, mu, m2, (float)min(PB, npix - (int64_t)b * PB), slab_mean[(size_t)b * C + c], slab_m2[(size_t)b * C + c]);
     sn[w][cl] = n; smu[w][cl] = mu; sm2[w][cl] = m2;
-    for (int st = kWalkers / 2; st >= 1; st >>= 1) {
+    for (int st = kSlabWalkers / 2; st >= 1; st >>= 1) {
         __syncthreads();
         if (w < st) {
             chan_add(n, mu, m2, sn[w + st][cl], smu[w + st][cl], sm2[w + st][cl]);
@@ -154,7 +118,7 @@ __global__ __launch_bounds__(256) void k_bn_stats_final(const unsigned short *__
         }
     }
     if (w != 0 || c >= C) return;
-    const float N = (float)npix, var = m2 / N, mc = bn_from_bf16(z[c]) + mu;
+    const float N = (float)npix, var = m2 / N, mc = bf16_widen(z[c]) + mu;
     mean[c] = mc;
     invstd[c] = 1.0f / sqrtf(var + eps);
     running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mc;
@@ -169,13 +133,13 @@ __global__ __launch_bounds__(256) void k_bn_silu_apply(const unsigned short *__r
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * 256) {
         const int c0 = (int)(i % C8) * 8;
         float v[8];
-        unpack8(reinterpret_cast<const uint4 *>(z)[i], v);
+        unpack8_bf16(reinterpret_cast<const uint4 *>(z)[i], v);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float y = gamma[c0 + j] * ((v[j] - mean[c0 + j]) * invstd[c0 + j]) + beta[c0 + j];
-            v[j] = ACT ? silu_f(y) : y;
+            v[j] = ACT ? silu_exact(y) : y;
         }
-        reinterpret_cast<uint4 *>(a)[i] = pack8(v);
+        reinterpret_cast<uint4 *>(a)[i] = pack8_bf16(v);
     }
 }
 
@@ -184,17 +148,12 @@ template <bool ACT>
 __device__ __forceinline__ void bn_bwd_terms(const uint4 zv, const uint4 dav, const float ga[8], const float be[8], const float mu[8], const float is[8],
                                              float g[8], float xh[8]) {
     float zf[8], df[8];
-    unpack8(zv, zf);
-    unpack8(dav, df);
+    unpack8_bf16(zv, zf);
+    unpack8_bf16(dav, df);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         xh[j] = (zf[j] - mu[j]) * is[j];
-        if (ACT) {
-            const float y = ga[j] * xh[j] + be[j], sg = 1.0f / (1.0f + expf(-y));
-            g[j] = df[j] * (sg * (1.0f + y * (1.0f - sg)));
-        } else {
-            g[j] = df[j];
-        }
+        g[j] = ACT ? df[j] * silu_grad_exact(ga[j] * xh[j] + be[j]) : df[j];
     }
 }
 
@@ -230,19 +189,11 @@ __global__ __launch_bounds__(256) void k_bn_bwd_part(const unsigned short *__res
 // backward, pass 2: dbeta = sum of the slab rows of g, dgamma = the same of g xhat (walkers, then the tree)
 __global__ __launch_bounds__(256) void k_bn_bwd_final(const float *__restrict__ slab_g, const float *__restrict__ slab_gx, int nbx, int C, float *__restrict__ dgamma,
                                                       float *__restrict__ dbeta) {
-    __shared__ float sg[kWalkers][kWalkCh], sgx[kWalkers][kWalkCh];
-    const int cl = threadIdx.x % kWalkCh, w = threadIdx.x / kWalkCh, c = blockIdx.x * kWalkCh + cl;
-    float a = 0.f, b = 0.f;
-    if (c < C)
-        for (int k = w; k < nbx; k += kWalkers) { a += slab_g[(size_t)k * C + c]; b += slab_gx[(size_t)k * C + c]; }
-    sg[w][cl] = a; sgx[w][cl] = b;
-    for (int st = kWalkers / 2; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (w < st) { a += sg[w + st][cl]; b += sgx[w + st][cl]; sg[w][cl] = a; sgx[w][cl] = b; }
-    }
-    if (w != 0 || c >= C) return;
-    dbeta[c] = a;
-    dgamma[c] = b;
+    const int c = slab_elem();
+    float a[2];
+    if (!slab_combine<2>({slab_g, slab_gx}, nbx, C, c, a)) return;
+    dbeta[c] = a[0];
+    dgamma[c] = a[1];
 }
 
 // backward, pass 3: dz = gamma invstd (g - dbeta / N - xhat dgamma / N)
@@ -259,7 +210,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const unsigned short *__re
         bn_bwd_terms<ACT>(reinterpret_cast<const uint4 *>(z)[i], reinterpret_cast<const uint4 *>(da)[i], ga, be, mu, is, g, xh);
 #pragma unroll
         for (int j = 0; j < 8; ++j) g[j] = ga[j] * is[j] * (g[j] - dbeta[c0 + j] * inv_n - xh[j] * (dgamma[c0 + j] * inv_n));
-        reinterpret_cast<uint4 *>(dz)[i] = pack8(g);
+        reinterpret_cast<uint4 *>(dz)[i] = pack8_bf16(g);
     }
 }
 
@@ -282,7 +233,7 @@ static int bn_fwd_impl(obb_ctx *ctx, const char *fn, bool act, const uint16_t *z
     if (!slab) return set_error(ctx, OBB_ERR_HIP, "%s: workspace allocation failed", fn);
     float *slab_m2 = slab + (size_t)g.nbx * C;
     hipLaunchKernelGGL(k_bn_stats_part, dim3((unsigned)g.nbx, (unsigned)g.ny), dim3(256), 0, st, z, npix, (int)C, g.PB, g.CW, g.RP, slab, slab_m2);
-    hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, z, slab, slab_m2, g.nbx, g.PB, npix, (int)C, eps, momentum, running_mean,
+    hipLaunchKernelGGL(k_bn_stats_final, dim3((unsigned)cdiv(C, kSlabWalkEl)), dim3(256), 0, st, z, slab, slab_m2, g.nbx, g.PB, npix, (int)C, eps, momentum, running_mean,
                        running_var, mean, invstd);
     const int64_t nchunk = npix * g.C8;
     if (act)
@@ -308,7 +259,7 @@ static int bn_bwd_impl(obb_ctx *ctx, const char *fn, bool act, const uint16_t *z
         hipLaunchKernelGGL(k_bn_bwd_part<true>, pgrid, dim3(256), 0, st, z, da, npix, (int)C, g.PB, g.CW, g.RP, gamma, beta, mean, invstd, slab, slab_gx);
     else
         hipLaunchKernelGGL(k_bn_bwd_part<false>, pgrid, dim3(256), 0, st, z, da, npix, (int)C, g.PB, g.CW, g.RP, gamma, beta, mean, invstd, slab, slab_gx);
-    hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)cdiv(C, kWalkCh)), dim3(256), 0, st, slab, slab_gx, g.nbx, (int)C, dgamma, dbeta);
+    hipLaunchKernelGGL(k_bn_bwd_final, dim3((unsigned)cdiv(C, kSlabWalkEl)), dim3(256), 0, st, slab, slab_gx, g.nbx, (int)C, dgamma, dbeta);
     const int64_t nchunk = npix * g.C8;
     const float inv_n = 1.0f / (float)npix;
     if (act)

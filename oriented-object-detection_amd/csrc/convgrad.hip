@@ -31,12 +31,11 @@
 #include "conv.h"
 #include "ctx.h"
 #include "launchcfg.h"
+#include "traindev.h"
 
 namespace obb {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4g;
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }
 
 // One workgroup = 4 waves = one (cout block, cin block) pair of dW for all KS*KS taps.  Channel blocks are ceil(c / 64) per side; the last block
 // of a side holds c % 64 live channels (8 .. 56).  A tile of the input = R rows x W pixels of one image: dY rows padded with zeros to a multiple
@@ -105,11 +104,11 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__rest
                     const int xg = xs * 4 + g;
                     float a[NCF];
 #pragma unroll
-                    for (int c = 0; c < NCF; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
+                    for (int c = 0; c < NCF; ++c) a[c] = bf16_widen(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
 #pragma unroll
                     for (int t = 0; t < TAPS; ++t) {
                         const int ky = t / KS, kx = t % KS;
-                        const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
+                        const float bv = bf16_widen(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
 #pragma unroll
                         for (int c = 0; c < NCF; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
                     }
@@ -121,11 +120,11 @@ __global__ __launch_bounds__(256) void k_conv_wgrad(const unsigned short *__rest
                 const int xg = xs * 4 + g;
                 float a[NCF];
 #pragma unroll
-                for (int c = 0; c < NCF; ++c) a[c] = bf16_to_f32(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
+                for (int c = 0; c < NCF; ++c) a[c] = bf16_widen(sdy[((size_t)ry * Wp + xg) * COW + c * 16 + r16]);
 #pragma unroll
                 for (int t = 0; t < TAPS; ++t) {
                     const int ky = t / KS, kx = t % KS;
-                    const float bv = bf16_to_f32(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
+                    const float bv = bf16_widen(sx[((size_t)(ry * S + ky) * Wx + xg * S + kx) * CIW + frag * 16 + r16]);
 #pragma unroll
                     for (int c = 0; c < NCF; ++c) acc[c][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], bv, acc[c][t], 0, 0, 0);
                 }
@@ -181,14 +180,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ 
 }
 
 // ---- assembled-chain pieces (round 4): device-side weight packing (no per-call host repack / synchronisation), the training forward that keeps
-//      the pre-activation, SiLU forward / backward, bias gradient
-// bf16 round-to-nearest-even of an fp32 value (host_to_bf16's bit arithmetic)
-__device__ __forceinline__ unsigned short dev_to_bf16(float f) {
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float dev_from_bf16(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+//      the pre-activation, SiLU forward / backward, bias gradient (bf16 rounding and the exact SiLU: traindev.h)
 
 // fp32 OIHW master weights (device) -> the forward kernel's bf16 A-operand fragment order [cout block][stage][k step][fragment][lane][8]
 // (pack_conv_weights' index arithmetic, element for element).  tflip = 1: the dgrad form -- the logical conv has the channel roles swapped and
@@ -212,31 +204,27 @@ __global__ __launch_bounds__(256) void k_pack_conv_bf16(const float *__restrict_
     float v = 0.f;
     if (co < coutL && c < cinL && tap < taps && (ks == 3 || c0 < CK))
         v = tflip ? w[((size_t)c * coutL + co) * taps + (taps - 1 - tap)] : w[((size_t)co * cinL + c) * taps + tap];
-    out[o] = dev_to_bf16(v);
+    out[o] = bf16_rne(v);
 }
 
 __global__ __launch_bounds__(256) void k_silu_bf16(const unsigned short *__restrict__ z, unsigned short *__restrict__ a, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = dev_from_bf16(z[i]);
-    a[i] = dev_to_bf16(x / (1.0f + expf(-x)));
+    a[i] = bf16_rne(silu_exact(bf16_widen(z[i])));
 }
 
 // dz = da * silu'(z), silu'(z) = s (1 + z (1 - s)), s = sigmoid(z): what autograd computes for x * sigmoid(x); bf16 in / out, fp32 inside
 __global__ __launch_bounds__(256) void k_silu_bwd_bf16(const unsigned short *__restrict__ z, const unsigned short *__restrict__ da, unsigned short *__restrict__ dz, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const float x = dev_from_bf16(z[i]), g = dev_from_bf16(da[i]);
-    const float sg = 1.0f / (1.0f + expf(-x));
-    dz[i] = dev_to_bf16(g * (sg * (1.0f + x * (1.0f - sg))));
+    dz[i] = bf16_rne(bf16_widen(da[i]) * silu_grad_exact(bf16_widen(z[i])));
 }
 
-// db[c] = sum over the pixels of dy[pixel][c], deterministic in a fixed order (bntrain.hip's slab pattern): pass 1 = one workgroup per (pixel
+// db[c] = sum over the pixels of dy[pixel][c], deterministic in a fixed order (traindev.h's slab pattern): pass 1 = one workgroup per (pixel
 // block of PB pixels, 64-channel column block), 4 thread rows each summing every 4th pixel of the block in fp32, the rows added in a fixed tree,
-// one partial per (block, channel) into the slab [nbx][cout]; pass 2 = kBgWalkers strided walkers per channel over the slab, then a pairwise
-// tree.  Partial sums stay small (PB / 4 terms per thread), so no bf16 value is lost against a large running sum -- the old form (4 threads per
-// channel walking all npix / 4 pixels serially) reached 6e-6 of sum |dy| at 64 x 104 x 104 pixels.
-constexpr int kBgWalkers = 64, kBgWalkCh = 256 / kBgWalkers;
+// one partial per (block, channel) into the slab [nbx][cout]; pass 2 = slab_combine.  Partial sums stay small (PB / 4 terms per thread), so no
+// bf16 value is lost against a large running sum -- the old form (4 threads per channel walking all npix / 4 pixels serially) reached 6e-6 of
+// sum |dy| at 64 x 104 x 104 pixels.
 
 __global__ __launch_bounds__(256) void k_bias_grad_part(const unsigned short *__restrict__ dy, int64_t npix, int cout, int64_t PB, float *__restrict__ slab) {
     __shared__ float part[4][64];
@@ -244,24 +232,16 @@ __global__ __launch_bounds__(256) void k_bias_grad_part(const unsigned short *__
     const int64_t p0 = (int64_t)blockIdx.x * PB, p1 = min(p0 + PB, npix);
     float s = 0.f;
     if (c < cout)
-        for (int64_t p = p0 + rowg; p < p1; p += 4) s += dev_from_bf16(dy[p * cout + c]);
+        for (int64_t p = p0 + rowg; p < p1; p += 4) s += bf16_widen(dy[p * cout + c]);
     part[rowg][threadIdx.x & 63] = s;
     __syncthreads();
     if (rowg == 0 && c < cout) slab[(size_t)blockIdx.x * cout + c] = (part[0][threadIdx.x] + part[1][threadIdx.x]) + (part[2][threadIdx.x] + part[3][threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void k_bias_grad_final(const float *__restrict__ slab, int nbx, int cout, float *__restrict__ db) {
-    __shared__ float sp[kBgWalkers][kBgWalkCh];
-    const int cl = threadIdx.x % kBgWalkCh, w = threadIdx.x / kBgWalkCh, c = blockIdx.x * kBgWalkCh + cl;
-    float a = 0.f;
-    if (c < cout)
-        for (int k = w; k < nbx; k += kBgWalkers) a += slab[(size_t)k * cout + c];
-    sp[w][cl] = a;
-    for (int st = kBgWalkers / 2; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (w < st) { a += sp[w + st][cl]; sp[w][cl] = a; }
-    }
-    if (w == 0 && c < cout) db[c] = a;
+    const int c = slab_elem();
+    float a[1];
+    if (slab_combine<1>({slab}, nbx, cout, c, a)) db[c] = a[0];
 }
 
 // dY bf16 [B][Ho][Wo][C] -> dY_up [B][H][W][C]: dY[i][j] at (2i, 2j), zeros elsewhere; one 16-byte chunk per thread and step
@@ -541,7 +521,7 @@ int obb_bias_grad_bf16(obb_ctx *ctx, const uint16_t *dy, int64_t npix, int32_t c
     float *slab = (float *)ctx->workspace(WS_TRAIN_F, (size_t)nbx * cout * 4);
     if (!slab) return set_error(ctx, OBB_ERR_HIP, "obb_bias_grad_bf16: workspace allocation failed");
     hipLaunchKernelGGL(k_bias_grad_part, dim3((unsigned)nbx, (unsigned)ncb), dim3(256), 0, st, dy, npix, (int)cout, PB, slab);
-    hipLaunchKernelGGL(k_bias_grad_final, dim3((unsigned)cdiv(cout, kBgWalkCh)), dim3(256), 0, st, slab, nbx, (int)cout, db);
+    hipLaunchKernelGGL(k_bias_grad_final, dim3((unsigned)cdiv(cout, kSlabWalkEl)), dim3(256), 0, st, slab, nbx, (int)cout, db);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }

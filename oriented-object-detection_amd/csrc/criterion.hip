@@ -16,6 +16,7 @@
 // loss kernel reads it through the pointer, so nothing returns to the host and the whole criterion is stream-ordered and capturable.
 #include "ctx.h"
 #include "loss_device.h"
+#include "traindev.h"
 
 namespace obb {
 
@@ -34,12 +35,6 @@ struct CritLevels {
     int a0, a1, A;                   // anchors of level 0, of levels 0 + 1, of all three
 };
 
-__device__ __forceinline__ unsigned short crit_to_bf16(float f) {  // round to nearest even (dwgrad.hip's)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-
 template <typename TB>
 __device__ __forceinline__ void crit_load_side(const void *base, int64_t row, int side, float (&x)[kCritReg]);
 template <>
@@ -55,15 +50,7 @@ template <>
 __device__ __forceinline__ void crit_load_side<unsigned short>(const void *base, int64_t row, int side, float (&x)[kCritReg]) {
     const uint4 *p = reinterpret_cast<const uint4 *>(reinterpret_cast<const unsigned short *>(base) + row * 64 + side * kCritReg);
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint4 v = p[k];
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x[8 * k + 2 * j] = __uint_as_float(w[j] << 16);
-            x[8 * k + 2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-        }
-    }
+    for (int k = 0; k < 2; ++k) unpack8_bf16(p[k], x + 8 * k);
 }
 
 // where an (image, anchor) lives: its level, its row in the level's [B*H*W] tensors, its anchor point and stride
@@ -196,12 +183,9 @@ __global__ __launch_bounds__(256) void k_crit_loss(CritLevels L, int B, int nc, 
     }
     ldfl = ((__shfl(ldfl, 0, 4) + __shfl(ldfl, 1, 4)) + __shfl(ldfl, 2, 4)) + __shfl(ldfl, 3, 4);
     if (!live) return;
-    unsigned w[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = (unsigned)crit_to_bf16(g[2 * k]) | ((unsigned)crit_to_bf16(g[2 * k + 1]) << 16);
     uint4 *o = reinterpret_cast<uint4 *>(reinterpret_cast<unsigned short *>(CRIT_PICK(L, d_box, an.lv)) + an.row * 64 + side * kCritReg);
-    o[0] = make_uint4(w[0], w[1], w[2], w[3]);
-    o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    o[0] = pack8_bf16(g);  // traindev.h's rounding
+    o[1] = pack8_bf16(g + 8);
     if (side == 0) {
         CRIT_PICK(L, d_ang, an.lv)[an.row] = dang;
         elem[q] = lbox; elem[n + q] = lcls; elem[2 * n + q] = ldfl;

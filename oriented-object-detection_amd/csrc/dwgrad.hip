@@ -14,46 +14,28 @@
 // dz window (dx: the flipped taps; dw: the window times the centre x), so the fused backward loads 3 dz chunks + 1 x chunk per pixel -- each of
 // x and dz comes from HBM once, the column neighbours and the stripe halo (2 rows per R) from the caches.
 // dw: a lane keeps 9 x 8 fp32 sums over its runs (`iters` of them once the run count exceeds kDwMaxSlabs workgroups' worth).  A workgroup is CW
-// chunk columns x RP run rows of lanes (bntrain.hip's layout); the RP lanes of a chunk meet in LDS in a fixed pairwise tree (row r takes in row
-// r + st, st = 128 .. 1), three taps per pass (24 KiB).  Workgroup bx writes its partial to the fp32 slab [bx][9][C] (WS_TRAIN_E, never read
-// before it is written: growing the slot changes nothing); k_dw_final adds the slabs in index order (64 strided walkers per element, then a
-// pairwise tree).  No atomics: bit-reproducible.  Longest fp32 addition chain of a dw element: L = R iters + ceil(log2 RP) + ceil(nbx / 64) + 6.
+// chunk columns x RP run rows of lanes (traindev.h's row_split); the RP lanes of a chunk meet in LDS in lds_row_tree, three tap planes per pass
+// under one barrier per step (24 KiB).  Workgroup bx writes its partial to the fp32 slab [bx][9][C] (WS_TRAIN_E, never read before it is
+// written: growing the slot changes nothing); k_dw_final adds the slabs in slab_combine's order.  No atomics: bit-reproducible.  Longest fp32
+// addition chain of a dw element: L = R iters + ceil(log2 RP) + slab_chain(nbx) (= ceil(nbx / 64) + 6).
 #include <algorithm>
 
 #include "ctx.h"
+#include "traindev.h"
 
 namespace obb {
 namespace {
 
-constexpr int kDwGroupChunks = 32;  // channel chunks per workgroup column group (256 channels)
 constexpr int kDwMaxSlabs = 512;    // workgroups per column group at most: beyond, a lane walks several runs
-constexpr int kDwWalkers = 64;      // strided walkers per element in k_dw_final (x 4 elements = 256 threads)
-constexpr int kDwWalkEl = 256 / kDwWalkers;
 constexpr int kDwTapsPerPass = 3;   // taps reduced per LDS pass: 3 x 256 x 8 floats = 24 KiB
 
-__device__ __forceinline__ unsigned short dw_to_bf16(float f) {  // round to nearest even (bntrain.hip's)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ void dw_unpack8(const uint4 v, float f[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(w[j] << 16); f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 dw_pack8(const float f[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (unsigned)dw_to_bf16(f[2 * j]) | ((unsigned)dw_to_bf16(f[2 * j + 1]) << 16);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
 // the 72 weights of channel chunk c8 -> wt[tap][lane channel], rounded to bf16
 __device__ __forceinline__ void dw_load_weights(const float *__restrict__ w, int c8, float wt[9][8]) {
     const float *wc = w + (size_t)c8 * 72;
 #pragma unroll
     for (int k = 0; k < 8; ++k)
 #pragma unroll
-        for (int t = 0; t < 9; ++t) wt[t][k] = __uint_as_float((unsigned)dw_to_bf16(wc[k * 9 + t]) << 16);
+        for (int t = 0; t < 9; ++t) wt[t][k] = bf16_round(wc[k * 9 + t]);
 }
 // row `i` of the window: columns j - 1, j, j + 1 of image row i (zero outside the map); img: the image's first element, chunk offset included
 __device__ __forceinline__ void dw_load_row(const unsigned short *__restrict__ img, int i, int j, int H, int W, int C, uint4 r[3]) {
@@ -67,22 +49,16 @@ __device__ __forceinline__ void dw_load_row(const unsigned short *__restrict__ i
 }
 
 // Work split of the backward (and the stripes of the forward)
-struct DwGeo { int C8, CW, RP, ny, R, ns, nbx, iters, L; int64_t P; };
+struct DwGeo : RowSplit { int R, ns, nbx, iters, L; int64_t P; };
 DwGeo dw_geo(int B, int H, int W, int C) {
     DwGeo g;
-    g.C8 = C / 8;
-    g.CW = std::min(g.C8, kDwGroupChunks);
-    g.RP = 256 / g.CW;
-    g.ny = (g.C8 + kDwGroupChunks - 1) / kDwGroupChunks;
+    static_cast<RowSplit &>(g) = row_split(C);
     g.R = H > 16 ? 4 : 2;
     g.ns = (int)cdiv(H, g.R);
     g.P = (int64_t)B * g.ns * W;                                        // runs
     g.nbx = (int)std::min<int64_t>(cdiv(g.P, g.RP), kDwMaxSlabs);       // workgroups per column group = slabs
     g.iters = (int)std::min<int64_t>(cdiv(g.P, (int64_t)g.nbx * g.RP), 1 << 30);  // runs per lane
-    int depth = 0;
-    while ((1 << depth) < g.RP) ++depth;
-    const int64_t L = (int64_t)g.R * g.iters + depth + cdiv(g.nbx, kDwWalkers) + 6;
-    g.L = (int)std::min<int64_t>(L, INT32_MAX);
+    g.L = (int)std::min<int64_t>((int64_t)g.R * g.iters + g.depth + slab_chain(g.nbx), INT32_MAX);
     return g;
 }
 
@@ -117,11 +93,11 @@ __global__ __launch_bounds__(256) void k_dwconv3_fwd(const unsigned short *__res
                 for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                     for (int kx = 0; kx < 3; ++kx) {
-                        dw_unpack8(win[ky][kx], f);
+                        unpack8_bf16(win[ky][kx], f);
 #pragma unroll
                         for (int k = 0; k < 8; ++k) acc[k] = fmaf(wt[ky * 3 + kx][k], f[k], acc[k]);
                     }
-                *reinterpret_cast<uint4 *>(z + base + ((size_t)i * W + j) * C) = dw_pack8(acc);
+                *reinterpret_cast<uint4 *>(z + base + ((size_t)i * W + j) * C) = pack8_bf16(acc);
 #pragma unroll
                 for (int q = 0; q < 3; ++q) { win[0][q] = win[1][q]; win[1][q] = win[2][q]; }
             }
@@ -135,7 +111,7 @@ __global__ __launch_bounds__(256) void k_dwconv3_bwd(const unsigned short *__res
                                                      int C, int ns, int64_t P, int CW, int RP, int iters, unsigned short *__restrict__ dx, float *__restrict__ slab) {
     __shared__ __attribute__((aligned(16))) float red[kDwTapsPerPass * 256 * 8];
     const int tid = threadIdx.x, col = tid % CW, row = tid / CW;
-    const int C8 = C / 8, c8 = blockIdx.y * kDwGroupChunks + col;
+    const int C8 = C / 8, c8 = blockIdx.y * kGroupChunks + col;
     const bool act = row < RP && c8 < C8;
     float wt[9][8], acc[9][8];
 #pragma unroll
@@ -161,19 +137,19 @@ __global__ __launch_bounds__(256) void k_dwconv3_bwd(const unsigned short *__res
                 if (i < H) {
                     dw_load_row(dimg, i + 1, j, H, W, C, win[2]);
                     float xc[8], g[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, f[8];
-                    if (DWG) dw_unpack8(*reinterpret_cast<const uint4 *>(x + base + ((size_t)i * W + j) * C), xc);
+                    if (DWG) unpack8_bf16(*reinterpret_cast<const uint4 *>(x + base + ((size_t)i * W + j) * C), xc);
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx) {
-                            dw_unpack8(win[2 - ky][2 - kx], f);  // dz[i - ky + 1, j - kx + 1]
+                            unpack8_bf16(win[2 - ky][2 - kx], f);  // dz[i - ky + 1, j - kx + 1]
 #pragma unroll
                             for (int k = 0; k < 8; ++k) {
                                 if (DX) g[k] = fmaf(wt[ky * 3 + kx][k], f[k], g[k]);
                                 if (DWG) acc[ky * 3 + kx][k] = fmaf(xc[k], f[k], acc[ky * 3 + kx][k]);
                             }
                         }
-                    if (DX) *reinterpret_cast<uint4 *>(dx + base + ((size_t)i * W + j) * C) = dw_pack8(g);
+                    if (DX) *reinterpret_cast<uint4 *>(dx + base + ((size_t)i * W + j) * C) = pack8_bf16(g);
 #pragma unroll
                     for (int q = 0; q < 3; ++q) { win[0][q] = win[1][q]; win[1][q] = win[2][q]; }
                 }
@@ -181,8 +157,6 @@ __global__ __launch_bounds__(256) void k_dwconv3_bwd(const unsigned short *__res
         }
     if (!DWG) return;
     // the RP lanes of a chunk column: pairwise tree over the rows, kDwTapsPerPass taps at a time; plane p of `red` is [row][col][8]
-    int top = 1;
-    while (top < RP) top <<= 1;
 #pragma unroll
     for (int t0 = 0; t0 < 9; t0 += kDwTapsPerPass) {
         if (row < RP) {
@@ -193,21 +167,8 @@ __global__ __launch_bounds__(256) void k_dwconv3_bwd(const unsigned short *__res
                 r4[1] = make_float4(acc[t0 + p][4], acc[t0 + p][5], acc[t0 + p][6], acc[t0 + p][7]);
             }
         }
-        for (int st = top >> 1; st >= 1; st >>= 1) {
-            __syncthreads();
-            if (row < st && row + st < RP) {
-#pragma unroll
-                for (int p = 0; p < kDwTapsPerPass; ++p) {
-                    float4 *r4 = reinterpret_cast<float4 *>(red + p * 2048 + (row * CW + col) * 8);
-                    const float4 *o4 = reinterpret_cast<const float4 *>(red + p * 2048 + ((row + st) * CW + col) * 8);
-                    const float4 a0 = r4[0], a1 = r4[1], b0 = o4[0], b1 = o4[1];
-                    r4[0] = make_float4(a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w);
-                    r4[1] = make_float4(a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w);
-                }
-            }
-        }
-        __syncthreads();
-        const int c = blockIdx.y * kDwGroupChunks * 8 + tid;  // row 0 of the plane: [col][8] = 8 CW consecutive channels
+        lds_row_tree<8, kDwTapsPerPass>(red, 2048, row, col, CW, RP);
+        const int c = blockIdx.y * kGroupChunks * 8 + tid;  // row 0 of the plane: [col][8] = 8 CW consecutive channels
         if (tid < CW * 8 && c < C) {
 #pragma unroll
             for (int p = 0; p < kDwTapsPerPass; ++p) slab[((size_t)blockIdx.x * 9 + t0 + p) * C + c] = red[p * 2048 + tid];
@@ -218,19 +179,11 @@ __global__ __launch_bounds__(256) void k_dwconv3_bwd(const unsigned short *__res
 
 // dw[c][tap] = sum over the slabs of slab[bx][tap][c]: element q = tap * C + c of the [nbx][9 C] matrix, walkers then the tree
 __global__ __launch_bounds__(256) void k_dw_final(const float *__restrict__ slab, int nbx, int C, float *__restrict__ dw) {
-    __shared__ float sm[kDwWalkers][kDwWalkEl];
-    const int el = threadIdx.x % kDwWalkEl, wk = threadIdx.x / kDwWalkEl, n = 9 * C, q = blockIdx.x * kDwWalkEl + el;
-    float a = 0.f;
-    if (q < n)
-        for (int k = wk; k < nbx; k += kDwWalkers) a += slab[(size_t)k * n + q];
-    sm[wk][el] = a;
-    for (int st = kDwWalkers / 2; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (wk < st) { a += sm[wk + st][el]; sm[wk][el] = a; }
-    }
-    if (wk != 0 || q >= n) return;
+    const int q = slab_elem();
+    float a[1];
+    if (!slab_combine<1>({slab}, nbx, 9 * C, q, a)) return;
     const int tap = q / C, c = q - tap * C;
-    dw[(size_t)c * 9 + tap] = a;
+    dw[(size_t)c * 9 + tap] = a[0];
 }
 
 namespace {
@@ -239,7 +192,7 @@ bool dw_aligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) =
 int dw_check(obb_ctx *ctx, const char *fn, int32_t B, int32_t H, int32_t W, int32_t C) {
     OBB_REQUIRE(ctx, ctx && C >= 8 && C % 8 == 0, "%s: C = %d must be a positive multiple of 8", fn, (int)C);
     OBB_REQUIRE(ctx, B >= 1 && H >= 1 && W >= 1, "%s: B = %d, H = %d, W = %d must be at least 1", fn, (int)B, (int)H, (int)W);
-    OBB_REQUIRE(ctx, (int64_t)B * H * W < (1ll << 40) && cdiv(C / 8, kDwGroupChunks) < 65536, "%s: B = %d, H = %d, W = %d, C = %d: too large", fn, (int)B, (int)H,
+    OBB_REQUIRE(ctx, (int64_t)B * H * W < (1ll << 40) && cdiv(C / 8, kGroupChunks) < 65536, "%s: B = %d, H = %d, W = %d, C = %d: too large", fn, (int)B, (int)H,
                 (int)W, (int)C);
     return OBB_OK;
 }
@@ -305,7 +258,7 @@ int obb_dwconv3_bwd_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dz, co
         dw_launch_bwd<4>(g, st, x, dz, w, (int)H, (int)W, (int)C, dx, slab);
     else
         dw_launch_bwd<2>(g, st, x, dz, w, (int)H, (int)W, (int)C, dx, slab);
-    if (dw) hipLaunchKernelGGL(k_dw_final, dim3((unsigned)cdiv(9 * (int64_t)C, kDwWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)C, dw);
+    if (dw) hipLaunchKernelGGL(k_dw_final, dim3((unsigned)cdiv(9 * (int64_t)C, kSlabWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)C, dw);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }

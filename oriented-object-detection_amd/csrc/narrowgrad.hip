@@ -1,7 +1,7 @@
 // Training-mode kernels of the conv layers whose channel counts are no multiples of 8 (`model.train(...)`,
 // Train_OBB.py:796-841): the plain `Conv2d` 1x1 + bias outputs of the head (model.23.cv3.i.2: c -> nc class logits, model.23.cv4.i.2: c -> 1 angle
 // logit) and the stem (model.0: Conv 3x3 s2 on the 3- or 4-channel uint8 tile).  Conventions of dwgrad.hip: the fp32 master weights are read
-// directly and rounded to bf16 (nearest even) as they are loaded -- no pack step --, products and sums are fp32 (a bf16 x bf16 product is exact in
+// directly and rounded to bf16 (traindev.h's bf16_round) as they are loaded -- no pack step --, products and sums are fp32 (a bf16 x bf16 product is exact in
 // fp32, so fmaf is the product followed by the addition), no atomics.  Every padded channel lives in registers or LDS, never in global memory.
 //
 // HEAD, pixels flattened, N = B H W, x bf16 [N][cin] (cin % 8 == 0, <= 512), y / dy fp32 [N][cout] dense (1 <= cout <= 64; rows of 4 cout bytes: scalar
@@ -13,9 +13,9 @@
 // Backward split (head_geo, the ONE place that decides it; obb_headconv_bwd_geometry returns it): a lane owns CPL input channels (2; 1 when cout >
 // 16) and OT outputs (4 / 16 / 64 >= cout, the padding in registers): its OT x CPL weights and dw sums stay in registers while it walks pixels
 // bx RP + row + t nbx RP, t < iters -- x, dy are read and dx is written once, dx / dw / db from the same pass.  A workgroup is CW channel lanes x
-// RP pixel rows; the dy rows of a pass are rounded once into LDS by the whole workgroup.  The RP lanes of a channel meet in LDS in a fixed pairwise
-// tree (row r takes in row r + st), 8 outputs per pass; workgroup bx writes its partial to the fp32 slab [bx][cout cin + cout] (WS_TRAIN_E, never read before it is written: growing the slot changes nothing);
-// k_narrow_final adds the slabs in index order (64 strided walkers per element, then a pairwise tree).  L = iters + ceil(log2 RP) + ceil(nbx / 64) + 6.
+// RP pixel rows; the dy rows of a pass are rounded once into LDS by the whole workgroup.  The RP lanes of a channel meet in LDS in traindev.h's
+// lds_row_tree, 8 outputs per pass; workgroup bx writes its partial to the fp32 slab [bx][cout cin + cout] (WS_TRAIN_E, never read before it is
+// written: growing the slot changes nothing); k_narrow_final adds the slabs in slab_combine's order.  L = iters + ceil(log2 RP) + slab_chain(nbx).
 //
 // STEM, x uint8 [B][H][W][cin] (cin 3 or 4), operand x~ = bf16(v / 255) from a 256-entry LDS table (an fp32 division, then nearest even: the value
 // the inference stem uses in its bf16 mode), w fp32 [cout][cin][3][3] (cout % 8 == 0, <= 64), z / dz bf16 [B][Ho][Wo][cout], Ho = (H + 1) / 2:
@@ -27,29 +27,15 @@
 #include <algorithm>
 
 #include "ctx.h"
+#include "traindev.h"
 
 namespace obb {
 namespace {
 
 constexpr int kNrMaxSlabs = 512;   // workgroups (= slabs) per column group at most: beyond, a lane's run grows
 constexpr int kNrMinRun = 8;       // pixels per lane run before a second workgroup is opened: amortises the lane's weight loads and the slab
-constexpr int kNrWalkers = 64;     // strided walkers per element in k_narrow_final (x 4 elements = 256 threads)
-constexpr int kNrWalkEl = 256 / kNrWalkers;
 constexpr int kHeadFwdThreads = 128;
 constexpr int kHeadMaxCin = 512, kHeadMaxCout = 64, kStemMaxCout = 64;
-
-__device__ __forceinline__ unsigned short nr_to_bf16(float f) {  // round to nearest even (dwgrad.hip's)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ float nr_round(float f) { return __uint_as_float((unsigned)nr_to_bf16(f) << 16); }
-
-int nr_depth(int rp) {
-    int d = 0;
-    while ((1 << d) < rp) ++d;
-    return d;
-}
 
 struct HeadGeo { int OT, CPL, CW, RP, ny, nbx, L; int64_t iters; };
 HeadGeo head_geo(int64_t N, int cin, int cout) {
@@ -62,7 +48,7 @@ HeadGeo head_geo(int64_t N, int cin, int cout) {
     g.RP = 256 / g.CW;
     g.nbx = (int)std::min<int64_t>(cdiv(N, (int64_t)g.RP * kNrMinRun), kNrMaxSlabs);
     g.iters = cdiv(N, (int64_t)g.nbx * g.RP);
-    g.L = (int)std::min<int64_t>(g.iters + nr_depth(g.RP) + cdiv(g.nbx, kNrWalkers) + 6, INT32_MAX);
+    g.L = (int)std::min<int64_t>(g.iters + tree_depth(g.RP) + slab_chain(g.nbx), INT32_MAX);
     return g;
 }
 
@@ -76,7 +62,7 @@ StemGeo stem_geo(int B, int H, int W, int cout) {
     g.RP = 256 / g.CW;
     g.nbx = (int)std::min<int64_t>(cdiv(g.NP, (int64_t)g.RP * kNrMinRun), kNrMaxSlabs);
     g.iters = cdiv(g.NP, (int64_t)g.nbx * g.RP);
-    g.L = (int)std::min<int64_t>(g.iters + nr_depth(g.RP) + cdiv(g.nbx, kNrWalkers) + 6, INT32_MAX);
+    g.L = (int)std::min<int64_t>(g.iters + tree_depth(g.RP) + slab_chain(g.nbx), INT32_MAX);
     return g;
 }
 
@@ -92,7 +78,7 @@ __global__ __launch_bounds__(kHeadFwdThreads) void k_headconv_fwd(const unsigned
         if (o0) __syncthreads();
         for (int e = threadIdx.x; e < OT * cin; e += kHeadFwdThreads) {
             const int o = o0 + e / cin;
-            wl[e] = o < cout ? nr_round(w[(size_t)o * cin + e % cin]) : 0.f;
+            wl[e] = o < cout ? bf16_round(w[(size_t)o * cin + e % cin]) : 0.f;
         }
         __syncthreads();
         if (n < N) {
@@ -101,11 +87,8 @@ __global__ __launch_bounds__(kHeadFwdThreads) void k_headconv_fwd(const unsigned
             for (int o = 0; o < OT; ++o) acc[o] = 0.f;
             const uint4 *xr = reinterpret_cast<const uint4 *>(x + (size_t)n * cin);
             for (int c8 = 0; c8 < cin / 8; ++c8) {
-                const uint4 v = xr[c8];
-                const unsigned u[4] = {v.x, v.y, v.z, v.w};
                 float f[8];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(u[j] << 16); f[2 * j + 1] = __uint_as_float(u[j] & 0xffff0000u); }
+                unpack8_bf16(xr[c8], f);
 #pragma unroll
                 for (int o = 0; o < OT; ++o) {
                     const float4 *wr = reinterpret_cast<const float4 *>(wl + o * cin + c8 * 8);
@@ -122,48 +105,21 @@ __global__ __launch_bounds__(kHeadFwdThreads) void k_headconv_fwd(const unsigned
     }
 }
 
-// ---------------------------------------------------------------------------------------------- the LDS tree and the slab combine (head and stem)
-// `red` holds [row][col][V] floats; afterwards row 0 holds the sums over the RP rows, added pairwise: row r takes in row r + st, st = top / 2 .. 1
-// (`on`: this lane owns a column; every thread of the workgroup calls)
-template <int V>
-__device__ __forceinline__ void nr_tree(float *red, int row, int col, int CW, int RP, bool on = true) {
-    int top = 1;
-    while (top < RP) top <<= 1;
-    for (int st = top >> 1; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (on && row < st && row + st < RP) {
-            float *a = red + (row * CW + col) * V;
-            const float *b = red + ((row + st) * CW + col) * V;
-#pragma unroll
-            for (int v = 0; v < V; ++v) a[v] += b[v];
-        }
-    }
-    __syncthreads();
-}
-
-// out element q = sum over the slabs of slab[k][q], k in index order: walkers then the tree.  STEM: q = (tap cin + c) cout + o -> dw[o][c][tap];
+// ---------------------------------------------------------------------------------------------- the slab combine (head and stem)
+// out element q = sum over the slabs of slab[k][q] in slab_combine's order.  STEM: q = (tap cin + c) cout + o -> dw[o][c][tap];
 // head: q < cout cin -> dw[q], else db[q - cout cin] (a NULL output is skipped)
 template <bool STEM>
 __global__ __launch_bounds__(256) void k_narrow_final(const float *__restrict__ slab, int nbx, int cin, int cout, float *__restrict__ dw, float *__restrict__ db) {
-    __shared__ float sm[kNrWalkers][kNrWalkEl];
-    const int el = threadIdx.x % kNrWalkEl, wk = threadIdx.x / kNrWalkEl;
-    const int n = STEM ? 9 * cin * cout : cout * cin + cout, q = blockIdx.x * kNrWalkEl + el;
-    float a = 0.f;
-    if (q < n)
-        for (int k = wk; k < nbx; k += kNrWalkers) a += slab[(size_t)k * n + q];
-    sm[wk][el] = a;
-    for (int st = kNrWalkers / 2; st >= 1; st >>= 1) {
-        __syncthreads();
-        if (wk < st) { a += sm[wk + st][el]; sm[wk][el] = a; }
-    }
-    if (wk != 0 || q >= n) return;
+    const int q = slab_elem();
+    float a[1];
+    if (!slab_combine<1>({slab}, nbx, STEM ? 9 * cin * cout : cout * cin + cout, q, a)) return;
     if (STEM) {
         const int o = q % cout, tc = q / cout, c = tc % cin, tap = tc / cin;
-        dw[((size_t)o * cin + c) * 9 + tap] = a;
+        dw[((size_t)o * cin + c) * 9 + tap] = a[0];
     } else if (q < cout * cin) {
-        if (dw) dw[q] = a;
+        if (dw) dw[q] = a[0];
     } else if (db) {
-        db[q - cout * cin] = a;
+        db[q - cout * cin] = a[0];
     }
 }
 
@@ -189,7 +145,7 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
         for (int o = 0; o < OT; ++o)
             if (o < cout) {
 #pragma unroll
-                for (int k = 0; k < CPL; ++k) wt[o][k] = nr_round(w[(size_t)o * cin + c0 + k]);
+                for (int k = 0; k < CPL; ++k) wt[o][k] = bf16_round(w[(size_t)o * cin + c0 + k]);
             }
     }
     // the dy rows of the workgroup's RP pixels of pass t, rounded once into LDS as [row][OT] (zeros past cout and past N) by all 256 threads --
@@ -200,7 +156,7 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
         const int64_t n0 = (int64_t)blockIdx.x * RP + t * stride;
         for (int e = tid; e < RP * OT; e += 256) {
             const int r = e / OT, o = e % OT;
-            buf[e] = (o < cout && n0 + r < N) ? nr_round(dy[(size_t)(n0 + r) * cout + o]) : 0.f;
+            buf[e] = (o < cout && n0 + r < N) ? bf16_round(dy[(size_t)(n0 + r) * cout + o]) : 0.f;
         }
         __syncthreads();
         const int64_t n = n0 + row;
@@ -214,10 +170,10 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
             if (DWG) {
                 if (CPL == 2) {
                     const unsigned u = *reinterpret_cast<const unsigned *>(x + (size_t)n * cin + c0);
-                    xv[0] = __uint_as_float(u << 16);
-                    xv[CPL - 1] = __uint_as_float(u & 0xffff0000u);
+                    xv[0] = bf16_lo(u);
+                    xv[CPL - 1] = bf16_hi(u);
                 } else {
-                    xv[0] = __uint_as_float((unsigned)x[(size_t)n * cin + c0] << 16);
+                    xv[0] = bf16_widen(x[(size_t)n * cin + c0]);
                 }
             }
             if (DX) {
@@ -229,9 +185,9 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
 #pragma unroll
                     for (int k = 0; k < CPL; ++k) g[k] = fmaf(wt[o][k], d[o], g[k]);
                 if (CPL == 2)
-                    *reinterpret_cast<unsigned *>(dx + (size_t)n * cin + c0) = (unsigned)nr_to_bf16(g[0]) | ((unsigned)nr_to_bf16(g[CPL - 1]) << 16);
+                    *reinterpret_cast<unsigned *>(dx + (size_t)n * cin + c0) = bf16_pack2(g[0], g[CPL - 1]);
                 else
-                    dx[(size_t)n * cin + c0] = nr_to_bf16(g[0]);
+                    dx[(size_t)n * cin + c0] = bf16_rne(g[0]);
             }
             if (DWG) {
 #pragma unroll
@@ -258,7 +214,7 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
 #pragma unroll
                 for (int k = 0; k < CPL; ++k) red[(row * CW + col) * (OP * CPL) + oo * CPL + k] = acc[o0 + oo][k];
         }
-        nr_tree<OP * CPL>(red, row, col, CW, RP);
+        lds_row_tree<OP * CPL>(red, 0, row, col, CW, RP);
         for (int e = tid; e < CW * OP * CPL; e += 256) {  // row 0: [col][oo][k]
             const int r = e % (OP * CPL), o = o0 + r / CPL, c = (blockIdx.y * CW + e / (OP * CPL)) * CPL + r % CPL;
             if (o < cout && c < cin) mine[(size_t)o * cin + c] = red[e];
@@ -270,13 +226,13 @@ __global__ __launch_bounds__(256) void k_headconv_bwd(const unsigned short *__re
 #pragma unroll
         for (int o = 0; o < OT; ++o) red[row * OT + o] = dbs[o];
     }
-    nr_tree<OT>(red, row, 0, 1, RP, col == 0);  // one column of OT values per row
+    lds_row_tree<OT>(red, 0, row, 0, 1, RP, col == 0);  // one column of OT values per row
     if (tid < cout) mine[(size_t)cout * cin + tid] = red[tid];
 }
 
 // ---------------------------------------------------------------------------------------------- stem
 __device__ __forceinline__ void stem_table(float *tab) {  // tab[v] = bf16(v / 255)
-    for (int v = threadIdx.x; v < 256; v += blockDim.x) tab[v] = nr_round((float)v / 255.0f);
+    for (int v = threadIdx.x; v < 256; v += blockDim.x) tab[v] = bf16_round((float)v / 255.0f);
 }
 // the CIN operands of input pixel (yy, xx) of image `img`
 template <int CIN>
@@ -300,7 +256,7 @@ __global__ __launch_bounds__(256) void k_stemconv_fwd(const unsigned char *__res
     stem_table(tab);
     for (int e = threadIdx.x; e < 9 * CIN * cout; e += 256) {
         const int o = e % cout, tc = e / cout, c = tc % CIN, tap = tc / CIN;
-        wl[e] = nr_round(w[((size_t)o * CIN + c) * 9 + tap]);
+        wl[e] = bf16_round(w[((size_t)o * CIN + c) * 9 + tap]);
     }
     __syncthreads();
     const int G = cout / (8 * OC);
@@ -338,12 +294,7 @@ __global__ __launch_bounds__(256) void k_stemconv_fwd(const unsigned char *__res
     }
     uint4 *zr = reinterpret_cast<uint4 *>(z + (size_t)pix * cout + o0);
 #pragma unroll
-    for (int q = 0; q < OC; ++q) {
-        unsigned u[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) u[m] = (unsigned)nr_to_bf16(acc[8 * q + 2 * m]) | ((unsigned)nr_to_bf16(acc[8 * q + 2 * m + 1]) << 16);
-        zr[q] = make_uint4(u[0], u[1], u[2], u[3]);
-    }
+    for (int q = 0; q < OC; ++q) zr[q] = pack8_bf16(acc + 8 * q);
 }
 
 // wgrad: grid nbx, workgroup = CW lanes of 4 outputs x RP pixel rows; lane (row, col) walks output pixels bx RP + row + t nbx RP
@@ -370,7 +321,7 @@ __global__ __launch_bounds__(256) void k_stemconv_wgrad(const unsigned char *__r
             const int64_t b = pix / ((int64_t)Wo * Ho);
             const unsigned char *img = x + (size_t)b * H * W * CIN;
             const uint2 dv = *reinterpret_cast<const uint2 *>(dz + (size_t)pix * cout + col * 4);
-            const float d[4] = {__uint_as_float(dv.x << 16), __uint_as_float(dv.x & 0xffff0000u), __uint_as_float(dv.y << 16), __uint_as_float(dv.y & 0xffff0000u)};
+            const float d[4] = {bf16_lo(dv.x), bf16_hi(dv.x), bf16_lo(dv.y), bf16_hi(dv.y)};
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky) {
                 const int yy = 2 * i + ky - 1;
@@ -397,7 +348,7 @@ __global__ __launch_bounds__(256) void k_stemconv_wgrad(const unsigned char *__r
 #pragma unroll
                 for (int k = 0; k < 4; ++k) red[(row * CW + col) * (CIN * 4) + c * 4 + k] = acc[tap][c][k];
         }
-        nr_tree<CIN * 4>(red, row, col, CW, RP);
+        lds_row_tree<CIN * 4>(red, 0, row, col, CW, RP);
         if (tid < CW * CIN * 4) {  // row 0: [col][c][k]
             const int r = tid % (CIN * 4), c = r / 4, o = (tid / (CIN * 4)) * 4 + r % 4;
             mine[((size_t)tap * CIN + c) * cout + o] = red[tid];
@@ -498,7 +449,7 @@ int obb_headconv_bwd_bf16(obb_ctx *ctx, const uint16_t *x, const float *dy, cons
     else
         head_launch_bwd<64, 1>(g, st, x, dy, w, N, (int)cin, (int)cout, dx, slab);
     if (grads)
-        hipLaunchKernelGGL((k_narrow_final<false>), dim3((unsigned)cdiv((int64_t)cout * cin + cout, kNrWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)cin, (int)cout, dw, db);
+        hipLaunchKernelGGL((k_narrow_final<false>), dim3((unsigned)cdiv((int64_t)cout * cin + cout, kSlabWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)cin, (int)cout, dw, db);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }
@@ -532,7 +483,7 @@ int obb_stemconv_wgrad_u8(obb_ctx *ctx, const uint8_t *x, const uint16_t *dz, in
         hipLaunchKernelGGL((k_stemconv_wgrad<3>), dim3((unsigned)g.nbx), dim3(256), 0, st, x, dz, (int)H, (int)W, g.Ho, g.Wo, (int)cout, g.NP, g.CW, g.RP, g.iters, slab);
     else
         hipLaunchKernelGGL((k_stemconv_wgrad<4>), dim3((unsigned)g.nbx), dim3(256), 0, st, x, dz, (int)H, (int)W, g.Ho, g.Wo, (int)cout, g.NP, g.CW, g.RP, g.iters, slab);
-    hipLaunchKernelGGL((k_narrow_final<true>), dim3((unsigned)cdiv(9 * (int64_t)cin * cout, kNrWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)cin, (int)cout, dw, (float *)nullptr);
+    hipLaunchKernelGGL((k_narrow_final<true>), dim3((unsigned)cdiv(9 * (int64_t)cin * cout, kSlabWalkEl)), dim3(256), 0, st, slab, g.nbx, (int)cin, (int)cout, dw, (float *)nullptr);
     OBB_LAUNCH_CHECK(ctx);
     return OBB_OK;
 }

@@ -1,7 +1,8 @@
 // Gradient routing through the parts of the trunk that are not convolutions (`model.train(...)`, Train_OBB.py:796-841
 // -> ultralytics SPPF / nn.Upsample / Concat): the three chained 5x5 max pools of SPPF (model 9), Upsample(2x) + Concat of the FPN (models 11/12,
 // 14/15), the plain Concat of the PAN (models 18, 21) and the gradient sum of a tensor with two consumers.  bf16 NHWC tensors, channel counts
-// multiples of 8: a lane moves one 16-byte chunk (8 channels).  No atomics, fixed summation order: bit-reproducible.  No workspace.
+// multiples of 8: a lane moves one 16-byte chunk (8 channels; traindev.h's unpack8_bf16 / pack8_bf16, the one rounding rule).  No atomics, fixed
+// summation order: bit-reproducible.  No workspace.
 //
 //   pools forward   cat = [x, y1, y2, y3], y_k = maxpool5x5(y_{k-1}) (stride 1, pad 2, padding never wins).  A workgroup owns one image and
 //                   `share` channel chunks with their whole H x W map in LDS (two planes, pooled plane to plane); values are copied, never
@@ -26,6 +27,7 @@
 
 #include "ctx.h"
 #include "launchcfg.h"
+#include "traindev.h"
 
 namespace obb {
 namespace {
@@ -34,29 +36,6 @@ constexpr int kPoolMaxSide = 32;      // H, W <= 32: imgsz <= 1024 at stride 32
 constexpr int kPoolMaxElems = 1024;   // pixels x chunks resident per workgroup
 constexpr int kPoolBwdBytes = 72;     // LDS bytes per resident (pixel, chunk) in the backward
 constexpr int kPoolFwdBytes = 32;
-
-__device__ __forceinline__ unsigned short rg_to_bf16(float f) {  // round to nearest even (bntrain.hip's)
-    unsigned u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ void rg_unpack8(const uint4 v, float f[8]) {
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(w[j] << 16); f[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u); }
-}
-__device__ __forceinline__ uint4 rg_pack8(const float f[8]) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (unsigned)rg_to_bf16(f[2 * j]) | ((unsigned)rg_to_bf16(f[2 * j + 1]) << 16);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-__device__ __forceinline__ uint4 rg_pack8_exact(const float f[8]) {  // f holds bf16 values: the high halves are the bits
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (__float_as_uint(f[2 * j]) >> 16) | (__float_as_uint(f[2 * j + 1]) & 0xffff0000u);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 int pool_share(int H, int W) { return H * W * 2 <= kPoolMaxElems ? 2 : 1; }
 
@@ -86,11 +65,11 @@ __global__ __launch_bounds__(256) void k_sppf_pools_fwd(const unsigned short *__
             for (int j = 0; j < 8; ++j) m[j] = -INFINITY;
             for (int yy = max(py - 2, 0); yy <= min(py + 2, H - 1); ++yy)
                 for (int xx = max(px - 2, 0); xx <= min(px + 2, W - 1); ++xx) {
-                    rg_unpack8(cur[(yy * W + xx) * cg + ch], f);
+                    unpack8_bf16(cur[(yy * W + xx) * cg + ch], f);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) m[j] = f[j] > m[j] ? f[j] : m[j];
                 }
-            const uint4 r = rg_pack8_exact(m);
+            const uint4 r = pack8_bf16_exact(m);
             nxt[e] = r;
             *reinterpret_cast<uint4 *>(cb + (size_t)p * 4 * C + (size_t)k * C + ch * 8) = r;
         }
@@ -112,7 +91,7 @@ __global__ __launch_bounds__(256) void k_sppf_pools_bwd(const unsigned short *__
     float f[8];
     for (int e = threadIdx.x; e < n; e += 256) {  // g_3 = dcat member 3
         const int p = e / cg, ch = e - p * cg;
-        rg_unpack8(*reinterpret_cast<const uint4 *>(db + (size_t)p * 4 * C + (size_t)3 * C + ch * 8), f);
+        unpack8_bf16(*reinterpret_cast<const uint4 *>(db + (size_t)p * 4 * C + (size_t)3 * C + ch * 8), f);
         cur[2 * e] = make_float4(f[0], f[1], f[2], f[3]);
         cur[2 * e + 1] = make_float4(f[4], f[5], f[6], f[7]);
     }
@@ -132,7 +111,7 @@ __global__ __launch_bounds__(256) void k_sppf_pools_bwd(const unsigned short *__
             for (int yy = max(py - 2, 0); yy <= min(py + 2, H - 1); ++yy)
                 for (int xx = max(px - 2, 0); xx <= min(px + 2, W - 1); ++xx) {
                     const unsigned c = (unsigned)((yy - py + 2) * 5 + (xx - px + 2));
-                    rg_unpack8(val[(yy * W + xx) * cg + ch], f);
+                    unpack8_bf16(val[(yy * W + xx) * cg + ch], f);
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
                         if (f[j] > m[j]) { m[j] = f[j]; code[j] = c; }
@@ -143,7 +122,7 @@ __global__ __launch_bounds__(256) void k_sppf_pools_bwd(const unsigned short *__
         for (int e = threadIdx.x; e < n; e += 256) {  // input pixel p gathers from the outputs whose argmax it is
             const int p = e / cg, ch = e - p * cg, py = p / W, px = p - py * W;
             float acc[8];
-            rg_unpack8(*reinterpret_cast<const uint4 *>(db + (size_t)p * 4 * C + (size_t)(k - 1) * C + ch * 8), acc);
+            unpack8_bf16(*reinterpret_cast<const uint4 *>(db + (size_t)p * 4 * C + (size_t)(k - 1) * C + ch * 8), acc);
             // output q = p - (oy, ox) holds p at window offset (oy, ox)
             for (int oy = -2; oy <= 2; ++oy) {
                 const int qy = py - oy;
@@ -167,7 +146,7 @@ __global__ __launch_bounds__(256) void k_sppf_pools_bwd(const unsigned short *__
                 nxt[2 * e] = make_float4(acc[0], acc[1], acc[2], acc[3]);
                 nxt[2 * e + 1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
             } else {
-                *reinterpret_cast<uint4 *>(xb + (size_t)p * C + ch * 8) = rg_pack8(acc);
+                *reinterpret_cast<uint4 *>(xb + (size_t)p * C + ch * 8) = pack8_bf16(acc);
             }
         }
         __syncthreads();
@@ -206,29 +185,29 @@ __global__ __launch_bounds__(256) void k_upcat_bwd(const unsigned short *__restr
             const int c = (int)(i - pix * Ca8), x = (int)(pix % W), y = (int)((pix / W) % H);
             const int64_t img = pix / ((int64_t)W * H);
             uint4 *dst = reinterpret_cast<uint4 *>(da) + i;
-            if (accum_a) rg_unpack8(*dst, acc);
+            if (accum_a) unpack8_bf16(*dst, acc);
             else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] = 0.f;
             }
             for (int dy = 0; dy < up; ++dy)
                 for (int dxx = 0; dxx < up; ++dxx) {
-                    rg_unpack8(d4[((img * uH + y * up + dy) * uW + x * up + dxx) * Co8 + c], f);
+                    unpack8_bf16(d4[((img * uH + y * up + dy) * uW + x * up + dxx) * Co8 + c], f);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) acc[j] += f[j];
                 }
-            *dst = rg_pack8(acc);
+            *dst = pack8_bf16(acc);
         } else {
             const int64_t k = i - nA, pix = k / Cb8;
             const int c = (int)(k - pix * Cb8);
             const uint4 v = d4[pix * Co8 + Ca8 + c];
             uint4 *dst = reinterpret_cast<uint4 *>(db) + k;
             if (accum_b) {
-                rg_unpack8(*dst, acc);
-                rg_unpack8(v, f);
+                unpack8_bf16(*dst, acc);
+                unpack8_bf16(v, f);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] += f[j];
-                *dst = rg_pack8(acc);
+                *dst = pack8_bf16(acc);
             } else {
                 *dst = v;
             }
@@ -240,11 +219,11 @@ __global__ __launch_bounds__(256) void k_upcat_bwd(const unsigned short *__restr
 __global__ __launch_bounds__(256) void k_add_bf16(const unsigned short *a, const unsigned short *__restrict__ b, int64_t nchunk, unsigned short *out) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nchunk; i += (int64_t)gridDim.x * 256) {
         float x[8], y[8];
-        rg_unpack8(reinterpret_cast<const uint4 *>(a)[i], x);
-        rg_unpack8(reinterpret_cast<const uint4 *>(b)[i], y);
+        unpack8_bf16(reinterpret_cast<const uint4 *>(a)[i], x);
+        unpack8_bf16(reinterpret_cast<const uint4 *>(b)[i], y);
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] += y[j];
-        reinterpret_cast<uint4 *>(out)[i] = rg_pack8(x);
+        reinterpret_cast<uint4 *>(out)[i] = pack8_bf16(x);
     }
 }
 
@@ -257,11 +236,11 @@ __global__ __launch_bounds__(256) void k_chanwin(const unsigned short *__restric
         uint4 v = reinterpret_cast<const uint4 *>(src)[pix * Cs8 + s8 + c];
         if (add) {
             float x[8], y[8];
-            rg_unpack8(v, x);
-            rg_unpack8(reinterpret_cast<const uint4 *>(add)[pix * Ca8 + a8 + c], y);
+            unpack8_bf16(v, x);
+            unpack8_bf16(reinterpret_cast<const uint4 *>(add)[pix * Ca8 + a8 + c], y);
 #pragma unroll
             for (int j = 0; j < 8; ++j) x[j] += y[j];
-            v = rg_pack8(x);
+            v = pack8_bf16(x);
         }
         reinterpret_cast<uint4 *>(dst)[pix * Cd8 + d8 + c] = v;
     }
