@@ -91,6 +91,11 @@ int obb_points_in_quads(obb_ctx *ctx, const double *pts, const int32_t *cls_p, i
  * Detect_OBB.py:87-133 (called per tile at :77).  bgr: uint8[B,h,w,3], out4: uint8[B,h,w,4] = [R, G, B, dt_edge].  The OpenCV steps
  * are restated from their documented algorithms (cv2 is absent offline: parity with cv2 itself is unpinned). */
 int obb_build_multich(obb_ctx *ctx, const uint8_t *bgr, int32_t B, int32_t h, int32_t w, uint8_t *out4, obb_stream_t s);
+/* The same launches with a read-out of the intermediates (for tests): every non-NULL pointer receives, densely, acc float[B,h,w]
+ * (max Scharr magnitude over the scales), edges uint8[B,h,w] (0 / 255, after the opening), dist float[B,h,w] (the chamfer distance)
+ * and stats double[B,5] = the 90th percentile of acc, the 1st and 99th of dist, min and max of acc.  All NULL == obb_build_multich. */
+int obb_build_multich_stages(obb_ctx *ctx, const uint8_t *bgr, int32_t B, int32_t h, int32_t w, uint8_t *out4, float *acc, uint8_t *edges,
+                             float *dist, double *stats, obb_stream_t s);
 
 /* ------------------------------------------------------------------ S3: merge_detections  (Detect_OBB.py:176-200) */
 /* order[n] = stable descending argsort of key (Python list.sort(key=conf, reverse=True), Detect_OBB.py:183). */

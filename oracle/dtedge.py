@@ -136,6 +136,13 @@ def build_multich(bgr, out_channels=4):
     assert out_channels in (3, 4)
     if out_channels == 3:
         return np.ascontiguousarray(bgr)
+    return stages(bgr)[4]
+
+
+def stages(bgr):
+    """The 4-channel branch of build_multich with its intermediates: -> (acc float32 [h,w], edges uint8 [h,w] after the opening,
+    dist float32 [h,w], (thr, lo, hi, mn, mx), out uint8 [h,w,4]); thr / lo / hi are the float64 percentiles (90th of acc, 1st and 99th of
+    dist), mn / mx the float32 extrema of acc that the min-max normalisation uses"""
     rgb_raw = bgr[..., ::-1]
     gray = gray_u8(bgr)
     acc = None
@@ -144,15 +151,16 @@ def build_multich(bgr, out_channels=4):
         mag = scharr_mag(blur)
         acc = mag if acc is None else np.maximum(acc, mag)
     lo, hi = np.percentile(acc, [DT_P_LO, DT_P_HI])
+    thr = hi
     edges = (acc >= np.float32(hi)).astype(np.uint8) * 255  # numpy 1.26: the float64 scalar is cast to the array's float32 before the compare
     if DT_MORPH_OPEN > 0:
         for _ in range(DT_MORPH_OPEN):
             edges = morph_open_cross(edges)
     non_edge = np.where(edges > 0, 0, 255).astype(np.uint8)
-    dist = distance_transform_3x3(non_edge).astype(np.float32)
-    lo, hi = np.percentile(dist, [1, 99])
+    dist_raw = distance_transform_3x3(non_edge).astype(np.float32)
+    lo, hi = np.percentile(dist_raw, [1, 99])
     den = max(1e-6, (hi - lo))                                          # float64 scalars so far
-    dist = np.clip((dist - np.float32(lo)) / np.float32(den), np.float32(0), np.float32(1))  # float32 from here on (numpy 1.26 value-based casting)
+    dist = np.clip((dist_raw - np.float32(lo)) / np.float32(den), np.float32(0), np.float32(1))  # float32 from here on (numpy 1.26 value-based casting)
     tau = np.float32(3.0)
     soft = exp32(-dist / tau)
     acc8_nrm = normalize_minmax01(acc)
@@ -160,4 +168,5 @@ def build_multich(bgr, out_channels=4):
     soft = np.clip(soft, np.float32(0), np.float32(1))
     assert soft.dtype == np.float32
     dt_edge = (soft * np.float32(255)).astype(np.uint8)
-    return np.ascontiguousarray(np.dstack([rgb_raw, dt_edge]).astype(np.uint8))
+    out = np.ascontiguousarray(np.dstack([rgb_raw, dt_edge]).astype(np.uint8))
+    return acc, edges, dist_raw, (float(thr), float(lo), float(hi), np.float32(acc.min()), np.float32(acc.max())), out

@@ -679,6 +679,14 @@ __global__ __launch_bounds__(256) void k_dt_blend(const uint8_t *__restrict__ bg
     reinterpret_cast<unsigned *>(out4)[blockIdx.z * n + i] = o;
 }
 
+// read-out only (obb_build_multich_stages): DtStats -> double[B][5] = thr, lo, hi, mn, mx (float -> double is exact)
+__global__ void k_dt_stats_out(const DtStats *__restrict__ stats, int B, double *__restrict__ out) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const DtStats st = stats[b];
+    out[b * 5 + 0] = st.thr; out[b * 5 + 1] = st.lo; out[b * 5 + 2] = st.hi; out[b * 5 + 3] = (double)st.mn; out[b * 5 + 4] = (double)st.mx;
+}
+
 static void gauss_taps(double sigma, int idx, DtTaps *K) {
     int q[16] = {0};
     const int n = (int)lrint(sigma * 6.0 + 1.0) | 1;
@@ -704,7 +712,9 @@ static void launch_chamfer(int B, hipStream_t s, const uint8_t *edges, size_t es
 
 using namespace obb;
 
-extern "C" int obb_build_multich(obb_ctx *ctx, const uint8_t *bgr, int32_t B, int32_t h, int32_t w, uint8_t *out4, obb_stream_t s) {
+// The builder with a read-out of its intermediates (tests): the same six launches, then dense copies of whatever the caller asked for.
+extern "C" int obb_build_multich_stages(obb_ctx *ctx, const uint8_t *bgr, int32_t B, int32_t h, int32_t w, uint8_t *out4, float *acc_out, uint8_t *edges_out,
+                                        float *dist_out, double *stats_out, obb_stream_t s) {
     OBB_REQUIRE(ctx, ctx && B >= 0 && h > 0 && w > 0, "obb_build_multich: bad arguments");
     if (B == 0) return OBB_OK;
     OBB_REQUIRE(ctx, bgr && out4, "obb_build_multich: NULL buffer");
@@ -740,5 +750,23 @@ extern "C" int obb_build_multich(obb_ctx *ctx, const uint8_t *bgr, int32_t B, in
     hipLaunchKernelGGL(k_dt_blend, dim3((unsigned)((w + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)B), dim3(256), 0, st, bgr, acc, acc_stride,
                        reinterpret_cast<const float *>(tt), tt_stride, stats, h, w, pitch, out4);
     OBB_LAUNCH_CHECK(ctx);
+    // ---- read-out: the pitch-P scratch images of every crop, densely (strided device copies on the same stream)
+    const size_t n = (size_t)h * w;
+    for (int b = 0; b < B && (acc_out || edges_out || dist_out); ++b) {
+        if (acc_out)
+            OBB_HIP(ctx, hipMemcpy2DAsync(acc_out + b * n, (size_t)w * 4, acc + b * acc_stride, (size_t)pitch * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToDevice, st));
+        if (edges_out)
+            OBB_HIP(ctx, hipMemcpy2DAsync(edges_out + b * n, (size_t)w, edges + b * edge_bytes, (size_t)pitch, (size_t)w, (size_t)h, hipMemcpyDeviceToDevice, st));
+        if (dist_out)
+            OBB_HIP(ctx, hipMemcpy2DAsync(dist_out + b * n, (size_t)w * 4, tt + b * tt_stride, (size_t)pitch * 4, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToDevice, st));
+    }
+    if (stats_out) {
+        hipLaunchKernelGGL(k_dt_stats_out, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, stats, B, stats_out);
+        OBB_LAUNCH_CHECK(ctx);
+    }
     return OBB_OK;
+}
+
+extern "C" int obb_build_multich(obb_ctx *ctx, const uint8_t *bgr, int32_t B, int32_t h, int32_t w, uint8_t *out4, obb_stream_t s) {
+    return obb_build_multich_stages(ctx, bgr, B, h, w, out4, nullptr, nullptr, nullptr, nullptr, s);
 }

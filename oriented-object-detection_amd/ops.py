@@ -84,6 +84,12 @@ def _build_multich(bgr: T, out: T) -> None:
     _call("obb_build_multich", ctx(bgr.device), _p(bgr), bgr.shape[0], bgr.shape[1], bgr.shape[2], _p(out), _stream())
 
 
+@_op("build_multich_stages", ("out", "acc", "edges", "dist", "stats"))
+def _build_multich_stages(bgr: T, out: T, acc: T, edges: T, dist: T, stats: T) -> None:
+    _call("obb_build_multich_stages", ctx(bgr.device), _p(bgr), bgr.shape[0], bgr.shape[1], bgr.shape[2], _p(out), _p(acc), _p(edges), _p(dist), _p(stats),
+          _stream())
+
+
 # ---------------------------------------------------------------- S3 merge_detections (Detect_OBB.py:176-200)
 @_op("sort_desc_stable", ("order",))
 def _sort_desc_stable(key: T, order: T) -> None:
@@ -476,6 +482,21 @@ def build_multich(bgr_tiles, out=None):
         assert tuple(out.shape) == (t.shape[0], t.shape[1], t.shape[2], 4)
     _O.build_multich(t, out)
     return out
+
+
+def build_multich_stages(bgr_tiles):
+    """build_multich with its intermediates read out: -> (out uint8 [B,h,w,4], acc float32 [B,h,w], edges uint8 [B,h,w] after the opening,
+    dist float32 [B,h,w], stats float64 [B,5] = thr, lo, hi, mn, mx).  The same launches as build_multich, then dense copies."""
+    t = _chk(bgr_tiles, torch.uint8, "bgr_tiles")
+    assert t.dim() == 4 and t.shape[3] == 3
+    B, h, w = t.shape[:3]
+    out = torch.empty((B, h, w, 4), dtype=torch.uint8, device=t.device)
+    acc = torch.empty((B, h, w), dtype=torch.float32, device=t.device)
+    edges = torch.empty((B, h, w), dtype=torch.uint8, device=t.device)
+    dist = torch.empty((B, h, w), dtype=torch.float32, device=t.device)
+    stats = torch.empty((B, 5), dtype=torch.float64, device=t.device)
+    _O.build_multich_stages(t, out, acc, edges, dist, stats)
+    return out, acc, edges, dist, stats
 
 
 def points_in_quads(pts, quads, cls_p=None, cls_q=None):
