@@ -8,7 +8,7 @@ namespace obb {
 
 struct BneckLaunch {
     TensorRef y1, y2;  // input / output members of a channel-blocked concat buffer (block size = C): dense [image][pixel][C] planes
-    const bf16_t *w1pk = nullptr, *w2pk = nullptr;  // pack_conv_weights(.., ks 3, {NF = 1, CK = C}) and (.., ks 3, {NF = C/16, CK = C/2})
+    const bf16_t *w1pk = nullptr, *w2pk = nullptr;  // pack_conv_weights(.., ks 3, {NF = 1, CK = C}) and (.., ks 3, {NF = C/16, CK = C/2}) (k steps: c16::ksteps, convgeom.h)
     const float *bias1 = nullptr, *bias2 = nullptr;  // padded to a multiple of 64 floats
     int B = 0, H = 0, W = 0, C = 0, f16 = 1;
     // optional closing 1x1 of the C3k2 block (cv2 over [y0 | y1 | y2] -> CO channels, SiLU) fused behind conv 2: y2 is then never written

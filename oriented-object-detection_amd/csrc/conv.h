@@ -33,7 +33,7 @@ struct ConvLaunch {
     int up_c = 0, up_W = 0, up_HW = 0;  // full-resolution width and pixels per image
     // optional fused trailing 1x1 conv without activation (the last layer of an OBB-head branch): its fp32 output rows go to tail_out,
     // the 16-bit output of THIS layer is then never written (conv_tail_supported lists the shapes that have a kernel)
-    const bf16_t *tail_wpk = nullptr;  // pack_conv_weights(w2, tail_cout, cout, 1, {.., NF = tail_cout <= 16 ? 1 : 4, CK = cout})
+    const bf16_t *tail_wpk = nullptr;  // pack_conv_weights(w2, tail_cout, cout, 1, {.., NF = the tail's cout fragments, CK = cout}): c16::tail_weight_bytes of LDS (convgeom.h)
     const float *tail_bias = nullptr;  // padded to a multiple of 64 floats
     int tail_cout = 0;
     bool tail_act16 = false;           // the tail has SiLU and writes ITS 16-bit result to `out` (cv1 of a C3k2 block behind a stride-2 conv)
@@ -51,6 +51,7 @@ struct ConvLaunch {
 
 struct ConvTiling { int TH, TW, MF, NF, CK; };
 
+// The host half below (everything but launch_conv) is convplan.hip: plain host arithmetic on the geometry of convgeom.h.
 // chooses tile shape / fragment blocking for a layer
 ConvTiling plan_conv(int ks, int stride, int cin, int cout, int Hout, int Wout, bool pair = true);  // pair: 64 -> 64-cout 3x3 layers on k_conv3_pair
 
@@ -60,7 +61,9 @@ ConvTiling plan_conv(int ks, int stride, int cin, int cout, int Hout, int Wout, 
 std::vector<bf16_t> pack_conv_weights(const float *w_oihw, int cout, int cin, int ks, const ConvTiling &t,
                                       const int *cout_perm /* optional: logical cout -> source row */, int in_u8, bool f16);
 
-int conv_ksteps(int ks, int CK);
+int conv_ksteps(int ks, int CK);  // (c16::ksteps, convgeom.h)
+// elements of pack_conv_weights' result
+int64_t conv_packed_elems(int cout, int cin, int ks, const ConvTiling &t, int in_u8);
 size_t conv_lds_bytes(const ConvLaunch &L);
 bool conv_tail_supported(int ks, int MF, int NF, int cout1, int cout2, bool act16 = false, int TH = 0);
 // NI (images per tile) for a launch planned on the generic small-map tile, or 1: the shapes the multi-image form has a kernel path for

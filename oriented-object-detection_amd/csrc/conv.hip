@@ -18,12 +18,12 @@
 //   * the network input layer reads the uint8 NHWC tile directly (BGR->RGB + /255 via a 256-entry LUT = exactly
 //     bf16(v/255)), i.e. the predictor's preprocess is fused into conv0.
 #include "conv.h"
+#include "convgeom.h"
+#include "convparams.h"
+#include "convvariants.h"
 #include "launchcfg.h"
 
-#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 namespace obb {
@@ -45,32 +45,6 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #endif
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;  // native vector: stays in registers where HIP's uint4 struct may not
 
-struct ConvParams {
-    const void *in; int64_t in_bs; int in_cs, in_co;
-    void *out; int64_t out_bs; int out_cs, out_co;
-    const bf16_t *res; int64_t res_bs; int res_cs, res_co;
-    // channel-blocked addressing (TensorRef::cpb): chunk cc of a pixel lives at (cc >> bsh) * ps + pixel * pp + (cc & bmask) * 8 elements;
-    // plain NHWC is the degenerate case bsh = 31, bmask = ~0, pp = cs
-    int in_bsh, in_bmask; unsigned in_ps2 /*bytes*/;
-    int out_bsh, out_bmask; int64_t out_ps;
-    int res_bsh, res_bmask; int64_t res_ps;
-    const bf16_t *wpk; const float *bias; const bf16_t *lut;
-    int Hin, Win, Hout, Wout, cin, cout, stride, act, flip_bgr;
-    int TH, TW, CK, sh /*log2(CK/8)*/, tiles_x, tiles_y, nstage, kst, out_hw, act_bytes;
-    int tpw, ntiles;  // consecutive pixel tiles per workgroup; total pixel tiles (batch included)
-    int NI, B;        // NI > 1: a tile = NI whole images of a small map (TH x TW = the map: the 4 x 4 level of the 128-px scale), B images in all
-    int gx, ncb;      // workgroups along the tile axis; cout blocks
-    unsigned in_span_bytes, w_bytes;  // buffer-descriptor ranges: bytes of one image's input slice span; bytes of the packed weights
-    // 1x1 over a virtual concat [nearest-x2 upsample of a low-res tensor | full-res tensor] (1-D launches only): channels [0, up_c) come
-    // from `in` (low-res NHWC slice, pixel (b, y/2, x/2)), the rest from `in2`; neither the upsampled tensor nor the concat is ever stored
-    const void *in2; int in2_cs, in2_co; unsigned in2_span_bytes; int up_c, up_W, up_HW;
-    // fused trailing 1x1 conv (TAIL): out2[pixel][cout2] = W2 . y[pixel][0 .. 16*NF) + bias2, fp32 rows of the head tensor
-    const bf16_t *w2pk; const float *bias2; float *out2; int64_t out2_bs; int out2_cs, out2_co, out2_hw, cout2, kst2, w2_off;
-    unsigned long long *stamps;  // diagnostic build (-DOBB_STAMPS) only
-    int dbg;  // timing experiments only (OBB_CONV_DBG): 1 skip MFMA loop, 2 skip activation loads, 4 skip SiLU, 8 skip stores, 16 skip weight loads
-    float inv_twin, inv_tw;
-};
-
 // TAIL > 0: the layer is followed by a plain 1x1 conv (no activation) whose output goes to the head tensor: that second GEMM runs
 // on the staged 16-bit output tile while it is still in LDS (TAIL = its NF), and the intermediate tensor is never written.
 // VCAT: 1x1 over a virtual [upsample | skip] concat (ConvParams::up_c); a separate instantiation so that the plain kernels stay branch-free
@@ -84,9 +58,8 @@ struct ConvParams {
 // NIT: multi-image tiles (ConvParams::NI > 1) -- a separate instantiation of the one shape that has them (3x3, one fragment per wave, 64-cout
 // groups, register-direct stores), so that the index arithmetic of the form costs the other variants, all at their register caps, nothing.
 template <int KS, int MF, int NF, bool IN_U8, bool OUT_F32, bool F16, int TAIL = 0, bool VCAT = false, bool T16 = false, bool WRES = false, bool NIT = false>
-// Register budget: the 64-cout 3x3 variants need ~210 VGPRs (two waves per SIMD); everything else fits 168 without spills, which is the
-// difference between two and three resident waves per SIMD (allocation granule 8: 170 registers already drop to two).
-__global__ __launch_bounds__(256, WRES ? 1 : ((NF == 4 && (KS == 3 ? MF >= 2 : MF == 3)) ? 2 : 3)) void k_conv_igemm(const ConvParams P) {
+// Register budget: c16::two_waves (convgeom.h) names the variants that run two waves per SIMD; everything else runs three.
+__global__ __launch_bounds__(c16::kNT, WRES ? 1 : (c16::two_waves(KS, MF, NF) ? 2 : 3)) void k_conv_igemm(const ConvParams P) {
     typedef typename HX<F16>::vec8 hx8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ __attribute__((aligned(16))) bf16_t s_lut[IN_U8 ? 256 : 8];  // u8 -> half(v/255); sized in multiples of 16 B (statics precede the dynamic region)
@@ -94,9 +67,9 @@ __global__ __launch_bounds__(256, WRES ? 1 : ((NF == 4 && (KS == 3 ? MF >= 2 : M
     const int g = lane >> 4, pl = lane & 15;
     constexpr int PAD = KS / 2;
     const int S = P.stride;
-    const int THin = (P.TH - 1) * S + KS, TWin = (P.TW - 1) * S + KS;
-    const int PST = IN_U8 ? 16 : P.CK * 2 + 16;  // bytes per staged pixel (+16 B pad spreads consecutive pixels over LDS banks; the
-                                                 // 8-channel input layer packs pixels densely: twice the groups per CU)
+    const int THin = c16::tile_in(P.TH, S, KS), TWin = c16::tile_in(P.TW, S, KS);
+    constexpr int PST_U8 = c16::pix_pitch(true, 8);
+    const int PST = IN_U8 ? PST_U8 : c16::pix_pitch(false, P.CK);  // bytes per staged pixel (the uint8 form's as a constant the front end sees)
     const int cpk = P.CK >> 3;
     const int nq = (KS == 3 ? 9 : 1) * cpk;
     const int in_px1 = THin * TWin;      // staged pixels of one image
@@ -137,7 +110,7 @@ __global__ __launch_bounds__(256, WRES ? 1 : ((NF == 4 && (KS == 3 ? MF >= 2 : M
         ptyx[mf] = ok ? ((il << 24) | (ty << 16) | tx) : -1;
     }
     // staging plan: this thread moves the 16-B chunks idx = tid + k*256 of the [in_px][CK] tile
-    constexpr int MAXLD = WRES ? 8 : ((KS == 1) ? 4 : 6);
+    constexpr int MAXLD = c16::maxld(WRES, KS);
     constexpr unsigned NOPIX = 0xffffffffu;
     int ipos[MAXLD];  // (iy << 16 | ix) inside the input tile, or -1
     if constexpr (!IN_U8) {
@@ -154,7 +127,7 @@ __global__ __launch_bounds__(256, WRES ? 1 : ((NF == 4 && (KS == 3 ? MF >= 2 : M
     }
     const int cbase = cb * 16 * NF + g * 4 * NF;
     const bool do_act = P.act && !(P.dbg & 4);
-    constexpr bool DBUF = NF == 4 && (KS == 3 ? MF >= 2 : MF == 3);  // the two-waves-per-SIMD register class (see __launch_bounds__)
+    constexpr bool DBUF = c16::two_waves(KS, MF, NF);  // the two-waves-per-SIMD register class (see __launch_bounds__)
     // 64-cout groups store their 16-bit outputs straight from registers: a lane's 16 couts are 32 contiguous bytes and the four lanes of a
     // pixel a whole 128-B row piece (or one 32-B row of four channel-blocked planes) -- nothing left for an LDS transpose to coalesce
     constexpr bool DIRECT = NF == 4 && TAIL == 0 && !OUT_F32 && !IN_U8;
@@ -410,7 +383,7 @@ __global__ __launch_bounds__(256, WRES ? 1 : ((NF == 4 && (KS == 3 ? MF >= 2 : M
 
         // ---- epilogue: lane owns couts [cbase, cbase + 4*NF) of its pixels: + bias, SiLU, + residual
         const bool full = (cbase + 4 * NF <= P.cout);
-        constexpr int ROWB = 32 * NF + 16;  // staged output row: 16*NF halves + 16 B pad
+        constexpr int ROWB = c16::out_row_bytes(NF);  // staged output row: 16*NF halves + 16 B pad
         // coalesced write-out of the staged 16-bit tile: consecutive lanes store consecutive 16-B pieces of a pixel's output row
         // (CPP = 16-B chunks per pixel, occ0 = first 8-channel chunk of this group inside the output slice)
         auto write_out = [&](auto cpp_c, int cout_o, int occ0) {
@@ -631,9 +604,10 @@ template <bool F16, int TAIL, int S, int NF = 4>
 __global__ __launch_bounds__(512, 1) void k_conv3_pair(const ConvParams P) {
     typedef typename HX<F16>::vec8 hx8;
     static_assert(NF == 4 || (NF == 5 && TAIL == 0 && S == 1), "merged 80-cout form: plain stride-1 layers only");
-    constexpr int MF = S == 1 ? 3 : 1, PST = 144, KST = 18, TH = S == 1 ? 13 : 4, T = 13, THIN = (TH - 1) * S + 3, TWIN = (T - 1) * S + 3;
-    constexpr int IN_PX = THIN * TWIN, NCHUNK = IN_PX * 8, MAXLD = 8, TF = TAIL > 0 ? 4 : 0;  // TF: cout fragments of the tail
-    static_assert(NCHUNK <= MAXLD * 256, "staging plan");
+    // (64 input channels as one resident stage: the geometry of the WRES form of k_conv_igemm at CK = 64)
+    constexpr int MF = S == 1 ? 3 : 1, PST = c16::pix_pitch(false, 64), KST = c16::ksteps(3, 64), TH = S == 1 ? 13 : 4, T = 13, THIN = c16::tile_in(TH, S, 3), TWIN = c16::tile_in(T, S, 3);
+    constexpr int IN_PX = THIN * TWIN, NCHUNK = IN_PX * 8, MAXLD = c16::maxld(true, 3), TF = TAIL > 0 ? 4 : 0;  // TF: cout fragments of the tail
+    static_assert(NCHUNK == c16::stage_chunks(1, TH, T, S, 3, 64) && NCHUNK <= c16::chunk_cap(true, 3), "staging plan");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ __attribute__((aligned(16))) float s_bias[16 * NF];
     __shared__ __attribute__((aligned(16))) float s_bias2[TAIL > 0 ? 64 : 4];
@@ -647,7 +621,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3_pair(const ConvParams P) {
     if (bx >= P.gx) return;
     char *abuf = smem + h * P.act_bytes;
     char *wlds = smem + 2 * P.act_bytes;
-    char *w2lds = wlds + KST * NF * 1024;
+    char *w2lds = wlds + c16::stage_weight_bytes(KST, NF);
     if (tid < 16 * NF) s_bias[tid] = P.bias[cb * 16 * NF + tid];
     if constexpr (TAIL > 0) {
         if (tid < 64) s_bias2[tid] = P.bias2[tid];
@@ -911,216 +885,54 @@ __global__ __launch_bounds__(512, 1) void k_conv3_pair(const ConvParams P) {
     STAMP_FLUSH
 }
 
-// ------------------------------------------------------------------------------------------------ host side
+// ------------------------------------------------------------------------------------------------ launch
+//
+// The host half -- planner, packer, argument checks, kernel parameters, which variant a launch asks for -- is convplan.hip; the
+// variants that exist are the rows of convvariants.h, expanded here into the kernels themselves.
 
-static int ilog2(int v) { int s = 0; while ((1 << s) < v) ++s; return s; }
+typedef void (*ConvKernel)(const ConvParams);
 
-int conv_ksteps(int ks, int CK) { return ((ks == 3 ? 9 : 1) * (CK / 8) + 3) / 4; }
-
-ConvTiling plan_conv(int ks, int stride, int cin, int cout, int Hout, int Wout, bool pair) {
-    ConvTiling t;
-    t.NF = cout <= 16 ? 1 : (cout <= 32 ? 2 : 4);
-    if (ks == 1) {
-        // 1x1: the whole batch is one long pixel row (caller passes Hout = 1, Wout = B*H*W)
-        static const int ck1 = getenv("OBB_CK1") ? atoi(getenv("OBB_CK1")) : 64;
-        t.TH = 1; t.MF = 2; t.TW = 64 * t.MF;
-        t.CK = cin >= 128 ? std::min(ck1, 64) : (cin >= 64 ? 64 : 32);
-        return t;
+static ConvKernel conv_kernel(const ConvVariant &V) {
+    switch (conv_variant_key(V)) {
+#define X(F16, TAIL, S, NF) \
+    case conv_pair_key(F16, TAIL, S, NF): return k_conv3_pair<F16, TAIL, S, NF>;
+        OBB_CONV_PAIR_VARIANTS(X)
+#undef X
+#define X(KS, MF, NF, IN_U8, OUT_F32, F16, TAIL, VCAT, T16, WRES, NIT) \
+    case conv_igemm_key(KS, MF, NF, IN_U8, OUT_F32, F16, TAIL, VCAT, T16, WRES, NIT): return k_conv_igemm<KS, MF, NF, IN_U8, OUT_F32, F16, TAIL, VCAT, T16, WRES, NIT>;
+        OBB_CONV_IGEMM_VARIANTS(X)
+#undef X
     }
-    int cin8 = (cin + 7) / 8 * 8;
-    if (Hout % 13 == 0 && Wout % 13 == 0) { t.TH = 13; t.TW = 13; t.MF = 3; }
-    else if (Hout >= 16 && Wout >= 16) { t.TH = 8; t.TW = 16; t.MF = 2; }
-    else { t.TH = 8; t.TW = 8; t.MF = 1; }
-    static const int ck3 = getenv("OBB_CK3") ? std::min(atoi(getenv("OBB_CK3")), 16) : 16;  // weights stage = 5 * NF KiB
-    int ck = 1;
-    while (ck * 2 <= cin8 && ck * 2 <= ck3) ck *= 2;  // power of two <= min(cin8, ck3)
-    if (ck < 8) ck = 8;
-    if (stride == 2 && ck > 16) ck = 16;             // keep the (2T+1)^2 halo tile small enough for several groups per CU
-    t.CK = ck;
-    // weights-resident single-stage form (WRES): 3x3 stride 1 on 13 x 13 tiles with 32 or 64 input channels
-    // (measured per 256 tiles: 64 -> 16 couts at 52^2 60.9 -> 50.4 us, 64 -> 32 at 26^2 24.6 -> 23.6 us; the 64-cout groups (104 KiB of LDS, one
-    //  group per CU) gained nothing -- 112.6 -> 115.7 us -- so they keep the 16-channel stages: their k loop is bound by LDS operand
-    //  reads, 7 KiB per 12 MFMAs and wave, not by the per-stage global-memory latency)
-    if (stride == 1 && t.MF == 3 && (cin == 32 || cin == 64) && (t.NF == 2 || t.NF == 1)) t.CK = cin;
-    // 64 -> 64-cout groups: the same single-stage packing, run by k_conv3_pair (two half-groups per CU sharing the resident weights)
-    if (pair && stride == 1 && t.MF == 3 && cin == 64 && t.NF == 4) t.CK = 64;
-    // stride 2, 64 input channels: 4-row stripes of 13 outputs per half-group (one fragment per wave), same packing
-    if (pair && stride == 2 && cin == 64 && t.NF == 4 && Wout % 13 == 0 && Hout >= 4) { t.TH = 4; t.TW = 13; t.MF = 1; t.CK = 64; }
-    return t;
+    return nullptr;
 }
-
-std::vector<bf16_t> pack_conv_weights(const float *w, int cout, int cin, int ks, const ConvTiling &t, const int *perm, int in_u8, bool f16) {
-    const int CK = t.CK, NF = t.NF, cpk = CK / 8;
-    const int cin_eff = in_u8 ? 8 : cin;
-    const int nstage = (cin_eff + CK - 1) / CK;
-    const int kst = conv_ksteps(ks, CK);
-    const int ncb = (cout + 16 * NF - 1) / (16 * NF);
-    const int taps = ks * ks;
-    std::vector<bf16_t> out((size_t)ncb * nstage * kst * NF * 64 * 8, 0);
-    size_t o = 0;
-    for (int cb = 0; cb < ncb; ++cb)
-        for (int st = 0; st < nstage; ++st)
-            for (int k = 0; k < kst; ++k)
-                for (int f = 0; f < NF; ++f)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        int r = lane & 15, gq = lane >> 4;
-                        int co = cb * 16 * NF + (r >> 2) * 4 * NF + f * 4 + (r & 3);
-                        int q = k * 4 + gq;
-                        int tap = (ks == 3) ? q / cpk : 0;
-                        int c0 = (ks == 3) ? (q % cpk) * 8 : q * 8;
-                        for (int j = 0; j < 8; ++j, ++o) {
-                            int c = st * CK + c0 + j;
-                            bool ok = co < cout && c < cin && tap < taps && (ks == 3 || c0 < CK);
-                            if (!ok) continue;
-                            int src = perm ? perm[co] : co;
-                            out[o] = host_to_half(w[((size_t)src * cin + c) * taps + tap], f16);
-                        }
-                    }
-    return out;
-}
-
-static bool conv_multi_stage(const ConvLaunch &L) { return (L.in_u8 ? 8 : L.cin) > L.CK; }
-static bool conv_wres(const ConvLaunch &L) { return L.ks == 3 && L.CK > 16; }
-static int tail_nf(int cout2);
-// k_conv3_pair's shapes (plan_conv gives them CK = 64): everything else with CK = 64 stays on the one-group WRES form of k_conv_igemm
-static bool conv_pair(const ConvLaunch &L) {
-    if (L.ks != 3 || L.NF != 4 || L.CK != 64 || L.cin != 64 || L.TW != 13 || L.in_u8 || L.out_f32 || L.res.p || L.up_c != 0) return false;
-    if (L.cout == 80) return L.stride == 1 && L.MF == 3 && L.TH == 13 && L.tail_cout == 0;  // two merged siblings, 64 + 16 couts: one group of five fragments
-    if (L.cout % 64) return false;
-    if (L.stride == 1)
-        return L.MF == 3 && L.TH == 13 && (L.tail_cout == 0 || (!L.tail_act16 && tail_nf(L.tail_cout) == 4 && L.cout == 64 && L.tail_cout % 4 == 0 && L.tail_out_hw == 0 &&
-                                                                ((L.tail_out.cs | L.tail_out.co) & 3) == 0));
-    return L.stride == 2 && L.MF == 1 && L.TH == 4 && (L.tail_cout == 0 || (L.tail_act16 && L.tail_cout == 64 && L.cout == 64));
-}
-
-// LDS layout: [input tile (one channel stage) | weights of the stage].  The epilogue's output staging starts at offset 0; for
-// multi-stage layers it may run over the weights as well (they are re-staged at every stage anyway), single-stage layers keep
-// their weights resident across tiles, so there the staging area must fit in front of them.
-static size_t conv_act_bytes(const ConvLaunch &L) {
-    int THin = (L.TH - 1) * L.stride + L.ks, TWin = (L.TW - 1) * L.stride + L.ks;
-    size_t in_tile = (size_t)std::max(1, L.NI) * THin * TWin * (L.in_u8 ? 16 : L.CK * 2 + 16);
-    size_t out_tile = L.out_f32 ? 0 : (size_t)64 * L.MF * (32 * L.NF + 16);
-    size_t a = conv_multi_stage(L) ? in_tile : std::max(in_tile, out_tile);
-    return (a + 15) / 16 * 16;
-}
-
-static size_t conv_main_lds(const ConvLaunch &L) {
-    size_t out_tile = L.out_f32 ? 0 : (size_t)64 * L.MF * (32 * L.NF + 16);
-    return (std::max(conv_act_bytes(L) + (size_t)conv_ksteps(L.ks, L.CK) * L.NF * 1024, out_tile) + 15) / 16 * 16;
-}
-
-static int tail_nf(int cout2) { return cout2 <= 16 ? 1 : (cout2 <= 32 ? 2 : 4); }
-
-size_t conv_lds_bytes(const ConvLaunch &L) {
-    size_t t = L.tail_cout > 0 ? (size_t)conv_ksteps(1, 16 * L.NF) * tail_nf(L.tail_cout) * 1024 : 0;  // tail weights behind everything else
-    return conv_main_lds(L) + t;
-}
-
-int conv_ni_supported(const ConvLaunch &L) {
-    // the register-direct store path of k_conv_igemm (64-cout groups, no tail, 16-bit plain-NHWC output) on the one-fragment-per-wave tile
-    if (L.ks != 3 || L.NF != 4 || L.MF != 1 || L.in_u8 || L.out_f32 || L.tail_cout > 0 || L.up_c > 0 || L.CK > 16) return 1;  // (channel-blocked slices included: an image is one stride inside every block plane)
-    if (L.Hout != L.Wout || (L.Hout != 4 && L.Hout != 2)) return 1;
-    return 64 / (L.Hout * L.Wout);
-}
-
-bool conv_tail_supported(int ks, int MF, int NF, int cout1, int cout2, bool act16, int TH) {
-    if (cout1 != 16 * NF || cout2 < 1 || cout2 > 64) return false;
-    const int nf2 = tail_nf(cout2);
-    if (act16 && ks == 3 && MF == 1 && NF == 4 && TH == 4) return cout2 == 64;  // k_conv3_pair, stride-2 stripes
-    if (act16) return ks == 3 && MF == 3 && (NF == 2 || NF == 4) && nf2 == NF && cout2 == 16 * nf2;  // whole 16-bit rows of the staging area
-    return (ks == 3 && MF == 3 && NF == 4 && nf2 == 4) || (ks == 3 && MF == 3 && NF == 1 && nf2 == 1) || (ks == 1 && MF == 2 && NF == 4 && nf2 == 1);
-}
-
-template <typename K>
-static hipError_t launch_big_lds(K kernel, const ConvParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    // (every k_conv_igemm instantiation has the same function-pointer type, so K does not tell them apart: the cap is kept per device and kernel address)
-    hipError_t e = allow_dyn_lds((const void *)kernel, 152 * 1024);  // + the static arrays (bias, LUT) <= 160 KiB
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, P);
-    return hipGetLastError();
-}
-
-template <int KS, int MF, int NF, bool F16>
-static hipError_t launch_t2(const ConvLaunch &L, const ConvParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    if constexpr (KS == 3 && MF == 3) {
-        if (conv_wres(L)) {  // weights-resident single-stage form: plain / 16-bit tail (T16) / fp32 head tail
-            if (L.tail_cout > 0 && L.tail_act16) return hipErrorInvalidValue;  // (the fused cv1 sits behind stride-2 convs only)
-            if (L.tail_cout > 0) {
-                constexpr int T = NF == 4 ? 4 : 1;
-                if constexpr (NF == 4 || NF == 1) {
-                    if (tail_nf(L.tail_cout) != T) return hipErrorInvalidValue;
-                    return launch_big_lds(k_conv_igemm<KS, MF, NF, false, false, F16, T, false, false, true>, P, grid, lds, st);
-                } else return hipErrorInvalidValue;
-            }
-            return launch_big_lds(k_conv_igemm<KS, MF, NF, false, false, F16, 0, false, false, true>, P, grid, lds, st);
-        }
-    }
-    if (L.tail_cout > 0 && L.tail_act16) {  // stride-2 backbone conv + the cv1 of the following C3k2 block
-        if constexpr (KS == 3 && MF == 3 && (NF == 2 || NF == 4)) {
-            if (L.in_u8 || L.out_f32 || tail_nf(L.tail_cout) != NF) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, false, F16, NF, false, true>), grid, dim3(256), lds, st, P);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if (L.tail_cout > 0) {  // only the three shapes of the OBB head are instantiated (conv_tail_supported)
-        constexpr int T = (KS == 3 && MF == 3 && NF == 4) ? 4 : 1;
-        if constexpr ((KS == 3 && MF == 3 && (NF == 4 || NF == 1)) || (KS == 1 && MF == 2 && NF == 4)) {
-            if (L.in_u8 || L.out_f32 || tail_nf(L.tail_cout) != T) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, false, F16, T>), grid, dim3(256), lds, st, P);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if (L.up_c > 0) {  // virtual upsample-concat input: one shape (the 1x1 convs behind Upsample + Concat in the neck)
-        if constexpr (KS == 1 && MF == 2 && NF == 4) {
-            if (L.in_u8 || L.out_f32) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, false, F16, 0, true>), grid, dim3(256), lds, st, P);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
-    }
-    if (L.in_u8) {
-        if constexpr (KS == 3) hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, true, false, F16>), grid, dim3(256), lds, st, P);
-        else return hipErrorInvalidValue;
-    } else if (L.out_f32) hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, true, F16>), grid, dim3(256), lds, st, P);
-    else if (P.NI > 1) {
-        if constexpr (KS == 3 && MF == 1 && NF == 4) hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, false, F16, 0, false, false, false, true>), grid, dim3(256), lds, st, P);
-        else return hipErrorInvalidValue;
-    } else hipLaunchKernelGGL((k_conv_igemm<KS, MF, NF, false, false, F16>), grid, dim3(256), lds, st, P);
-    return hipGetLastError();
-}
-
-template <int KS, int MF, int NF>
-static hipError_t launch_t(const ConvLaunch &L, const ConvParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    return L.f16 ? launch_t2<KS, MF, NF, true>(L, P, grid, lds, st) : launch_t2<KS, MF, NF, false>(L, P, grid, lds, st);
-}
-
-template <int KS, int MF>
-static hipError_t launch_nf(const ConvLaunch &L, const ConvParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    switch (L.NF) {
-        case 1: return launch_t<KS, MF, 1>(L, P, grid, lds, st);
-        case 2: return launch_t<KS, MF, 2>(L, P, grid, lds, st);
-        case 4: return launch_t<KS, MF, 4>(L, P, grid, lds, st);
-    }
-    return hipErrorInvalidValue;
-}
-
-static hipError_t launch_conv_impl(const ConvLaunch &L, hipStream_t st, unsigned long long **stamps_out);
 
 hipError_t launch_conv(const ConvLaunch &L, hipStream_t st) {
-    unsigned long long *sd = nullptr;
-    hipError_t e = launch_conv_impl(L, st, &sd);
+    ConvParams P;
+    ConvVariant V;
+    unsigned grid_x = 0, threads = 0;
+    size_t lds = 0;
+    hipError_t e = conv_params(L, P, V, grid_x, threads, lds);
+    if (e != hipSuccess) return e;
+    const ConvKernel kernel = conv_kernel(V);
+    if (!kernel) return hipErrorInvalidValue;  // (a guard only: conv_params has refused a variant without a row, and both switches expand the same list)
+    // (every k_conv_igemm instantiation has the same function-pointer type: the cap is kept per device and kernel address)
+    const int cap = conv_variant_lds_cap(V);
+    if (cap > c16::kLdsDefault && (e = allow_dyn_lds((const void *)kernel, (size_t)cap)) != hipSuccess) return e;
 #ifdef OBB_STAMPS
-    if (e == hipSuccess && sd) {  // diagnostic build: synchronise and print this launch's phase sums (cycles per wave and tile)
+    static unsigned long long *stamp_dev = nullptr;
+    if (!stamp_dev) (void)hipMalloc((void **)&stamp_dev, 64);
+    (void)hipMemsetAsync(stamp_dev, 0, 64, st);
+    P.stamps = stamp_dev;
+#endif
+    hipLaunchKernelGGL(kernel, dim3(grid_x), dim3(threads), lds, st, P);
+    e = hipGetLastError();
+#ifdef OBB_STAMPS
+    if (e == hipSuccess) {  // diagnostic build: synchronise and print this launch's phase sums (cycles per wave and tile)
         unsigned long long h[8];
         (void)hipStreamSynchronize(st);
-        (void)hipMemcpy(h, sd, 64, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(h, stamp_dev, 64, hipMemcpyDeviceToHost);
         const double n = h[5] ? (double)h[5] : 1.0;
-        if (conv_pair(L))
+        if (V.pair)
             fprintf(stderr, "STAMPS pair k%d s%d cin%d cout%d out%dx%d tail%d | per wave-tile cycles: barrier %.0f  epilogue %.0f  lds_copy %.0f  kloop %.0f  fetch_issue %.0f  (wave-tiles %.0f)\n",
                     L.ks, L.stride, L.cin, L.cout, L.Hout, L.Wout, L.tail_cout, h[0] / n, h[1] / n, h[2] / n, h[3] / n, h[4] / n, n);
         else
@@ -1129,160 +941,6 @@ hipError_t launch_conv(const ConvLaunch &L, hipStream_t st) {
     }
 #endif
     return e;
-}
-
-static hipError_t launch_conv_impl(const ConvLaunch &L, hipStream_t st, unsigned long long **stamps_out) {
-    ConvParams P;
-    P.in = L.in.p; P.in_bs = L.in.bs; P.in_cs = L.in.cs; P.in_co = L.in.co;
-    P.out = L.out.p; P.out_bs = L.out.bs; P.out_cs = L.out.cs; P.out_co = L.out.co;
-    P.res = (const bf16_t *)L.res.p; P.res_bs = L.res.bs; P.res_cs = L.res.cs; P.res_co = L.res.co;
-    P.in_bsh = P.out_bsh = P.res_bsh = 31;
-    P.in_bmask = P.out_bmask = P.res_bmask = 0x7fffffff;
-    P.in_ps2 = 0; P.out_ps = 0; P.res_ps = 0;
-    int64_t in_block_span = 0;  // blocked input: elements from the slice's first block to the end of its last block (one image)
-    {
-        auto blocked = [](const TensorRef &T, int C, int &bsh, int &bmask, int64_t &ps, int &co, int &cs, int64_t *span) -> bool {
-            if (T.cpb <= 0) return true;
-            const int blk = 8 * T.cpb;
-            if ((T.cpb & (T.cpb - 1)) || T.co % blk || T.cs != blk) return false;
-            bsh = 0;
-            while ((1 << bsh) < T.cpb) ++bsh;
-            bmask = T.cpb - 1;
-            ps = T.ps;
-            if (span) *span = (int64_t)((C + blk - 1) / blk - 1) * T.ps;
-            co = 0;  // the slice offset is a whole number of blocks: folded into the base pointer by the caller below
-            return true;
-        };
-        int64_t ps_in = 0;
-        int co_in = P.in_co, cs_in = P.in_cs;
-        if (!L.in_u8) {
-            if (!blocked(L.in, L.cin, P.in_bsh, P.in_bmask, ps_in, co_in, cs_in, &in_block_span)) return hipErrorInvalidValue;
-            if (L.in.cpb > 0) {
-                if (ps_in * 2 >= (1ll << 32)) return hipErrorInvalidValue;
-                P.in = (const bf16_t *)L.in.p + (int64_t)(L.in.co / (8 * L.in.cpb)) * L.in.ps;
-                P.in_co = 0;
-                P.in_ps2 = (unsigned)(ps_in * 2);
-            }
-        } else if (L.in.cpb > 0) return hipErrorInvalidValue;
-        int co_out = P.out_co, cs_out = P.out_cs;
-        if (!blocked(L.out, L.cout, P.out_bsh, P.out_bmask, P.out_ps, co_out, cs_out, nullptr) || (L.out.cpb > 0 && L.out_f32)) return hipErrorInvalidValue;
-        if (L.out.cpb > 0) { P.out = (bf16_t *)L.out.p + (int64_t)(L.out.co / (8 * L.out.cpb)) * L.out.ps; P.out_co = 0; }
-        int co_res = P.res_co, cs_res = P.res_cs;
-        if (L.res.p) {
-            if (!blocked(L.res, L.cout, P.res_bsh, P.res_bmask, P.res_ps, co_res, cs_res, nullptr)) return hipErrorInvalidValue;
-            if (L.res.cpb > 0) { P.res = (const bf16_t *)L.res.p + (int64_t)(L.res.co / (8 * L.res.cpb)) * L.res.ps; P.res_co = 0; }
-        }
-    }
-    if (!L.lut) return hipErrorInvalidValue;  // also the sink of the unconditional stores (lut + 512 B .. + 1.5 KiB): never NULL
-    P.wpk = L.wpk; P.bias = L.bias; P.lut = L.lut;
-    P.Hin = L.Hin; P.Win = L.Win; P.Hout = L.Hout; P.Wout = L.Wout;
-    P.cin = L.cin; P.cout = L.cout; P.stride = L.stride; P.act = L.act; P.flip_bgr = L.flip_bgr;
-    P.TH = L.TH; P.TW = L.TW; P.CK = L.CK; P.sh = ilog2(L.CK / 8);
-    P.tiles_x = L.tiles_x; P.tiles_y = L.tiles_y; P.out_hw = L.out_hw; P.act_bytes = (int)conv_act_bytes(L);
-    const int NI = std::max(1, L.NI);
-    P.NI = NI; P.B = L.B;
-    if (NI > 1 && (NI != conv_ni_supported(L) || L.TH != L.Hout || L.TW != L.Wout || L.tiles_x != 1 || L.tiles_y != 1 || L.out_hw)) return hipErrorInvalidValue;
-#if defined(OBB_STAMPS) || defined(OBB_DIAG)  // timing-only ablations exist in the diagnostic build alone (tools/stamp_conv.sh): the product library ignores the variable
-    static const int dbg = getenv("OBB_CONV_DBG") ? atoi(getenv("OBB_CONV_DBG")) : 0;
-    P.dbg = dbg;
-#else
-    P.dbg = 0;
-#endif
-    P.stamps = nullptr;
-#ifdef OBB_STAMPS
-    static unsigned long long *stamp_dev = nullptr;
-    if (!stamp_dev) (void)hipMalloc((void **)&stamp_dev, 64);
-    (void)hipMemsetAsync(stamp_dev, 0, 64, st);
-    P.stamps = stamp_dev;
-    *stamps_out = stamp_dev;
-#endif
-    P.in2 = L.in2.p; P.in2_cs = L.in2.cs; P.in2_co = L.in2.co; P.up_c = L.up_c; P.up_W = L.up_W; P.up_HW = L.up_HW; P.in2_span_bytes = 0;
-    if (L.up_c > 0) {  // virtual [upsample | skip] concat: 1-D 1x1 launches over plain NHWC sources only
-        if (L.ks != 1 || L.in_u8 || L.B != 1 || L.Hin != 1 || L.in.cpb || L.in2.cpb || !L.in2.p || L.up_c % L.CK || L.up_c >= L.cin || (L.up_W & 1) ||
-            (L.up_HW % L.up_W) || ((L.up_HW / L.up_W) & 1) || L.Win % L.up_HW)
-            return hipErrorInvalidValue;
-        int64_t s2 = ((int64_t)L.Win * L.in2.cs - L.in2.co) * 2, s1 = ((int64_t)(L.Win / 4) * L.in.cs - L.in.co) * 2;
-        if (s1 <= 0 || s2 <= 0 || s1 >= (1ll << 32) - 65536 || s2 >= (1ll << 32) - 65536) return hipErrorInvalidValue;
-        P.in2_span_bytes = (unsigned)s2;
-    }
-    P.w2pk = L.tail_wpk; P.bias2 = L.tail_bias; P.out2 = (float *)L.tail_out.p; P.out2_bs = L.tail_out.bs; P.out2_cs = L.tail_out.cs;
-    P.out2_co = L.tail_out.co; P.out2_hw = L.tail_out_hw; P.cout2 = L.tail_cout; P.kst2 = conv_ksteps(1, 16 * L.NF);
-    P.w2_off = (int)conv_main_lds(L);
-    if (L.tail_cout > 0 && (!conv_tail_supported(L.ks, L.MF, L.NF, L.cout, L.tail_cout, L.tail_act16, L.TH) || !L.tail_wpk || !L.tail_bias || (!L.tail_act16 && !L.tail_out.p))) return hipErrorInvalidValue;
-
-    int cin_eff = L.in_u8 ? 8 : L.cin;
-    P.nstage = (cin_eff + L.CK - 1) / L.CK;
-    P.kst = conv_ksteps(L.ks, L.CK);
-    {
-        int64_t span = ((int64_t)L.Hin * L.Win * L.in.cs - L.in.co) * 2;  // from the slice's first element to the end of the image
-        if (L.in.cpb > 0) span = (in_block_span + (int64_t)L.Hin * L.Win * L.in.cs) * 2;  // ... to the end of the slice's last block
-        if (L.up_c > 0) span = ((int64_t)(L.Win / 4) * L.in.cs - L.in.co) * 2;  // the low-res source of a virtual concat
-        span += (int64_t)(NI - 1) * L.in.bs * 2;  // a multi-image tile reads up to the end of its last image
-        int64_t wb = (int64_t)((L.cout + 16 * L.NF - 1) / (16 * L.NF)) * P.nstage * P.kst * L.NF * 1024;
-        if (span <= 0 || span >= (1ll << 32) - 65536 || wb >= (1ll << 31)) return hipErrorInvalidValue;  // 32-bit buffer offsets
-        P.in_span_bytes = (unsigned)span;
-        P.w_bytes = (unsigned)wb;
-        if (conv_wres(L) && !conv_pair(L) && (L.stride != 1 || L.MF != 3 || L.CK != L.cin || (L.cin != 32 && L.cin != 64) || L.in_u8 || L.out_f32 || L.up_c > 0)) return hipErrorInvalidValue;
-    }
-    int TWin = (L.TW - 1) * L.stride + L.ks;
-    P.inv_twin = 1.0f / (float)TWin;
-    P.inv_tw = 1.0f / (float)L.TW;
-    if ((1 << P.sh) != L.CK / 8 || NI * L.TH * L.TW > 64 * L.MF || L.MF < 1 || L.MF > 3) return hipErrorInvalidValue;
-    {
-        int THin = (L.TH - 1) * L.stride + L.ks;
-        if (!L.in_u8 && (int64_t)NI * THin * TWin * (L.CK / 8) > (conv_wres(L) ? 8 : (L.ks == 1 ? 4 : 6)) * 256) return hipErrorInvalidValue;  // staging plan: chunks per thread
-        if (L.ks == 1 && L.CK > 64) return hipErrorInvalidValue;
-    }
-    int ncb = (L.cout + 16 * L.NF - 1) / (16 * L.NF);
-    int64_t ntiles = NI > 1 ? ((int64_t)L.B + NI - 1) / NI : (int64_t)L.B * L.tiles_y * L.tiles_x;
-    if (ntiles >= (1ll << 31)) return hipErrorInvalidValue;
-    P.ntiles = (int)ntiles;
-    if (conv_pair(L)) {  // one 512-thread workgroup per CU, its two halves walking alternate tiles
-        const int nf5 = L.cout == 80 ? 1 : 0;
-        if (nf5) ncb = 1;
-        const int64_t groups = std::max<int64_t>(1, 256 / ncb);
-        P.tpw = (int)std::max<int64_t>(2, (ntiles + groups - 1) / groups);
-        P.gx = (int)((ntiles + P.tpw - 1) / P.tpw); P.ncb = ncb;
-        const size_t lds = 2 * (size_t)P.act_bytes + (size_t)P.kst * (L.NF + nf5) * 1024 + (L.tail_cout > 0 ? 2 * 4 * 1024 : 0);
-        if (P.kst != 18 || P.nstage != 1 || lds > 158 * 1024) return hipErrorInvalidValue;
-        const dim3 grid((unsigned)((P.gx + 7) / 8 * 8 * ncb));
-        auto go = [&](auto kernel) -> hipError_t {
-            hipError_t e = allow_dyn_lds((const void *)kernel, 158 * 1024);  // + static bias arrays <= 160 KiB
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kernel, grid, dim3(512), lds, st, P);
-            return hipGetLastError();
-        };
-        if (L.stride == 2) {
-            if (L.tail_cout > 0) return L.f16 ? go(k_conv3_pair<true, 16, 2>) : go(k_conv3_pair<false, 16, 2>);
-            return L.f16 ? go(k_conv3_pair<true, 0, 2>) : go(k_conv3_pair<false, 0, 2>);
-        }
-        if (nf5) return L.f16 ? go(k_conv3_pair<true, 0, 1, 5>) : go(k_conv3_pair<false, 0, 1, 5>);
-        if (L.tail_cout > 0) return L.f16 ? go(k_conv3_pair<true, 4, 1>) : go(k_conv3_pair<false, 4, 1>);
-        return L.f16 ? go(k_conv3_pair<true, 0, 1>) : go(k_conv3_pair<false, 0, 1>);
-    }
-    // tiles per workgroup: keep >= ~8 groups per CU in flight, walk up to 8 consecutive tiles per group beyond that
-    static const int tpw_max = getenv("OBB_TPW") ? atoi(getenv("OBB_TPW")) : 8;
-    int64_t tpw = ntiles * ncb / (256 * 8);
-    P.tpw = (int)std::max<int64_t>(1, std::min<int64_t>(tpw, tpw_max));
-    if (conv_wres(L)) P.tpw = (int)std::max<int64_t>(1, std::min<int64_t>(ntiles * ncb / (256 * 2), 16));  // one group per CU: two rounds of groups, <= 16 tiles each
-    P.gx = (int)((ntiles + P.tpw - 1) / P.tpw); P.ncb = ncb;
-    dim3 grid((unsigned)((P.gx + 7) / 8 * 8 * ncb));  // 1-D: see the XCD-aware decoding at the top of the kernel
-    size_t lds = conv_lds_bytes(L);
-    if (lds > (conv_wres(L) ? 152 : 64) * 1024) return hipErrorInvalidValue;
-    if (L.ks == 3) {
-        switch (L.MF) {
-            case 1: return launch_nf<3, 1>(L, P, grid, lds, st);
-            case 2: return launch_nf<3, 2>(L, P, grid, lds, st);
-            case 3: return launch_nf<3, 3>(L, P, grid, lds, st);
-        }
-    } else if (L.ks == 1) {
-        switch (L.MF) {
-            case 1: return launch_nf<1, 1>(L, P, grid, lds, st);
-            case 2: return launch_nf<1, 2>(L, P, grid, lds, st);
-            case 3: return launch_nf<1, 3>(L, P, grid, lds, st);
-        }
-    }
-    return hipErrorInvalidValue;
 }
 
 }  // namespace obb

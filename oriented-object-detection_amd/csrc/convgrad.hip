@@ -334,8 +334,7 @@ int packed_elems(obb_ctx *ctx, const char *fn, int cout, int cin, int ks, int st
     OBB_REQUIRE(ctx, ctx && n_elems && cout > 0 && cin > 0 && (ks == 1 || ks == 3) && H > 0 && W > 0, "%s: bad arguments", fn);
     const int coutL = dgrad_form ? cin : cout, cinL = dgrad_form ? cout : cin;
     const ConvTiling t = plan_conv(ks, stride, cinL, coutL, out_dim(H, stride), out_dim(W, stride), false);
-    const int nstage = (cinL + t.CK - 1) / t.CK, ncb = (coutL + 16 * t.NF - 1) / (16 * t.NF);
-    *n_elems = (int64_t)ncb * nstage * conv_ksteps(ks, t.CK) * t.NF * 64 * 8;
+    *n_elems = conv_packed_elems(coutL, cinL, ks, t, 0);
     return OBB_OK;
 }
 

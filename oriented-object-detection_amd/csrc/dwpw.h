@@ -12,7 +12,7 @@ struct DwPwLaunch {
     void *sink = nullptr;  // >= 1 KiB of device scratch: lanes of the tail without a cout store there (stores stay unconditional)
     const bf16_t *dw_w = nullptr;   // [9][cin] in the storage type
     const float *dw_b = nullptr;    // [cin]
-    const bf16_t *pw_w = nullptr;   // pack_conv_weights(w, 64, cin, 1, {NF = 4, CK = cin})
+    const bf16_t *pw_w = nullptr;   // pack_conv_weights(w, 64, cin, 1, {NF = 4, CK = cin}) (k steps: c16::ksteps, convgeom.h)
     const float *pw_b = nullptr;    // [64]
     const bf16_t *tail_w = nullptr; // pack_dwpw_tail(w2, tail_cout, f16)
     const float *tail_b = nullptr;  // [16]

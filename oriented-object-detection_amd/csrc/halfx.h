@@ -10,6 +10,7 @@ namespace obb {
 
 typedef uint16_t half_bits_t;  // raw 16-bit pattern, interpretation given by the F16 template flag
 
+#if defined(__HIPCC__)  // device helpers: host-only translation units built with the host compiler (convplan.hip) see the conversions below alone
 template <bool F16>
 struct HX;
 
@@ -85,6 +86,8 @@ __device__ __forceinline__ void fma8_mixed(float (&acc)[8], const uint4 &x, cons
 // SiLU with the hardware exp and reciprocal (v_exp_f32 / v_rcp_f32, ~1 ulp): its error is far below the 16-bit storage rounding
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+#endif  // __HIPCC__
+
 // host-side conversions (RNE)
 inline half_bits_t host_to_bf16(float f) {
     uint32_t u;
@@ -92,11 +95,24 @@ inline half_bits_t host_to_bf16(float f) {
     if ((u & 0x7fffffffu) > 0x7f800000u) return (half_bits_t)((u >> 16) | 0x40);
     return (half_bits_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
-inline half_bits_t host_to_f16(float f) {
-    _Float16 h = (_Float16)f;
-    half_bits_t b;
-    __builtin_memcpy(&b, &h, 2);
-    return b;
+// fp16 for a host compiler without _Float16, in integer arithmetic (RNE, subnormals, NaN with the truncated payload);
+// tests/test_halfx_cpu.py holds the two below to the _Float16 conversions, value for value
+inline half_bits_t host_to_f16_int(float f) {
+    uint32_t u;
+    __builtin_memcpy(&u, &f, 4);
+    const uint32_t sign = (u >> 16) & 0x8000u;
+    u &= 0x7fffffffu;
+    if (u > 0x7f800000u) return (half_bits_t)(sign | 0x7e00u | ((u >> 13) & 0x3ffu));
+    if (u >= 0x477ff000u) return (half_bits_t)(sign | 0x7c00u);  // >= 65520 rounds to infinity
+    if (u >= 0x38800000u) {
+        const uint32_t v = u - 0x38000000u;
+        return (half_bits_t)(sign | ((v + 0xfffu + ((v >> 13) & 1u)) >> 13));
+    }
+    if (u <= 0x33000000u) return (half_bits_t)sign;  // <= 2^-25: zero (the tie goes to even)
+    const uint32_t mant = (u & 0x7fffffu) | 0x800000u, shift = 126u - (u >> 23), half = 1u << (shift - 1), rem = mant & ((1u << shift) - 1);
+    uint32_t h = mant >> shift;
+    if (rem > half || (rem == half && (h & 1u))) ++h;
+    return (half_bits_t)(sign | h);
 }
 inline float host_from_bf16(half_bits_t h) {
     uint32_t u = (uint32_t)h << 16;
@@ -104,11 +120,38 @@ inline float host_from_bf16(half_bits_t h) {
     __builtin_memcpy(&f, &u, 4);
     return f;
 }
+inline float host_from_f16_int(half_bits_t b) {
+    const uint32_t sign = (uint32_t)(b & 0x8000u) << 16, e = (b >> 10) & 31u, m = b & 0x3ffu;
+    uint32_t u;
+    if (e == 31) u = sign | 0x7f800000u | (m << 13);
+    else if (e) u = sign | ((e + 112) << 23) | (m << 13);
+    else if (!m) u = sign;
+    else {
+        int s = 0;
+        uint32_t mm = m;
+        while (!(mm & 0x400u)) { mm <<= 1; ++s; }
+        u = sign | ((uint32_t)(113 - s) << 23) | ((mm & 0x3ffu) << 13);
+    }
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+#if defined(__FLT16_MANT_DIG__)
+inline half_bits_t host_to_f16(float f) {
+    _Float16 h = (_Float16)f;
+    half_bits_t b;
+    __builtin_memcpy(&b, &h, 2);
+    return b;
+}
 inline float host_from_f16(half_bits_t b) {
     _Float16 h;
     __builtin_memcpy(&h, &b, 2);
     return (float)h;
 }
+#else
+inline half_bits_t host_to_f16(float f) { return host_to_f16_int(f); }
+inline float host_from_f16(half_bits_t b) { return host_from_f16_int(b); }
+#endif
 inline half_bits_t host_to_half(float f, bool f16) { return f16 ? host_to_f16(f) : host_to_bf16(f); }
 inline float host_from_half(half_bits_t h, bool f16) { return f16 ? host_from_f16(h) : host_from_bf16(h); }
 
