@@ -226,6 +226,26 @@ int obb_conv_dgrad_s2_bf16(obb_ctx *ctx, const uint16_t *dy, const uint16_t *pac
                            uint16_t *dx, obb_stream_t s);
 int obb_conv_wgrad_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *dy, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, float *dw,
                            obb_stream_t s);
+/* The bf16 weights of EVERY dense Conv of `model.train(...)` for one iteration in one launch (Train_OBB.py:796-841: autocast casts each fp32
+ * master weight once per forward; here that cast is the pack of obb_conv_pack_bf16 / obb_conv_s2_pack_bf16, per layer in its forward form and
+ * its dgrad form).  The layers' weights are windows of ONE flat fp32 device buffer and the blobs segments of ONE bf16 device buffer, each
+ * segment starting at a multiple of 256 elements and bit-identical to what the per-layer entry writes.
+ * obb_conv_pack_plan (once per layer list and input size; it copies the table to the device and synchronises): record i = a layer cout[i] x
+ *   cin[i] x ks[i] x ks[i] of stride[i] whose INPUT map is H[i] x W[i], in the form dgrad_form[i] (1: the stride plays no part, as in
+ *   obb_conv_dgrad_s2_bf16), its weights at element src_off[i] of a flat buffer of src_elems elements -> dst_off[i], n_elems[i] (the segment of
+ *   record i in the packed buffer), *total (elements of the packed buffer, a multiple of 256) and, unless `table` is NULL, the device table of
+ *   table_words = OBB_PACK_TABLE_HEAD + nrec * OBB_PACK_TABLE_REC int64 words.
+ * obb_conv_pack_multi_bf16 (every step): ONE kernel launch, no host read, copy, allocation or synchronisation (capturable in a graph).  w_flat /
+ *   w_elems: the flat buffer; table / table_words / nrec and packed / packed_elems as the plan gave them.  A table size that does not match nrec,
+ *   a packed_elems that is no positive multiple of 256 or a NULL pointer is refused with OBB_ERR_INVALID before any launch; a table whose own
+ *   head disagrees with nrec, packed_elems or w_elems (a plan made for other layers or another input size) makes the kernel store nothing. */
+#define OBB_PACK_TABLE_HEAD 4
+#define OBB_PACK_TABLE_REC 8
+int obb_conv_pack_plan(obb_ctx *ctx, int32_t nrec, const int32_t *cout, const int32_t *cin, const int32_t *ks, const int32_t *stride, const int32_t *H,
+                       const int32_t *W, const int32_t *dgrad_form, const int64_t *src_off, int64_t src_elems, int64_t *dst_off, int64_t *n_elems,
+                       int64_t *total, int64_t *table, int64_t table_words, obb_stream_t s);
+int obb_conv_pack_multi_bf16(obb_ctx *ctx, const float *w_flat, int64_t w_elems, const int64_t *table, int64_t table_words, int32_t nrec,
+                             uint16_t *packed, int64_t packed_elems, obb_stream_t s);
 /* Weight gradient of every dense Conv of `model.train(...)` (Train_OBB.py:796-841 -> loss.backward() through Conv2d under bf16 autocast) whose
  * channel counts are multiples of 8, both >= 8 -- what obb_conv_wgrad_bf16 / obb_conv_wgrad_s2_bf16 refuse below multiples of 64: model.1, the
  * C3k2 Bottlenecks down to 16 -> 8, the 1x1s behind a 48- / 96-channel concat, the head's angle branch.  (ks, stride) = (1, 1), (3, 1) or

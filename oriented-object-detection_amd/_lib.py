@@ -53,6 +53,8 @@ SIGNATURES = {
     "obb_conv_fwd_s2_bf16": [_V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_conv_dgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_conv_wgrad_s2_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_conv_pack_plan": [_V, C.c_int32, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_lp, C.c_int64, c_lp, c_lp, c_lp, _V, C.c_int64, _V],
+    "obb_conv_pack_multi_bf16": [_V, _V, C.c_int64, _V, C.c_int64, C.c_int32, _V, C.c_int64, _V],
     "obb_conv_wgrad_c8_bf16": [_V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_bn_silu_fwd_bf16": [_V, _V, C.c_int64, C.c_int32, _V, _V, C.c_float, C.c_float, _V, _V, _V, _V, _V, _V],
     "obb_bn_silu_bwd_bf16": [_V, _V, _V, C.c_int64, C.c_int32, _V, _V, _V, _V, _V, _V, _V, _V],
@@ -109,6 +111,7 @@ SIGNATURES = {
     "obb_ema_update": [_V, _V, _V, c_lp, C.c_int32, C.c_double, _V],
 }
 _RESTYPE = {"obb_last_error": C.c_char_p}
+PACK_TABLE_HEAD, PACK_TABLE_REC = 4, 8  # OBB_PACK_TABLE_HEAD / OBB_PACK_TABLE_REC: int64 words of obb_conv_pack_plan's table
 
 
 class ObbHipError(RuntimeError):

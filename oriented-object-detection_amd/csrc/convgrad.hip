@@ -184,11 +184,9 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ 
 
 // fp32 OIHW master weights (device) -> the forward kernel's bf16 A-operand fragment order [cout block][stage][k step][fragment][lane][8]
 // (pack_conv_weights' index arithmetic, element for element).  tflip = 1: the dgrad form -- the logical conv has the channel roles swapped and
-// the taps flipped: W'[ci][co][t] = W[co][ci][taps - 1 - t].
-__global__ __launch_bounds__(256) void k_pack_conv_bf16(const float *__restrict__ w, int coutL, int cinL, int ks, int CK, int NF, int tflip, unsigned short *__restrict__ out,
-                                                       int64_t total) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (o >= total) return;
+// the taps flipped: W'[ci][co][t] = W[co][ci][taps - 1 - t].  pack_conv_elem = element o of one layer's blob: what k_pack_conv_bf16 and
+// k_pack_conv_multi_bf16 both store.
+__device__ __forceinline__ unsigned short pack_conv_elem(const float *__restrict__ w, int coutL, int cinL, int ks, int CK, int NF, int tflip, int64_t o) {
     const int cpk = CK / 8, taps = ks * ks, kst = ((ks == 3 ? 9 : 1) * cpk + 3) / 4, nstage = (cinL + CK - 1) / CK;
     const int j = (int)(o & 7), lane = (int)((o >> 3) & 63);
     int64_t rest = o >> 9;
@@ -204,7 +202,44 @@ __global__ __launch_bounds__(256) void k_pack_conv_bf16(const float *__restrict_
     float v = 0.f;
     if (co < coutL && c < cinL && tap < taps && (ks == 3 || c0 < CK))
         v = tflip ? w[((size_t)c * coutL + co) * taps + (taps - 1 - tap)] : w[((size_t)co * cinL + c) * taps + tap];
-    out[o] = bf16_rne(v);
+    return bf16_rne(v);
+}
+
+__global__ __launch_bounds__(256) void k_pack_conv_bf16(const float *__restrict__ w, int coutL, int cinL, int ks, int CK, int NF, int tflip, unsigned short *__restrict__ out,
+                                                       int64_t total) {
+    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (o >= total) return;
+    out[o] = pack_conv_elem(w, coutL, cinL, ks, CK, NF, tflip, o);
+}
+
+// Every dense conv of a network, both forms, in ONE launch: the weights are windows of one flat fp32 buffer (train.ParamGroups' group 0) and the
+// packed blobs segments of one bf16 buffer, described by a device-resident table of int64 words (built once per (layer list, input size) by
+// obb_conv_pack_plan):
+//     head   [0] kPackMagic  [1] records  [2] elements of the packed buffer  [3] elements of the flat buffer the records read up to
+//     record [0] source offset  [1] destination offset  [2] elements  [3] first workgroup  [4] coutL | cinL << 32  [5] ks | tflip << 32
+//            [6] CK | NF << 32  [7] 0
+// A segment starts at a multiple of 256 elements and owns ceil(elements / 256) workgroups, so a workgroup lies in one segment: it finds its
+// record by bisection over the records' first workgroups (uniform loads), then every lane stores pack_conv_elem of its element.  The padding
+// behind a segment is never written.  The head is compared with the launch's own arguments: a table of another plan, or a flat buffer too short
+// for it, makes every workgroup return before its first store.
+constexpr int64_t kPackMagic = 0x4f42425041434b31ll;  // "OBBPACK1"
+constexpr int kPackHead = OBB_PACK_TABLE_HEAD, kPackRec = OBB_PACK_TABLE_REC;
+
+__global__ __launch_bounds__(256) void k_pack_conv_multi_bf16(const float *__restrict__ w, int64_t w_elems, const int64_t *__restrict__ tab, int nrec,
+                                                             unsigned short *__restrict__ out, int64_t total) {
+    if (tab[0] != kPackMagic || tab[1] != nrec || tab[2] != total || tab[3] > w_elems) return;
+    int lo = 0, hi = nrec - 1;
+    while (lo < hi) {  // the last record whose first workgroup is <= blockIdx.x
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[kPackHead + (int64_t)mid * kPackRec + 3] <= (int64_t)blockIdx.x) lo = mid; else hi = mid - 1;
+    }
+    const int64_t *__restrict__ r = tab + kPackHead + (int64_t)lo * kPackRec;
+    const int64_t src = r[0], dst = r[1], n = r[2];
+    const int64_t o = ((int64_t)blockIdx.x - r[3]) * 256 + threadIdx.x;
+    const int coutL = (int)(r[4] & 0xffffffff), cinL = (int)(r[4] >> 32), ks = (int)(r[5] & 0xffffffff), tflip = (int)(r[5] >> 32);
+    const int CK = (int)(r[6] & 0xffffffff), NF = (int)(r[6] >> 32);
+    if (o < 0 || o >= n || dst < 0 || dst + o >= total || src < 0 || src + (int64_t)coutL * cinL * ks * ks > w_elems) return;
+    out[dst + o] = pack_conv_elem(w + src, coutL, cinL, ks, CK, NF, tflip, o);
 }
 
 __global__ __launch_bounds__(256) void k_silu_bf16(const unsigned short *__restrict__ z, unsigned short *__restrict__ a, int64_t n) {
@@ -443,6 +478,63 @@ int obb_conv_s2_packed_elems(obb_ctx *ctx, int32_t cout, int32_t cin, int32_t H,
 
 int obb_conv_s2_pack_bf16(obb_ctx *ctx, const float *w_oihw, int32_t cout, int32_t cin, int32_t H, int32_t W, uint16_t *packed, obb_stream_t s) {
     return pack_launch(ctx, "obb_conv_s2_pack_bf16", w_oihw, cout, cin, 3, 2, H, W, 0, packed, (hipStream_t)s);
+}
+
+// ---- every dense conv in one launch (k_pack_conv_multi_bf16): the plan, once per (layer list, input size), and the per-step launch
+int obb_conv_pack_plan(obb_ctx *ctx, int32_t nrec, const int32_t *cout, const int32_t *cin, const int32_t *ks, const int32_t *stride, const int32_t *H,
+                       const int32_t *W, const int32_t *dgrad_form, const int64_t *src_off, int64_t src_elems, int64_t *dst_off, int64_t *n_elems,
+                       int64_t *total, int64_t *table, int64_t table_words, obb_stream_t s) {
+    const char *fn = "obb_conv_pack_plan";
+    OBB_REQUIRE(ctx, ctx && nrec >= 1 && cout && cin && ks && stride && H && W && dgrad_form && src_off && dst_off && n_elems && total && src_elems > 0,
+                "%s: bad arguments", fn);
+    OBB_REQUIRE(ctx, !table || table_words == kPackHead + (int64_t)nrec * kPackRec, "%s: the table holds %lld words, %lld needed for %d records", fn,
+                (long long)table_words, (long long)(kPackHead + (int64_t)nrec * kPackRec), (int)nrec);
+    std::vector<int64_t> tab((size_t)(kPackHead + (int64_t)nrec * kPackRec), 0), dst((size_t)nrec), cnt((size_t)nrec);
+    int64_t blk = 0, need = 0;
+    for (int i = 0; i < nrec; ++i) {
+        OBB_REQUIRE(ctx, (stride[i] == 1 && (ks[i] == 1 || ks[i] == 3)) || (stride[i] == 2 && ks[i] == 3), "%s: record %d: k = %d at stride %d", fn, i, (int)ks[i],
+                    (int)stride[i]);
+        // (the dgrad form is a stride-1 conv on the layer's H x W input, whatever the layer's stride: obb_conv_dgrad_s2_bf16)
+        const int st = dgrad_form[i] ? 1 : stride[i];
+        int64_t n = 0;
+        if (int rc = packed_elems(ctx, fn, cout[i], cin[i], ks[i], st, H[i], W[i], dgrad_form[i], &n)) return rc;
+        const int64_t wn = (int64_t)cout[i] * cin[i] * ks[i] * ks[i];
+        OBB_REQUIRE(ctx, src_off[i] >= 0 && src_off[i] + wn <= src_elems, "%s: record %d reads [%lld, %lld) of a flat buffer of %lld elements", fn, i,
+                    (long long)src_off[i], (long long)(src_off[i] + wn), (long long)src_elems);
+        const int coutL = dgrad_form[i] ? cin[i] : cout[i], cinL = dgrad_form[i] ? cout[i] : cin[i];
+        const ConvTiling t = plan_conv(ks[i], st, cinL, coutL, out_dim(H[i], st), out_dim(W[i], st), false);
+        int64_t *r = tab.data() + kPackHead + (int64_t)i * kPackRec;
+        r[0] = src_off[i]; r[1] = blk * 256; r[2] = n; r[3] = blk;
+        r[4] = (int64_t)coutL | ((int64_t)cinL << 32); r[5] = (int64_t)ks[i] | ((int64_t)(dgrad_form[i] ? 1 : 0) << 32); r[6] = (int64_t)t.CK | ((int64_t)t.NF << 32);
+        dst[(size_t)i] = r[1]; cnt[(size_t)i] = n;
+        blk += cdiv(n, 256);
+        need = std::max(need, src_off[i] + wn);
+    }
+    OBB_REQUIRE(ctx, blk < (1ll << 31), "%s: %lld workgroups: too many for one launch", fn, (long long)blk);
+    tab[0] = kPackMagic; tab[1] = nrec; tab[2] = blk * 256; tab[3] = need;
+    if (table) {
+        hipStream_t st = (hipStream_t)s;
+        OBB_HIP(ctx, hipMemcpyAsync(table, tab.data(), tab.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        OBB_HIP(ctx, hipStreamSynchronize(st));  // (the host copy of the table goes out of scope)
+    }
+    std::copy(dst.begin(), dst.end(), dst_off);
+    std::copy(cnt.begin(), cnt.end(), n_elems);
+    *total = blk * 256;
+    return OBB_OK;
+}
+
+int obb_conv_pack_multi_bf16(obb_ctx *ctx, const float *w_flat, int64_t w_elems, const int64_t *table, int64_t table_words, int32_t nrec, uint16_t *packed,
+                             int64_t packed_elems_, obb_stream_t s) {
+    const char *fn = "obb_conv_pack_multi_bf16";
+    OBB_REQUIRE(ctx, ctx && w_flat && table && packed, "%s: NULL buffer", fn);
+    OBB_REQUIRE(ctx, nrec >= 1 && w_elems > 0 && table_words == kPackHead + (int64_t)nrec * kPackRec, "%s: the table holds %lld words, %lld needed for %d records", fn,
+                (long long)table_words, (long long)(kPackHead + (int64_t)nrec * kPackRec), (int)nrec);
+    OBB_REQUIRE(ctx, packed_elems_ > 0 && packed_elems_ % 256 == 0 && packed_elems_ / 256 < (1ll << 31),
+                "%s: the packed buffer holds %lld elements: a plan's total is a positive multiple of 256", fn, (long long)packed_elems_);
+    hipLaunchKernelGGL(k_pack_conv_multi_bf16, dim3((unsigned)(packed_elems_ / 256)), dim3(256), 0, (hipStream_t)s, w_flat, w_elems, table, (int)nrec, packed,
+                       packed_elems_);
+    OBB_LAUNCH_CHECK(ctx);
+    return OBB_OK;
 }
 
 int obb_conv_fwd_s2_bf16(obb_ctx *ctx, const uint16_t *x, const uint16_t *packed_w, const float *bias, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout,

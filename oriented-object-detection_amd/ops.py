@@ -362,6 +362,11 @@ def _chanwin(src: T, s0: int, add: Optional[T], a0: int, n: int, dst: T, d0: int
           src.numel() // src.shape[-1], int(n), _p(dst), dst.shape[-1], int(d0), _stream())
 
 
+@_op("conv_pack_multi", ("out",))
+def _conv_pack_multi(flat: T, table: T, nrec: int, out: T) -> None:
+    _call("obb_conv_pack_multi_bf16", ctx(flat.device), _p(flat), flat.numel(), _p(table), table.numel(), int(nrec), _p(out), out.numel(), _stream())
+
+
 def _crit_levels(box, cls, angle):
     """-> the host-side level arrays of obb_crit_*: (box[3], box_bf16, cls[3], angle[3], H[3], W[3], B, nc)"""
     vp = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
@@ -690,6 +695,51 @@ def conv_pack_bf16(w, H, W, dgrad_form=False, stride=1):
         _call("obb_conv_s2_pack_bf16", ctx(ww.device), _p(ww), cout, cin, int(H), int(W), _p(out), _stream())
     else:
         _call("obb_conv_pack_bf16", ctx(ww.device), _p(ww), cout, cin, ks, int(H), int(W), int(bool(dgrad_form)), _p(out), _stream())
+    return out
+
+
+class PackTable:
+    """What `conv_pack_plan` returns: `table` (int64 device tensor: the records of csrc/convgrad.hip's k_pack_conv_multi_bf16), `layers` (the
+    tuples it was planned from), `dst_off` / `n_elems` (per record: its segment of the packed buffer), `total` (elements of the packed buffer) and
+    `src_elems` (elements of the flat weight buffer)."""
+
+    def __init__(self, table, layers, dst_off, n_elems, total, src_elems):
+        self.table, self.layers, self.dst_off, self.n_elems, self.total, self.src_elems = table, layers, dst_off, n_elems, total, src_elems
+
+    nrec = property(lambda self: len(self.layers))
+
+
+def conv_pack_plan(device, layers, src_elems):
+    """The plan of `conv_pack_multi_bf16`, made ONCE per (layer list, input size): layers = [(cout, cin, ks, stride, H, W, dgrad_form, src_off)],
+    H x W the layer's INPUT map and src_off the element offset of its [cout,cin,ks,ks] fp32 weights in a flat buffer of src_elems elements -> a
+    `PackTable`.  Each record is planned as `conv_pack_bf16` plans the same layer (stride 2 in the forward form: the s2 layout; the dgrad form does
+    not depend on the stride), and its segment starts at a multiple of 256 elements.  Synchronises (the table is copied to the device)."""
+    layers = [tuple(int(v) for v in L) for L in layers]
+    n = len(layers)
+    if n < 1 or any(len(L) != 8 for L in layers):
+        raise ValueError("conv_pack_plan: layers is a non-empty list of (cout, cin, ks, stride, H, W, dgrad_form, src_off)")
+    for L in layers:
+        _stride_ok(L[2], L[3])
+    cols = [(C.c_int32 * n)(*[L[j] for L in layers]) for j in range(7)]
+    src = (C.c_int64 * n)(*[L[7] for L in layers])
+    dst, cnt, total = (C.c_int64 * n)(), (C.c_int64 * n)(), C.c_int64(0)
+    dev = torch.device(device)
+    table = torch.zeros(_lib.PACK_TABLE_HEAD + n * _lib.PACK_TABLE_REC, dtype=torch.int64, device=dev)
+    _call("obb_conv_pack_plan", ctx(dev), n, *cols, src, int(src_elems), dst, cnt, C.byref(total), _p(table), table.numel(), _stream())
+    return PackTable(table, layers, list(dst), list(cnt), total.value, int(src_elems))
+
+
+def conv_pack_multi_bf16(flat, plan, out=None):
+    """Every layer of `plan` (a `PackTable`) packed from the flat fp32 weight buffer `flat` into ONE bf16 buffer of plan.total elements (`out`, or
+    a new one) by ONE kernel launch: segment i = out[dst_off[i] : dst_off[i] + n_elems[i]] holds the bits `conv_pack_bf16` gives for layer i; the
+    padding between segments is not written.  No host read, copy or synchronisation: it can sit inside a captured graph."""
+    ff = _chk(flat, torch.float32, "flat")
+    if ff.numel() != plan.src_elems:
+        raise ValueError(f"conv_pack_multi_bf16: the plan was made for a flat buffer of {plan.src_elems} elements, got {ff.numel()}")
+    out = torch.empty(plan.total, dtype=torch.bfloat16, device=ff.device) if out is None else _chk(out, torch.bfloat16, "out")
+    if out.numel() != plan.total or out.device != ff.device or plan.table.device != ff.device:
+        raise ValueError(f"conv_pack_multi_bf16: out holds {out.numel()} elements, the plan's total is {plan.total}: a plan for other layers or another map size?")
+    _O.conv_pack_multi(ff, plan.table, plan.nrec, out)
     return out
 
 

@@ -360,13 +360,22 @@ class ConvBN(_BNBlock):
             raise ValueError(f"ConvBN: k = {k}, s = {s}: k 1 or 3 at stride 1, k 3 at stride 2")
         super().__init__(groups, w, gamma, beta, c1, c2, k, s, act, running_mean, running_var, eps, momentum)
 
+    pack = None  # the PackPlan that holds this layer's packed weights, once one is attached (then nothing is packed per call)
+
+    def _packed(self, H, W, dgrad_form=False):
+        """This step's bf16 weights for H x W input maps: a view of the attached plan's buffer (the consuming op checks its length with
+        ops._check_packed), or packed here, per call."""
+        if self.pack is not None:
+            return self.pack.view(self, H, W, dgrad_form)
+        return ops.conv_pack_bf16(self.w, H, W, dgrad_form=True) if dgrad_form else ops.conv_pack_bf16(self.w, H, W, stride=self.s)
+
     def _conv_fwd(self, x):
-        return ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2], stride=self.s), None, self.c2, self.k, stride=self.s)
+        return ops.conv_fwd_bf16(x, self._packed(x.shape[1], x.shape[2]), None, self.c2, self.k, stride=self.s)
 
     def _conv_bwd(self, x, dz):
         H, W = x.shape[1], x.shape[2]
         conv_wgrad(x, dz, self.k, self.s, out=self.dw)
-        bw = ops.conv_pack_bf16(self.w, H, W, dgrad_form=True)
+        bw = self._packed(H, W, dgrad_form=True)
         if self.s == 2:
             return ops.conv_dgrad_s2_bf16(dz, bw, self.c1, H, W)
         return ops.conv_fwd_bf16(dz, bw, None, self.c1, self.k)
@@ -782,15 +791,22 @@ class BoxOut(_ConvBias):
     with BF16 logits: forward(x bf16 [B,H,W,c]) -> bf16 [B,H,W,cout] = pack + conv + bias; backward(dy bf16) -> dx bf16 = weight gradient and bias
     gradient into the groups' gradient views, then the conv on the dgrad-form pack."""
 
+    k, s, pack = 1, 1, None  # (pack: as ConvBN's)
+
+    def _packed(self, H, W, dgrad_form=False):
+        if self.pack is not None:
+            return self.pack.view(self, H, W, dgrad_form)
+        return ops.conv_pack_bf16(self.w, H, W, dgrad_form=dgrad_form)
+
     def forward(self, x):
         self.saved = x
-        return ops.conv_fwd_bf16(x, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2]), self.b, self.c2, 1)
+        return ops.conv_fwd_bf16(x, self._packed(x.shape[1], x.shape[2]), self.b, self.c2, 1)
 
     def backward(self, dy):
         x = self.saved
         conv_wgrad(x, dy, 1, out=self.dw)
         ops.bias_grad_bf16(dy, self.db)
-        return ops.conv_fwd_bf16(dy, ops.conv_pack_bf16(self.w, x.shape[1], x.shape[2], dgrad_form=True), None, self.c1, 1)
+        return ops.conv_fwd_bf16(dy, self._packed(x.shape[1], x.shape[2], dgrad_form=True), None, self.c1, 1)
 
 
 class _DetectBoxBranch(_Chain):
@@ -956,22 +972,29 @@ class DetectHead(_Step):
     convs / pairs as DetectBoxBranchStep / DetectClassBranchStep / DetectAngleBranch take them; per level the parameters are registered in the order
     box, cls, angle.  forward(feats) -> (box, cls, angle) lists (bf16 [B,H,W,64], fp32 [B,H,W,nc], fp32 [B,H,W,1]); backward(d_box, d_cls, d_angle) ->
     one dx per level, the sum of the three branches' input gradients through ops.add_bf16 in the fixed order (box + class) + angle;
-    step(feats, gt_labels, gt_bboxes, mask_gt) = forward, criterion, backward, DDP gradient average, optimiser step -> (items, dx list)."""
+    step(feats, gt_labels, gt_bboxes, mask_gt) = forward, criterion, backward, DDP gradient average, optimiser step -> (items, dx list).
+    groups=: the head as part of a larger net (`Net`) on the caller's ParamGroups, which the caller builds; the branches are then registered in
+    checkpoint order (all box branches, all class branches, all angle branches)."""
 
     def __init__(self, levels, nc, gains=(7.5, 0.5, 1.5), optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3,
-                 bn_momentum=0.03):
+                 bn_momentum=0.03, groups=None):
         if len(levels) != 3:
             raise ValueError("DetectHead: three levels (P3, P4, P5)")
-        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
-        self.box, self.cls, self.angle = [], [], []
-        for lv in levels:
-            self.box.append(_DetectBoxBranch(self.groups, *lv["box"], eps, bn_momentum))
-            self.cls.append(_DetectClassBranch(self.groups, *lv["cls"], eps, bn_momentum))
-            self.angle.append(DetectAngleBranch(self.groups, *lv["angle"], eps=eps, momentum=bn_momentum))
-            if self.box[-1].cout3 != 64 or self.cls[-1].out.c2 != nc or self.angle[-1].out.c2 != 1:
-                raise ValueError(f"DetectHead: a level's branches end in 64, nc = {nc} and 1 channels, got {self.box[-1].cout3}, "
-                                 f"{self.cls[-1].out.c2}, {self.angle[-1].out.c2}")
-        self.groups.build()
+        own = groups is None
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov) if own else groups
+        self.box, self.cls, self.angle = [None] * 3, [None] * 3, [None] * 3
+        fams = (("box", self.box, _DetectBoxBranch), ("cls", self.cls, _DetectClassBranch), ("angle", self.angle, DetectAngleBranch))
+        # registration order: per level box, cls, angle on groups of its own; as part of a larger net (`Net`, the caller's groups, built by the
+        # caller) CHECKPOINT order: cv2.0-2, cv3.0-2, cv4.0-2
+        order = [(f, i) for i in range(3) for f in fams] if own else [(f, i) for f in fams for i in range(3)]
+        for (key, dst, cls_), i in order:
+            dst[i] = cls_(self.groups, *levels[i][key], eps, bn_momentum)
+        for i in range(3):
+            if self.box[i].cout3 != 64 or self.cls[i].out.c2 != nc or self.angle[i].out.c2 != 1:
+                raise ValueError(f"DetectHead: a level's branches end in 64, nc = {nc} and 1 channels, got {self.box[i].cout3}, "
+                                 f"{self.cls[i].out.c2}, {self.angle[i].out.c2}")
+        if own:
+            self.groups.build()
         self.criterion = OBBCriterion(nc, gains)
 
     def forward(self, feats):
@@ -986,6 +1009,302 @@ class DetectHead(_Step):
         box, cls, angle = self.forward(feats)
         items, (d_box, d_cls, d_angle) = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
         return items, self.backward(d_box, d_cls, d_angle)
+
+
+class PackPlan:
+    """This iteration's bf16 weights of MANY dense convs from one launch.  convs: layers with `_packed` (ConvBN, BoxOut) whose weights live in
+    group 0 of `groups` (built); shapes: each layer's INPUT map (H, W).  The plan owns the device table (ops.conv_pack_plan) and ONE bf16 buffer
+    with two segments per layer -- the forward form (stride-2 layers: the s2 layout) and the dgrad form -- and attaches itself to the layers
+    (`layer.pack`), which then read views of that buffer in place of packing per call.  `run()` repacks everything from the flat group-0
+    parameters (ops.conv_pack_multi_bf16: one launch, capturable); call it after every optimiser step and before the next forward (a layer that asks for its
+    view after the flat parameters were written and before `run()` raises: stale weights are never read).  A layer asked
+    for another H x W than planned raises: the layout depends on the map size.  `detach()` puts the layers back on per-call packing."""
+
+    def __init__(self, groups, convs, shapes):
+        convs, shapes = list(convs), [(int(h), int(w)) for h, w in shapes]
+        if groups.opts is None or not convs or len(convs) != len(shapes):
+            raise ValueError("PackPlan: built groups, and one (H, W) per layer of a non-empty list")
+        self.flat = groups.opts[0].param
+        layers = []
+        for m, (H, W) in zip(convs, shapes):
+            w = m.w
+            if w.untyped_storage().data_ptr() != self.flat.untyped_storage().data_ptr() or not w.is_contiguous():
+                raise ValueError("PackPlan: a layer's weights are no view of the groups' flat group-0 parameters")
+            off = w.storage_offset() - self.flat.storage_offset()
+            layers += [(m.c2, m.c1, m.k, m.s, H, W, f, off) for f in (0, 1)]
+        self.table = ops.conv_pack_plan(self.flat.device, layers, self.flat.numel())
+        self.packed = torch.zeros(self.table.total, dtype=torch.bfloat16, device=self.flat.device)
+        seg = [self.packed[d:d + n] for d, n in zip(self.table.dst_off, self.table.n_elems)]
+        self.convs, self._views, self._packed_version = convs, {}, None  # (None: never run)
+        for i, (m, hw) in enumerate(zip(convs, shapes)):
+            self._views[id(m)] = (hw, seg[2 * i], seg[2 * i + 1])
+            m.pack = self
+
+    def run(self):
+        ops.conv_pack_multi_bf16(self.flat, self.table, out=self.packed)
+        self._packed_version = self.flat._version
+
+    def view(self, m, H, W, dgrad_form=False):
+        hw, fwd, bwd = self._views[id(m)]
+        if self.flat._version != self._packed_version:  # (torch counts the in-place writes of the flat parameters: an optimiser step, an EMA swap)
+            raise RuntimeError("PackPlan: the parameters were written since the last run(): the packed weights are stale; call run() before the forward")
+        if hw != (int(H), int(W)):
+            raise ValueError(f"PackPlan: the layer {m.c1} -> {m.c2} was planned for {hw[0]} x {hw[1]} input maps and is asked for {H} x {W}: the packed layout "
+                             "depends on the map size")
+        return bwd if dgrad_form else fwd
+
+    def detach(self):
+        for m in self.convs:
+            if m.pack is self:
+                m.pack = None
+
+
+def _state_block(params, name):
+    """(w, gamma, beta, running_mean, running_var) of the Conv block `name` of an Ultralytics state dict (BatchNorm entries that are missing: None)"""
+    return (params[name + ".conv.weight"],) + tuple(params.get(f"{name}.bn.{k}") for k in ("weight", "bias", "running_mean", "running_var"))
+
+
+class Trunk:
+    """Models 0-22 of yolo11-obb.yaml (backbone + FPN / PAN neck) in training mode over ONE `ParamGroups` (the caller builds it after the
+    constructor).  params: a dict keyed by Ultralytics state-dict names (`model.2.m.0.cv1.conv.weight`, `...bn.weight`, `...bn.bias`,
+    `...bn.running_mean`, `...bn.running_var`); scale "n" or "s".  The parameters are registered in checkpoint order: model.0, model.1,
+    model.2.cv1, model.2.cv2, model.2.m.0.cv1, ...
+
+        0 stem  1 Conv s2  2 C3k2  3 Conv s2  4 C3k2  5 Conv s2  6 C3k2(c3k)  7 Conv s2  8 C3k2(c3k)  9 SPPF  10 C2PSA
+        12 = cat(up(10), 6) -> 13 C3k2    15 = cat(up(13), 4) -> 16 C3k2 (P3)    17 Conv s2    18 = cat(17, 13) -> 19 C3k2 (P4)
+        20 Conv s2    21 = cat(20, 10) -> 22 C3k2(c3k) (P5)
+
+    forward(tiles uint8 [B,H,W,3|4], H and W multiples of 32) -> [P3, P4, P5] bf16 NHWC; backward([d3, d4, d5]) writes every parameter gradient.
+    Six tensors have two consumers.  Each one's gradient is ops.add_bf16(first, second) = bf16(fp32 + fp32), FIRST the gradient of the consumer
+    that comes LATER in the yaml (the one the backward reaches first), SECOND that of the earlier one:
+        19: head P4 + model.20      16: head P3 + model.17      13: concat 18 + upsample/concat 15      10: concat 21 + upsample/concat 12
+         6: concat 12 + model.7      4: concat 15 + model.5
+    `taps`: set `record_taps = True` and the next forward / backward fill taps[i] = {"in", "out", "dout", "din"} per top-level module i (the
+    concat modules under 12, 15, 18, 21 with "in" = (a, b), "din" = (da, db)) and taps["fan"][i] = (first, second, sum) per fan-out tensor."""
+
+    SCALES = {"n": 16, "s": 32}  # stem width = make_divisible(64 * width, 8): the scales `train_kernel_of` and the shape catalogue cover
+    IN_LEVEL = {1: 2, 2: 4, 3: 4, 4: 8, 5: 8, 6: 16, 7: 16, 8: 32, 9: 32, 10: 32, 13: 16, 16: 8, 17: 8, 19: 16, 20: 16, 22: 32}  # input stride per module
+    CONVS, C3K2S = (1, 3, 5, 7, 17, 20), (2, 4, 6, 8, 13, 16, 19, 22)
+
+    def __init__(self, groups, params, scale="n", eps=1e-3, momentum=0.03):
+        if scale not in self.SCALES:
+            raise ValueError(f"Trunk: scale {scale!r}: the training kernels cover the n and s scales")
+        t = lambda name: _state_block(params, name)
+        if params["model.0.conv.weight"].shape[0] != self.SCALES[scale]:
+            raise ValueError(f"Trunk: model.0 has {params['model.0.conv.weight'].shape[0]} channels, scale {scale!r} has {self.SCALES[scale]}")
+        self.groups, self.scale, self.m = groups, scale, {}
+        self.record_taps, self.taps = False, None
+
+        def bneck(p):
+            return (t(p + ".cv1"), t(p + ".cv2"))
+
+        def c3k2(i):
+            p, members, c3k = f"model.{i}", [], f"model.{i}.m.0.cv3.conv.weight" in params
+            while f"{p}.m.{len(members)}.cv1.conv.weight" in params:
+                q = f"{p}.m.{len(members)}"
+                if c3k:
+                    inner = []
+                    while f"{q}.m.{len(inner)}.cv1.conv.weight" in params:
+                        inner.append(bneck(f"{q}.m.{len(inner)}"))
+                    members.append((t(q + ".cv1"), t(q + ".cv2"), t(q + ".cv3"), inner))
+                else:
+                    members.append(bneck(q))
+            return C3k2(groups, t(p + ".cv1"), t(p + ".cv2"), members, c3k=c3k, eps=eps, momentum=momentum)
+
+        for i in range(23):
+            if i == 0:
+                self.m[0] = _bn_block(StemConvBN, groups, t("model.0"), eps, momentum)
+            elif i in self.CONVS:
+                self.m[i] = _bn_block(ConvBN, groups, t(f"model.{i}"), eps, momentum, s=2)
+            elif i in self.C3K2S:
+                self.m[i] = c3k2(i)
+            elif i == 9:
+                self.m[9] = SPPF(groups, t("model.9.cv1"), t("model.9.cv2"), eps, momentum)
+            elif i == 10:
+                blocks = []
+                while f"model.10.m.{len(blocks)}.attn.qkv.conv.weight" in params:
+                    q = f"model.10.m.{len(blocks)}"
+                    blocks.append(tuple(t(f"{q}.{n}") for n, _ in C2PSA.PSA_NAMES))
+                nh = params["model.10.cv1.conv.weight"].shape[0] // 128
+                self.m[10] = C2PSA(groups, t("model.10.cv1"), t("model.10.cv2"), blocks, nh, eps, momentum)
+            elif i in (12, 15):
+                self.m[i] = UpCat(2)
+            elif i in (18, 21):
+                self.m[i] = UpCat(1)
+        self.ch = self.m[0].c1
+
+    def named_blocks(self):
+        """[(state-dict name, block)] of every Conv block (a _BNBlock) in registration = checkpoint order"""
+        out = []
+        for i in sorted(self.m):
+            m = self.m[i]
+            if isinstance(m, _BNBlock):
+                out.append((f"model.{i}", m))
+            elif isinstance(m, SPPF):
+                out += [(f"model.{i}.cv1", m.cv1), (f"model.{i}.cv2", m.cv2)]
+            elif hasattr(m, "named_blocks"):
+                out += [(f"model.{i}.{n}", b) for n, b in m.named_blocks()]
+        return out
+
+    def fold(self):
+        """-> {state-dict name: (w, b)}: eval-mode BN folded into every conv, fp32, the qkv convs in checkpoint channel order."""
+        out = {}
+        for i in sorted(self.m):
+            m = self.m[i]
+            if isinstance(m, _BNBlock):
+                out[f"model.{i}"] = m.fold()
+            elif isinstance(m, SPPF):
+                out.update({f"model.{i}.cv1": m.cv1.fold(), f"model.{i}.cv2": m.cv2.fold()})
+            elif hasattr(m, "fold"):
+                out.update({f"model.{i}.{n}": wb for n, wb in m.fold().items()})
+        return out
+
+    def pack_layers(self, H, W):
+        """-> (layers, shapes) for a `PackPlan`: every dense conv with its input map at H x W tiles"""
+        layers, shapes = [], []
+        for name, b in self.named_blocks():
+            if isinstance(b, ConvBN):
+                lv = self.IN_LEVEL[int(name.split(".")[1])]
+                layers.append(b); shapes.append((H // lv, W // lv))
+        return layers, shapes
+
+    def _f(self, i, *xs):
+        y = self.m[i].forward(*xs)
+        if self.taps is not None:
+            self.taps[i] = {"in": xs[0] if len(xs) == 1 else xs, "out": y}
+        return y
+
+    def _b(self, i, d):
+        r = self.m[i].backward(d)
+        if self.taps is not None:
+            self.taps[i].update(dout=d, din=r)
+        return r
+
+    def _sum(self, i, first, second):
+        s = ops.add_bf16(first, second)
+        if self.taps is not None:
+            self.taps["fan"][i] = (first, second, s)
+        return s
+
+    def forward(self, tiles):
+        if tiles.dim() != 4 or tiles.shape[1] % 32 or tiles.shape[2] % 32 or tiles.shape[3] != self.ch:
+            raise ValueError(f"Trunk.forward: tiles uint8 [B,H,W,{self.ch}] with H and W multiples of 32, got {tuple(tiles.shape)}")
+        self.taps = {"fan": {}} if self.record_taps else None
+        x = tiles
+        keep = {}
+        for i in range(11):
+            x = keep[i] = self._f(i, x)
+        x13 = self._f(13, self._f(12, keep[10], keep[6]))
+        x16 = self._f(16, self._f(15, x13, keep[4]))
+        x19 = self._f(19, self._f(18, self._f(17, x16), x13))
+        x22 = self._f(22, self._f(21, self._f(20, x19), keep[10]))
+        return [x16, x19, x22]
+
+    def backward(self, d):
+        d3, d4, d5 = d
+        d20, d10a = self._b(21, self._b(22, d5))
+        g19 = self._sum(19, d4, self._b(20, d20))
+        d17, d13a = self._b(18, self._b(19, g19))
+        g16 = self._sum(16, d3, self._b(17, d17))
+        d13b, d4a = self._b(15, self._b(16, g16))
+        d10b, d6a = self._b(12, self._b(13, self._sum(13, d13a, d13b)))
+        g = self._sum(10, d10a, d10b)
+        for i in (10, 9, 8):
+            g = self._b(i, g)
+        g = self._sum(6, d6a, self._b(7, g))
+        g = self._sum(4, d4a, self._b(5, self._b(6, g)))
+        for i in (4, 3, 2, 1, 0):
+            g = self._b(i, g)
+
+
+class Net(_Step):
+    """The whole YOLO11-OBB training iteration: `Trunk` (models 0-22) + the branches of `DetectHead` (model.23) + `OBBCriterion` over ONE
+    `ParamGroups`, the parameters registered in checkpoint order (the trunk's, then model.23.cv2.0-2, cv3.0-2, cv4.0-2).  params: a dict keyed by
+    Ultralytics state-dict names (`Trunk`; the head's plain convs as `model.23.cv2.0.2.weight` / `.bias`); scale "n" or "s" (anything else:
+    ValueError); ch = 3 or 4.
+        forward_backward(tiles uint8 [B,H,W,ch], gt_labels, gt_bboxes, mask_gt) -> items fp32[3] (the ground truth of `pad_targets`, on the device)
+        step(..., ni=, epoch=) with `net.update = TrainerUpdate(net.groups, ...)`, or step(...) for the plain optimiser step (`_Step`)
+    The dense convs' bf16 weights come from ONE launch per iteration (`PackPlan`, built lazily for the tile size seen, run first thing in
+    forward_backward); `pack = False` packs per layer and call as the blocks do on their own -- the results are bit-identical.  `taps`: set
+    `record_taps = True`; the next forward_backward fills taps[0..22] and taps["fan"] (`Trunk`) and taps[23] = {"in": [P3, P4, P5], "out": (box, cls,
+    angle), "dout": (d_box, d_cls, d_angle), "din": [d3, d4, d5]}."""
+
+    def __init__(self, params, scale="n", nc=12, ch=3, gains=(7.5, 0.5, 1.5), optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True,
+                 eps=1e-3, bn_momentum=0.03, pack=True):
+        w0 = params["model.0.conv.weight"]
+        if w0.shape[1] != ch:
+            raise ValueError(f"Net: model.0 reads {w0.shape[1]} channels, ch = {ch}")
+        self.groups = ParamGroups(optimizer, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        self.trunk = Trunk(self.groups, params, scale, eps, bn_momentum)
+        t = lambda name: _state_block(params, name)
+        wb = lambda name: (params[name + ".weight"], params[name + ".bias"])
+        levels = []
+        for i in range(3):
+            b, c, a = f"model.23.cv2.{i}", f"model.23.cv3.{i}", f"model.23.cv4.{i}"
+            levels.append({"box": ([t(b + ".0"), t(b + ".1")], *wb(b + ".2")),
+                           "cls": ([(t(c + ".0.0"), t(c + ".0.1")), (t(c + ".1.0"), t(c + ".1.1"))], *wb(c + ".2")),
+                           "angle": ([t(a + ".0"), t(a + ".1")], *wb(a + ".2"))})
+        self.head = DetectHead(levels, nc, gains, eps=eps, bn_momentum=bn_momentum, groups=self.groups)
+        self.groups.build()
+        self.scale, self.nc, self.ch, self.pack = scale, int(nc), int(ch), bool(pack)
+        self.plan, self._plan_hw = None, None
+        self.record_taps, self.taps = False, None
+
+    @classmethod
+    def from_state(cls, params, scale="n", nc=12, ch=3, **kw):
+        return cls(params, scale, nc, ch, **kw)
+
+    criterion = property(lambda self: self.head.criterion)
+
+    def named_blocks(self):
+        """[(state-dict name, layer)] in registration order: the trunk's Conv blocks, then per head branch its Conv blocks and its plain output conv"""
+        out = self.trunk.named_blocks()
+        h = self.head
+        for i in range(3):
+            out += [(f"model.23.cv2.{i}.{j}", b) for j, b in enumerate(h.box[i].chain)]
+        for i in range(3):
+            for j, p in enumerate(h.cls[i].pairs):
+                out += [(f"model.23.cv3.{i}.{j}.0", p.dw), (f"model.23.cv3.{i}.{j}.1", p.pw)]
+            out.append((f"model.23.cv3.{i}.2", h.cls[i].out))
+        for i in range(3):
+            out += [(f"model.23.cv4.{i}.{j}", b) for j, b in enumerate(h.angle[i].chain)]
+        return out
+
+    def fold(self):
+        """-> {state-dict name: (w, b)} of every conv of the model, fp32: eval-mode BN folded (the qkv convs in checkpoint channel order), the head's
+        plain output convs as they are."""
+        out = self.trunk.fold()
+        for name, b in self.named_blocks():
+            if name.startswith("model.23."):
+                out[name] = b.fold() if isinstance(b, _BNBlock) else (b.w, b.b)
+        return out
+
+    def _attach(self, H, W):
+        if not self.pack:
+            return
+        if self._plan_hw != (H, W):
+            if self.plan is not None:
+                self.plan.detach()
+            layers, shapes = self.trunk.pack_layers(H, W)
+            for name, b in self.named_blocks():
+                if name.startswith("model.23.") and hasattr(b, "_packed"):
+                    lv = (8, 16, 32)[int(name.split(".")[3])]
+                    layers.append(b); shapes.append((H // lv, W // lv))
+            self.plan, self._plan_hw = PackPlan(self.groups, layers, shapes), (H, W)
+        self.plan.run()
+
+    def forward_backward(self, tiles, gt_labels, gt_bboxes, mask_gt):
+        self._attach(tiles.shape[1], tiles.shape[2])
+        self.trunk.record_taps = self.record_taps
+        feats = self.trunk.forward(tiles)
+        box, cls, angle = self.head.forward(feats)
+        items, dlog = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
+        dfe = self.head.backward(*dlog)
+        self.trunk.backward(dfe)
+        self.taps = self.trunk.taps
+        if self.taps is not None:
+            self.taps[23] = {"in": feats, "out": (box, cls, angle), "dout": dlog, "din": dfe}
+        return items
 
 
 def clip_grad_norm(groups_or_flat_grads, max_norm=10.0):
