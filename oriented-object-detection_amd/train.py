@@ -974,7 +974,10 @@ class DetectHead(_Step):
     one dx per level, the sum of the three branches' input gradients through ops.add_bf16 in the fixed order (box + class) + angle;
     step(feats, gt_labels, gt_bboxes, mask_gt) = forward, criterion, backward, DDP gradient average, optimiser step -> (items, dx list).
     groups=: the head as part of a larger net (`Net`) on the caller's ParamGroups, which the caller builds; the branches are then registered in
-    checkpoint order (all box branches, all class branches, all angle branches)."""
+    checkpoint order (all box branches, all class branches, all angle branches).
+    `taps`: set `record_taps = True` and the next forward fills taps = {"in": feats, "out": (box, cls, angle)}; the next backward adds "dout" =
+    (d_box, d_cls, d_angle), "branch_din" = [(dx_box, dx_cls, dx_angle)] per level, "partial" = [bf16(dx_box + dx_cls)] per level and "din" = the
+    three sums it returns.  With the flag off nothing is kept (taps is None)."""
 
     def __init__(self, levels, nc, gains=(7.5, 0.5, 1.5), optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True, eps=1e-3,
                  bn_momentum=0.03, groups=None):
@@ -996,14 +999,25 @@ class DetectHead(_Step):
         if own:
             self.groups.build()
         self.criterion = OBBCriterion(nc, gains)
+        self.record_taps, self.taps = False, None
 
     def forward(self, feats):
-        return ([b.forward(x) for b, x in zip(self.box, feats)], [c.forward(x) for c, x in zip(self.cls, feats)],
-                [a.forward(x) for a, x in zip(self.angle, feats)])
+        out = ([b.forward(x) for b, x in zip(self.box, feats)], [c.forward(x) for c, x in zip(self.cls, feats)],
+               [a.forward(x) for a, x in zip(self.angle, feats)])
+        self.taps = {"in": list(feats), "out": out} if self.record_taps else None
+        return out
 
     def backward(self, d_box, d_cls, d_angle):
-        return [ops.add_bf16(ops.add_bf16(self.box[i].backward(d_box[i]), self.cls[i].backward(d_cls[i])), self.angle[i].backward(d_angle[i]))
-                for i in range(3)]
+        branch, partial, din = [], [], []
+        for i in range(3):
+            dxs = (self.box[i].backward(d_box[i]), self.cls[i].backward(d_cls[i]), self.angle[i].backward(d_angle[i]))
+            p = ops.add_bf16(dxs[0], dxs[1])
+            din.append(ops.add_bf16(p, dxs[2]))
+            if self.record_taps:
+                branch.append(dxs); partial.append(p)
+        if self.record_taps:
+            self.taps = dict(self.taps or {}, dout=(d_box, d_cls, d_angle), branch_din=branch, partial=partial, din=din)
+        return din
 
     def forward_backward(self, feats, gt_labels, gt_bboxes, mask_gt):
         box, cls, angle = self.forward(feats)
@@ -1227,7 +1241,8 @@ class Net(_Step):
     The dense convs' bf16 weights come from ONE launch per iteration (`PackPlan`, built lazily for the tile size seen, run first thing in
     forward_backward); `pack = False` packs per layer and call as the blocks do on their own -- the results are bit-identical.  `taps`: set
     `record_taps = True`; the next forward_backward fills taps[0..22] and taps["fan"] (`Trunk`) and taps[23] = {"in": [P3, P4, P5], "out": (box, cls,
-    angle), "dout": (d_box, d_cls, d_angle), "din": [d3, d4, d5]}."""
+    angle), "dout": (d_box, d_cls, d_angle), "din": [d3, d4, d5]} plus the head's own "branch_din" and "partial" (`DetectHead`: the three summands of
+    every d and the sum of the first two)."""
 
     def __init__(self, params, scale="n", nc=12, ch=3, gains=(7.5, 0.5, 1.5), optimizer="SGD", lr=0.01, momentum=0.9, weight_decay=5e-4, nesterov=True,
                  eps=1e-3, bn_momentum=0.03, pack=True):
@@ -1295,7 +1310,7 @@ class Net(_Step):
 
     def forward_backward(self, tiles, gt_labels, gt_bboxes, mask_gt):
         self._attach(tiles.shape[1], tiles.shape[2])
-        self.trunk.record_taps = self.record_taps
+        self.trunk.record_taps = self.head.record_taps = self.record_taps
         feats = self.trunk.forward(tiles)
         box, cls, angle = self.head.forward(feats)
         items, dlog = self.criterion(box, cls, angle, gt_labels, gt_bboxes, mask_gt)
@@ -1303,7 +1318,8 @@ class Net(_Step):
         self.trunk.backward(dfe)
         self.taps = self.trunk.taps
         if self.taps is not None:
-            self.taps[23] = {"in": feats, "out": (box, cls, angle), "dout": dlog, "din": dfe}
+            h = self.head.taps
+            self.taps[23] = {"in": feats, "out": (box, cls, angle), "dout": dlog, "din": dfe, "branch_din": h["branch_din"], "partial": h["partial"]}
         return items
 
 

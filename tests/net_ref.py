@@ -9,6 +9,10 @@
   module_input(i, outs, wiring)   what the yaml graph feeds module i, built from the modules' outputs with torch cat and nearest upsample (NHWC)
   eval_forward(folded, tiles, nc, wiring)   the eval-mode forward in fp64 on folded weights, written from WIRING and torch.nn.functional alone: an
                                   independent statement of the graph to hold against oracle.yolo11_obb.Yolo11OBB.forward_raw
+  check_wiring / check_head_wiring(taps)    the bit-for-bit wiring checks on train.Trunk's / Net's / DetectHead's taps; StandInTrunk / StandInHead
+                                  produce taps of the same format on the CPU, with planted mistakes
+  module_spec / run_module / module_refs    the trunk's modules restated from the block_ref / route_ref / attn_ref / dw_ref leaves
+  head_spec / run_branch / branch_refs / collect_branch    the nine branches of model.23 from the state dict (dw_ref.RefBlock, narrow_ref.RefHead)
 """
 import math
 
@@ -207,11 +211,33 @@ def _din_slot(taps, consumer, t):
     return taps[consumer]["din"][0 if w[1] == t else 1]
 
 
+def _add(a, b):
+    return (a.float() + b.float()).to(torch.bfloat16)
+
+
+def check_head_wiring(taps, received=True):
+    """AssertionError unless the head's gradient sum in taps[23] (train.DetectHead's tap keys) is, per level and bit for bit, partial = bf16(fp32(dx_box)
+    + fp32(dx_cls)) and din = bf16(fp32(partial) + fp32(dx_angle)); received: din is also the tensor the trunk took in -- the FIRST summand of the
+    fan-outs 16 and 19, model.22's dout (not for a head driven on its own)."""
+    h = taps[23]
+    assert len(h["branch_din"]) == len(h["partial"]) == len(h["din"]) == 3
+    for lv, t in enumerate(HEAD_FROM):
+        dxb, dxc, dxa = h["branch_din"][lv]
+        assert _same(h["partial"][lv], _add(dxb, dxc)), f"head level {lv}: the partial sum is not bf16(box + cls)"
+        assert _same(h["din"][lv], _add(h["partial"][lv], dxa)), f"head level {lv}: the sum is not bf16((box + cls) + angle)"
+        if received:
+            got = taps["fan"][t][0] if t in FAN else taps[t]["dout"]
+            assert _same(got, h["din"][lv]), f"head level {lv}: model.{t} did not receive the head's sum"
+
+
 def check_wiring(taps):
     """AssertionError unless `taps` (train.Trunk's / Net's format, taps[23] = {"in": [P3, P4, P5], "din": [d3, d4, d5]}) is the yaml graph bit for
     bit: every module's input is built from the tapped outputs (torch cat, nearest upsample), the concats hand their gradient halves back (the
     upsampled half as the fp32 sum of its 2 x 2 pixels, one rounding), a tensor with one consumer receives that consumer's gradient, and each of
-    the six fan-out tensors receives bf16(fp32(first) + fp32(second)) of its two consumers' gradients in FAN's order."""
+    the six fan-out tensors receives bf16(fp32(first) + fp32(second)) of its two consumers' gradients in FAN's order.  Where taps[23] carries the
+    head's own keys ("branch_din", "partial") the head's sum is checked too (check_head_wiring)."""
+    if "branch_din" in taps[23]:
+        check_head_wiring(taps)
     consumers = {i: [] for i in ORDER}
     for c, w in WIRING.items():
         for t in w[1:]:
@@ -283,7 +309,7 @@ class StandInTrunk:
         return torch.autograd.grad(y, xr, d.float())[0].to(torch.bfloat16)
 
     def run(self, x, d_of):
-        """x bf16 [B,H,W,3]; d_of(feats) -> [d3, d4, d5] -> taps"""
+        """x bf16 [B,H,W,3]; d_of(feats) -> [d3, d4, d5], or a head's tap dict with them under "din" (StandInHead) -> taps"""
         taps, outs = {"fan": {}}, {}
         for i in ORDER:
             if i == 0:
@@ -299,8 +325,9 @@ class StandInTrunk:
             taps[i] = {"in": xin, "out": outs[i]}
         feats = [outs[t] for t in HEAD_FROM]
         d = d_of(feats)
-        taps[23] = {"in": feats, "din": d}
-        pend = {t: [(23, g)] for t, g in zip(HEAD_FROM, d)}   # tensor -> [(consumer, gradient)] in arrival order
+        head, d = (d, d["din"]) if isinstance(d, dict) else ({}, d)
+        taps[23] = {**head, "in": feats, "din": d}
+        pend ={t: [(23, g)] for t, g in zip(HEAD_FROM, d)}   # tensor -> [(consumer, gradient)] in arrival order
         for i in reversed(ORDER):
             got = pend.get(i, [])
             if i in FAN:
@@ -331,6 +358,33 @@ class StandInTrunk:
                 pend.setdefault(w[2], []).append((i, din[1]))
             taps[i].update(dout=dout, din=din)
         return taps
+
+
+class StandInHead:
+    """A CPU stand-in for the gradient sum of train.DetectHead.backward in its tap format: the three branch gradients of a level are given, the
+    sums are restated.  mistake at `level` (the other levels are summed correctly): "drop_angle" returns box + cls, "drop_cls" box + angle,
+    "order" (box + angle) + cls."""
+
+    def __init__(self, mistake=None, level=None):
+        self.mistake, self.level = mistake, level
+
+    def backward(self, branch_din):
+        partial, din = [], []
+        for lv, (b, c, a) in enumerate(branch_din):
+            wrong = self.mistake if lv == self.level else None
+            if wrong == "drop_angle":
+                p = s = _add(b, c)
+            elif wrong == "drop_cls":
+                p = b
+                s = _add(p, a)
+            elif wrong == "order":
+                p = _add(b, a)
+                s = _add(p, c)
+            else:
+                p = _add(b, c)
+                s = _add(p, a)
+            partial.append(p); din.append(s)
+        return {"branch_din": [tuple(t) for t in branch_din], "partial": partial, "din": din}
 
 
 # ============================================================================================== training-mode restatement from the leaves
@@ -518,8 +572,96 @@ def ref_module_inputs(st, tiles):
 
 
 def check_module(what, got, rounded, plain):
-    """block_ref.assert_within with the three vacuous dbeta quantities left out of the assertion (printed all the same)"""
+    """block_ref.assert_within with the three vacuous dbeta quantities left out of the assertion (printed all the same) -> the worst asserted
+    figure / bound"""
     fig, bnd = BR.figures(got, rounded), BR.bounds(rounded, plain)
     print(f"{what}: " + ", ".join(f"{n} {fig[n]:.2e} / {bnd[n]:.2e}" for n in fig))
     bad = {n: (fig[n], bnd[n]) for n in fig if not n.endswith(VACUOUS) and not fig[n] <= bnd[n]}
     assert not bad, (what, bad)
+    return max(fig[n] / bnd[n] for n in fig if not n.endswith(VACUOUS))
+
+
+# ============================================================================================== the head's nine branches from the state dict
+import narrow_ref as NW  # noqa: E402
+
+HEAD_KINDS = ("box", "cls", "angle")
+HEAD_CV = {"box": "cv2", "cls": "cv3", "angle": "cv4"}
+# the layers of model.23 whose shape is the same at all three levels (a level mix-up among them raises nothing): {family: names under cv?.<level>}
+HEAD_SAME_SHAPE = {"cv2": ("1", "2"), "cv3": ("1.0", "1.1", "2"), "cv4": ("1", "2")}
+
+
+def _plain_conv(st, name):
+    w, b = (st[f"{name}.{k}"].detach().cpu().float() for k in ("weight", "bias"))
+    R = NW.RefHead(torch.Generator().manual_seed(0), w.shape[1], w.shape[0])
+    R.init = (w.clone(), b.clone())
+    R.reset()
+    return R
+
+
+def head_spec(st, level):
+    """{"box" | "cls" | "angle": [(name under model.23.cv?.<level>, leaf)]} of one level with the state dict's parameters in the leaves, as
+    criterion_ref.head_case builds them: dw_ref.RefBlock per Conv block, narrow_ref.RefHead ("out") for the plain output conv."""
+    def three(q):
+        return [("0", _block(st, q + ".0", True)), ("1", _block(st, q + ".1", True)), ("out", _plain_conv(st, q + ".2"))]
+    c = f"model.23.cv3.{level}"
+    return {"box": three(f"model.23.cv2.{level}"), "angle": three(f"model.23.cv4.{level}"),
+            "cls": [(f"{i}.{j}", _block(st, f"{c}.{i}.{j}", True)) for i in (0, 1) for j in (0, 1)] + [("out", _plain_conv(st, c + ".2"))]}
+
+
+def run_branch(kind, spec, x, dy, plain):
+    """One branch of head_spec's `spec` from its own input x (bf16 NHWC) and the gradient dy of its logits (NHWC: bf16 for box, fp32 for cls and
+    angle) -> {out, dx, <leaf>.dW / dgamma / dbeta / rmean / rvar, out.dW, out.db}, NCHW.  plain: the nn.Module stack in fp64; else the rounding
+    points of criterion_ref.run_head: the leaves' own (weights, z, a; da, dz, dx), the box logits and their gradient bf16, the class and angle
+    logits fp32 with their gradient rounded to bf16 where the output conv reads it."""
+    leaves = spec[kind]
+    for _, m in leaves:
+        m.reset()
+    xr = x.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
+    a = xr
+    for _, m in leaves:
+        a = m(a, not plain)
+    if kind == "box" and not plain:
+        a = DR._GradBf16.apply(DR._q(a))
+    a.backward(dy.double().permute(0, 3, 1, 2))
+    out = {"out": a.detach().clone(), "dx": xr.grad.clone()}
+    for name, m in leaves:
+        out.update(m.results(name + "."))
+    return out
+
+
+def branch_refs(st, level, kind, x, dy):
+    """-> (rounded, plain)"""
+    spec = head_spec(st, level)
+    plain = run_branch(kind, spec, x, dy, True)
+    return run_branch(kind, spec, x, dy, False), plain
+
+
+def collect_branch(kind, br, out, dx):
+    """a branch of train.DetectHead after forward + backward -> run_branch's names (copies on the CPU), every gradient read through the layer's
+    OWN view of the flat buffers"""
+    nchw = lambda t: t.double().cpu().permute(0, 3, 1, 2)
+    blocks = [(f"{i}.{j}", b) for i, p in enumerate(br.pairs) for j, b in enumerate((p.dw, p.pw))] if kind == "cls" else \
+        [(str(i), b) for i, b in enumerate(br.blocks)]
+    got = {"out": nchw(out), "dx": nchw(dx), "out.dW": br.out.dw.cpu(), "out.db": br.out.db.cpu()}
+    for name, d in blocks:
+        got.update({f"{name}.{k}": t.cpu() for k, t in (("dW", d.dw), ("dgamma", d.dgamma), ("dbeta", d.dbeta), ("rmean", d.running_mean), ("rvar", d.running_var))})
+    return got
+
+
+BACKWARD_KINDS = ("dx", "dW", "dgamma", "dbeta", "db")
+
+
+def head_dense_grads(seed, maps, nc):
+    """A full gradient for every logit of every level (the second drive of the head tests): maps = [(B, H, W)] per level -> (d_box bf16 on
+    dw_ref._grad_in's grid, d_cls fp32 N(0, 0.1^2) -- NOT bf16 values: the output conv's backward rounds them as it loads --, d_angle fp32 on the grid)"""
+    g = torch.Generator().manual_seed(seed)
+    return ([DR._grad_in(g, *m, 64) for m in maps], [torch.randn(*m, nc, generator=g) * 0.1 for m in maps],
+            [DR._grad_in(g, *m, 1).float() for m in maps])
+
+
+def fold_of_state(st, name, running_mean=None, running_var=None, eps=1e-3):
+    """(w, b) of layer `name` folded from the STATE DICT's parameters and the given running statistics, in train._BNBlock.fold's operation order"""
+    if is_plain(name):
+        return st[name + ".weight"], st[name + ".bias"]
+    f = st[name + ".bn.weight"] / torch.sqrt(running_var + eps)
+    return st[name + ".conv.weight"] * f.view(-1, 1, 1, 1), st[name + ".bn.bias"] - running_mean * f

@@ -149,7 +149,8 @@ def sppf_case(B, H, W, c1, c2):
 BF, U = 2.0 ** -8, 2.0 ** -24
 # A figure of (nearly) zero gives no bound by itself: the bound is then the reference's own grain -- one flipped bf16 rounding of the largest element
 # for the bf16 tensors, the fp32 reference's summation error (16 roundings of 2^-24) for the fp32 gradients and statistics.
-FLOOR = {"out": BF, "dx": BF, "dskip": BF, "dW": 16 * U, "dgamma": 16 * U, "dbeta": 16 * U, "rmean": 16 * U, "rvar": 16 * U}
+FLOOR = {"out": BF, "dx": BF, "dskip": BF, "dW": 16 * U, "dgamma": 16 * U, "dbeta": 16 * U, "rmean": 16 * U, "rvar": 16 * U,
+         "db": 16 * U}  # (db: the bias gradient of the head's plain output convs, a per-channel sum of the incoming gradient like dbeta)
 # measured (MI355X), max |d| / max |ref| of every compared quantity, per SPPF case (B, H, W, c1, c2); asserted at 2.5 x its own figure
 SPPF_MEASURED = {
     (2, 13, 13, 256, 256): {"out": 3.09e-3, "dx": 6.87e-3, "cv1.dW": 5.91e-3, "cv1.dgamma": 1.09e-2, "cv1.dbeta": 1.54e-2, "cv1.rmean": 6.89e-7,

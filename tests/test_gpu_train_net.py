@@ -2,11 +2,16 @@
 builds from the tapped outputs; every fan-out gradient is bf16(fp32 + fp32) of its two tapped contributions in the documented order), the pack plan
 against per-layer packing, Net against its parts driven by hand, and two trainer steps against the same iterations driven by hand.  The modules
 of the trunk are then run by the fp64 references from their own tapped input and gradient (net_ref.module_refs) under block_ref's bound, and the
-whole trunk is held against one plain fp64 autograd graph (figures only)."""
+whole trunk is held against one plain fp64 autograd graph (figures only).  The head inside the net (n at three tile shapes and the whole s net): its
+gradient sum bit for bit from the head's own taps, each of the nine branches by the fp64 references built from the state dict (net_ref.head_spec /
+run_branch) from its own tapped input and gradient under the same bound -- once under the criterion's gradients, once under dense seeded ones --,
+the criterion per element on the net's own logits (criterion_ref's bounds), and the head's fold() against the state dict."""
 import pytest
 import torch
 
+import criterion_ref as CR
 import net_ref as NR
+from bounds import _check
 
 pytestmark = pytest.mark.gpu
 
@@ -37,6 +42,10 @@ def _state_of(net):
 
 
 def _check_wiring(taps, head=True):
+    """head: taps[23] carries the head's own summands, and check_wiring holds the head's sum with them"""
+    if head:
+        assert {"branch_din", "partial"} <= set(taps[23])
+        NR.check_head_wiring(taps)
     NR.check_wiring(taps)
 
 
@@ -66,7 +75,7 @@ def test_net_wiring_bit_for_bit(H, W, ch):
     assert all(some.values()), some
     net.record_taps = False
     net.forward_backward(_tiles(H, W, ch), *gt)
-    assert net.taps is None  # (filled only when asked)
+    assert net.taps is None and net.head.taps is None  # (filled only when asked)
 
 
 def test_trunk_s_wiring_bit_for_bit():
@@ -84,7 +93,7 @@ def test_trunk_s_wiring_bit_for_bit():
     torch.cuda.synchronize()
     taps = trunk.taps
     taps[23] = {"in": feats, "din": d}  # (the three gradients stand in for the head's)
-    _check_wiring(taps, head=True)
+    _check_wiring(taps, head=False)
     assert bool(torch.isfinite(groups.opts[0].grad).all())
     for name, b in trunk.named_blocks():
         assert float(b.dw.abs().max()) > 0, name
@@ -246,3 +255,166 @@ def test_stale_plan_is_refused():
     net.plan.run()
     net.trunk.forward(tiles)
     assert bool(torch.isfinite(net.forward_backward(tiles, *gt)).all())
+
+
+# ---------------------------------------------------------------------------------------------- the head inside the net
+_HEAD_CASES = {}
+
+
+def _head_case(case):
+    """One whole Net per net_ref.MODULE_CASES entry (n AND s), run once and shared by the head tests below: forward_backward under the criterion
+    with taps (drive "criterion"), then DetectHead.backward once more from the same forward under net_ref.head_dense_grads (drive "dense": every
+    branch of every level receives a full gradient whatever the assigner did).  The branch backward OVERWRITES its gradient views (every kernel
+    writes its whole output: train.py hands the views as `out=`), so nothing is zeroed between the drives; what the first drive left is copied to
+    the CPU before the second runs.  A failure is kept and raised again: nothing runs twice."""
+    if case in _HEAD_CASES:
+        if isinstance(_HEAD_CASES[case], BaseException):
+            raise _HEAD_CASES[case]
+        return _HEAD_CASES[case]
+    try:
+        _HEAD_CASES[case] = _run_head_case(*case)
+    except BaseException as e:
+        _HEAD_CASES[case] = e
+        raise
+    return _HEAD_CASES[case]
+
+
+def _collect_head(net, h):
+    return {(lv, kind): NR.collect_branch(kind, getattr(net.head, kind)[lv], h["out"][k][lv], h["branch_din"][lv][k])
+            for lv in range(3) for k, kind in enumerate(NR.HEAD_KINDS)}
+
+
+def _run_head_case(scale, ch, H, W, seed):
+    TR = _train()
+    st = NR.make_state(scale, 12, ch, seed=seed)
+    tiles = torch.randint(0, 256, (2, H, W, ch), dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
+    net = TR.Net.from_state({k: v.cuda() for k, v in st.items()}, scale, 12, ch)
+    net.record_taps = True
+    items = net.forward_backward(tiles.cuda(), *TR.pad_targets(ROWS, 2, (H, W), device="cuda"))
+    torch.cuda.synchronize()
+    taps, h = net.taps, net.taps[23]
+    cpu = lambda ts: [t.detach().cpu() for t in ts]
+    c = {"st": st, "net": net, "taps": taps, "items": items.cpu(), "x": cpu(h["in"]), "imgsz": (H, W)}
+    c["dout"] = {"criterion": tuple(cpu(d) for d in h["dout"])}
+    c["got"] = {"criterion": _collect_head(net, h)}
+    c["fold"] = {n: (w.clone(), b.clone()) for n, (w, b) in net.fold().items() if n.startswith("model.23.")}
+    c["last"] = {k: v.cpu() for k, v in net.criterion.last.items()}
+    dense = NR.head_dense_grads(seed + 200, [tuple(x.shape[:3]) for x in c["x"]], 12)
+    din = net.head.backward(*[[t.cuda() for t in d] for d in dense])
+    torch.cuda.synchronize()
+    hb = net.head.taps
+    assert all(_bits(a, b) for a, b in zip(din, hb["din"])) and all(_bits(a, b) for a, b in zip(hb["in"], h["in"]))
+    c["dout"]["dense"], c["got"]["dense"], c["taps_dense"] = dense, _collect_head(net, hb), {23: hb}
+    c["refs"] = {}
+    return c
+
+
+def _branch_refs(c, drive, lv, kind):
+    """(rounded, plain) of one branch under one drive, computed once per case"""
+    key = (drive, lv, kind)
+    if key not in c["refs"]:
+        c["refs"][key] = NR.branch_refs(c["st"], lv, kind, c["x"][lv], c["dout"][drive][NR.HEAD_KINDS.index(kind)][lv])
+    return c["refs"][key]
+
+
+def _fg_per_level(c):
+    fg = c["last"]["fg_mask"].bool()
+    return [int(t.sum()) for t in CR.split_levels(fg[..., None], c["imgsz"])]
+
+
+@pytest.mark.parametrize("case", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_head_sum_bit_for_bit(case):
+    """The whole net's wiring with the head's sum -- partial = bf16(box + cls), din = bf16(partial + angle), din what models 16, 19 and 22 received --
+    for n at the three tile shapes and for the WHOLE s net under the criterion, and the same sum under the dense drive."""
+    c = _head_case(case)
+    H, W = c["imgsz"]
+    assert bool(torch.isfinite(c["items"]).all()) and float(c["items"].sum()) > 0
+    assert [tuple(t.shape[1:3]) for t in c["taps"][23]["in"]] == [(H // 8, W // 8), (H // 16, W // 16), (H // 32, W // 32)]
+    _check_wiring(c["taps"], head=True)
+    NR.check_head_wiring(c["taps_dense"], received=False)
+    for o in c["net"].groups.opts:
+        assert bool(torch.isfinite(o.grad).all())
+
+
+@pytest.mark.parametrize("drive", ["criterion", "dense"])
+@pytest.mark.parametrize("case", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_each_head_branch_from_its_own_tapped_input_and_gradient(case, drive):
+    """The nine branches of model.23 inside the net (yolo11n: widths 64 / 64 / 16 on 64 / 128 / 256 channels; yolo11s: 64 / 128 / 32 on 128 / 256 /
+    512; nc = 12; maps 8^2 / 4^2 / 2^2 or 8 x 12 / 4 x 6 / 2 x 3), each run by the fp64 references built from the STATE DICT under its checkpoint
+    name (net_ref.head_spec: a level or slot mix-up in Net.__init__ feeds the device other weights than the reference) from the input and the logit
+    gradient the device fed it: out, dx, every dW / dgamma / dbeta / running statistic, out.dW and out.db -- each device gradient read through the
+    layer's own view of the flat buffers -- under block_ref's bound max(FLOOR, 4 x grain) from the two references alone.
+    criterion: what the net did.  A level without a foreground anchor sends exact zeros into its box and angle branches: every backward quantity
+    of those two is then required to be EXACTLY zero (and is not compared under a relative figure).  dense: net_ref.head_dense_grads."""
+    c = _head_case(case)
+    nfg = _fg_per_level(c)
+    print(f"  {case} {drive}: foreground anchors per level {nfg}")
+    worst = {k: 0.0 for k in NR.HEAD_KINDS}
+    for lv in range(3):
+        for k, kind in enumerate(NR.HEAD_KINDS):
+            got = dict(c["got"][drive][(lv, kind)])
+            rounded, plain = (dict(r) for r in _branch_refs(c, drive, lv, kind))
+            assert set(got) == set(rounded) == set(plain)
+            if drive == "criterion" and kind != "cls" and nfg[lv] == 0:
+                assert not bool(c["dout"][drive][k][lv].float().any()), (lv, kind)
+                zero = [n for n in got if n.split(".")[-1] in NR.BACKWARD_KINDS]
+                assert len(zero) == 9  # dx, two blocks' dW / dgamma / dbeta, out.dW, out.db
+                for n in zero:
+                    assert not bool(got[n].any()), (lv, kind, n)
+                    got.pop(n), rounded.pop(n), plain.pop(n)
+                print(f"  {case} level {lv} {kind}: no foreground anchor, the {len(zero)} backward quantities are exactly zero")
+            w = NR.check_module(f"{case} {drive} model.23.{NR.HEAD_CV[kind]}.{lv}", got, rounded, plain)
+            worst[kind] = max(worst[kind], w)
+    print(f"  {case} {drive}: worst figure / bound " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("case", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_criterion_on_the_nets_own_logits(case):
+    """items, tss and the three logit gradients of OBBCriterion inside the net, and a fresh ops.crit_decode, per element against criterion_ref's fp64
+    restatement and bounds on the TAPPED logits and the device's own assignment: nc = 12 at A = 84 (64 x 64: levels 8^2, 4^2, 2^2) and A = 126
+    (64 x 96: 8 x 12, 4 x 6, 2 x 3), n and s.  (The assigner's discrete outputs are test_gpu_train_loss.py's subject.)"""
+    from oriented_object_detection_amd import ops
+    c = _head_case(case)
+    imgsz, last = c["imgsz"], c["last"]
+    box, cls, ang = c["taps"][23]["out"]
+    A = sum(h * w for h, w in CR.level_shapes(imgsz))
+    assert A == (84 if imgsz == (64, 64) else 126) and cls[0].shape[-1] == 12
+    fb, fc, fa = CR.cat_levels([t.float().cpu() for t in box]), CR.cat_levels([t.cpu() for t in cls]), CR.cat_levels([t.cpu() for t in ang])[..., 0]
+    fg = last["fg_mask"].bool()
+    assert fg.shape == (2, A) and int(fg.sum()) >= 1
+    ref, bound = CR.crit_bounds(fb, fc, fa, last["target_bboxes"], last["target_scores"], fg, imgsz)
+    d_box, d_cls, d_ang = c["dout"]["criterion"]
+    what = f"{case} in-net"
+    _check(f"{what} items", c["items"], ref["items"], bound["items"])
+    _check(f"{what} tss", last["tss"], ref["tss"], bound["tss"])
+    _check(f"{what} d_box", CR.cat_levels([t.float() for t in d_box]), ref["d_box"], bound["d_box"])
+    _check(f"{what} d_cls", CR.cat_levels(d_cls), ref["d_cls"], bound["d_cls"])
+    _check(f"{what} d_angle", CR.cat_levels(d_ang)[..., 0], ref["d_ang"], bound["d_ang"])
+    gb, ga = CR.cat_levels([t.float() for t in d_box]), CR.cat_levels(d_ang)[..., 0]
+    assert bool((gb[~fg] == 0).all()) and bool((ga[~fg] == 0).all())  # background anchors: exact zeros
+    ps, pb, ap, st = ops.crit_decode(list(box), list(cls), list(ang))
+    (rps, rpb), (bps, bpb) = CR.decode_bounds(fb, fc, fa, imgsz)
+    _check(f"{what} pd_scores", ps, rps, bps)
+    _check(f"{what} pd_bboxes", pb, rpb, bpb)
+    anc, strides = CR.anchors(imgsz)
+    assert torch.equal(ap.double().cpu(), anc * strides[:, None]) and torch.equal(st.double().cpu(), strides)
+
+
+@pytest.mark.parametrize("case", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_head_fold_against_the_state_dict(case):
+    """Net.fold()'s model.23 entries against a fold computed from the STATE DICT's parameters under each layer's checkpoint name and the device's
+    running statistics after the forward (held against the references by the branch test), bit for bit; the statistics moved."""
+    c = _head_case(case)
+    blocks = dict(c["net"].named_blocks())
+    st = {k: v.cuda() for k, v in c["st"].items() if k.startswith("model.23.")}  # (folded on the device, with fold()'s own operations: same bits)
+    names = [n for n in NR.conv_table(case[0], 12, case[1]) if n.startswith("model.23.")]
+    assert set(c["fold"]) == set(names) and len(names) == 33
+    for n in names:
+        b = blocks[n]
+        plain = NR.is_plain(n)
+        rm, rv = (None, None) if plain else (b.running_mean, b.running_var)
+        we, be = NR.fold_of_state(st, n, rm, rv, b.eps if not plain else None)
+        w, bb = c["fold"][n]
+        assert torch.equal(w, we) and torch.equal(bb, be), n
+        if not plain:
+            assert not torch.equal(rm, st[n + ".bn.running_mean"]) and not torch.equal(rv, st[n + ".bn.running_var"]), n

@@ -173,3 +173,93 @@ def test_module_bounds_stay_below_half(scale, ch, H, W, seed):
     top = sorted(worst.items(), key=lambda kv: -kv[1])[:5]
     print("  largest bounds:", ", ".join(f"{n} {b:.3f}" for n, b in top))
     assert top[0][1] < 0.5, top
+
+
+# ---------------------------------------------------------------------------------------------- the head inside the net
+def _branch_dx_of(g):
+    return lambda fs: [tuple((torch.randn(f.shape, generator=g) * 0.1).to(torch.bfloat16) for _ in range(3)) for f in fs]
+
+
+def test_head_wiring_check_catches_planted_mistakes():
+    """net_ref.check_head_wiring (through check_wiring, as the GPU test applies it to the device's taps) passes a stand-in head that sums (box + cls)
+    + angle and fails, at each of the three levels, one that drops the angle summand, one that drops the class summand and one that sums
+    (box + angle) + cls -- on inputs for which that order changes at least one bit of the sum."""
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(2, 64, 96, 3, generator=g).to(torch.bfloat16)
+    dx_of = _branch_dx_of(g)
+    kept = {}
+
+    def d_of(head):
+        def f(fs):
+            kept["dx"] = dx_of(fs)
+            return head.backward(kept["dx"])
+        return f
+    taps = NR.StandInTrunk().run(x, d_of(NR.StandInHead()))
+    assert "branch_din" in taps[23] and "partial" in taps[23]
+    NR.check_wiring(taps)
+    NR.check_head_wiring(taps)
+    for lv in range(3):
+        for mistake, msg in (("drop_angle", "the sum is not"), ("drop_cls", "the partial sum is not"), ("order", "the partial sum is not")):
+            with pytest.raises(AssertionError, match=rf"head level {lv}: {msg}"):
+                NR.check_wiring(NR.StandInTrunk().run(x, d_of(NR.StandInHead(mistake, lv))))
+            if mistake == "order":  # the inputs just used: the two orders give different bits at this level
+                b, c, a = kept["dx"][lv]
+                assert not NR._same(NR._add(NR._add(b, c), a), NR._add(NR._add(b, a), c))
+    # a sum the trunk did not receive (the head returned something else than it recorded)
+    taps = NR.StandInTrunk().run(x, d_of(NR.StandInHead()))
+    taps[23]["din"] = [t.clone() for t in taps[23]["din"]]
+    taps[23]["din"][1][0, 0, 0, 0] += 1.0
+    with pytest.raises(AssertionError, match="head level 1"):
+        NR.check_head_wiring(taps)
+
+
+@pytest.mark.parametrize("scale,ch,H,W,seed", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_head_same_shape_layers_differ_between_levels(scale, ch, H, W, seed):
+    """The layers of model.23 whose shapes are the same at all three levels hold different values at every level in the state dicts the GPU test
+    uses (net_ref.make_state draws every tensor on its own), so the references built from model.23.cv3.1.1.* are not those of cv3.2.1.*: a level
+    mix-up in Net.__init__ cannot pass the per-branch comparison."""
+    st = NR.make_state(scale, 12, ch, seed=seed)
+    n = 0
+    for fam, names in NR.HEAD_SAME_SHAPE.items():
+        for name in names:
+            keys = [k[len(f"model.23.{fam}.0.{name}"):] for k in st if k.startswith(f"model.23.{fam}.0.{name}.")]
+            assert keys
+            for key in keys:
+                t = [st[f"model.23.{fam}.{lv}.{name}{key}"] for lv in range(3)]
+                assert t[0].shape == t[1].shape == t[2].shape, (fam, name, key)
+                for i, j in ((0, 1), (0, 2), (1, 2)):
+                    assert float((t[i] - t[j]).abs().max()) > 1e-2 * float(t[i].abs().max()), (fam, name, key, i, j)
+                    n += 1
+    assert n == 3 * (4 * 5 + 3 * 2)  # four Conv blocks of five tensors, three plain convs of two, three level pairs each
+    x = torch.randn(2, 4, 4, st["model.23.cv3.1.1.0.conv.weight"].shape[0], generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+    outs = []
+    for lv in (1, 2):  # and the references themselves: the second class pair of levels 1 and 2 on one input
+        a = x.double().permute(0, 3, 1, 2)
+        for name, m in NR.head_spec(st, lv)["cls"][2:4]:
+            m.reset()
+            a = m(a, True)
+        outs.append(a.detach())
+    assert NR.DR.rel_dist(outs[0], outs[1]) > 0.5
+
+
+@pytest.mark.parametrize("scale,ch,H,W,seed", NR.MODULE_CASES, ids=lambda v: str(v))
+def test_head_bounds_stay_below_half(scale, ch, H, W, seed):
+    """The bounds of the per-branch head test, max(FLOOR, 4 x grain), for the nine branches at the inputs they see inside the net (the rounded
+    restatement chained on the CPU) under the dense seeded gradients the GPU test's second drive uses (net_ref.head_dense_grads, seed + 200), from
+    the two references alone: none reaches 0.5, no quantity left out."""
+    st = NR.make_state(scale, 12, ch, seed=seed)
+    tiles = torch.randint(0, 256, (2, H, W, ch), dtype=torch.uint8, generator=torch.Generator().manual_seed(seed))
+    _, outs = NR.ref_module_inputs(st, tiles)
+    feats = [outs[t] for t in NR.HEAD_FROM]
+    dense = NR.head_dense_grads(seed + 200, [tuple(f.shape[:3]) for f in feats], 12)
+    worst = {}
+    for lv, x in enumerate(feats):
+        for k, kind in enumerate(NR.HEAD_KINDS):
+            rounded, plain = NR.branch_refs(st, lv, kind, x, dense[k][lv])
+            assert sum(n.endswith(("dW", "dgamma", "dbeta", "rmean", "rvar")) for n in rounded) == (20 if kind == "cls" else 10) + 1
+            for n, b in NR.BR.bounds(rounded, plain).items():
+                worst[f"{kind}.{lv}.{n}"] = b
+    assert len(worst) == 3 * (2 * 14 + 24)
+    top = sorted(worst.items(), key=lambda kv: -kv[1])[:5]
+    print("  largest head bounds:", ", ".join(f"{n} {b:.3f}" for n, b in top))
+    assert top[0][1] < 0.5, top
