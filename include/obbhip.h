@@ -520,6 +520,53 @@ int obb_adamw_step_multi(obb_ctx *ctx, float *const *param, const float *const *
 int obb_grad_accumulate(obb_ctx *ctx, float *const *acc, const float *const *grad, const int64_t *n, int32_t nseg, int32_t first, obb_stream_t s);
 int obb_ema_update(obb_ctx *ctx, float *const *ema, const float *const *src, const int64_t *n, int32_t nseg, double decay, obb_stream_t s);
 
+/* ------------------------------------------------------------------ f1 (training batches): the dataloader's augmentation, on the device */
+/* What the Ultralytics dataloader does to a tile between the disk and `model.train(...)` (Train_OBB.py:796-841 leaves every augmentation argument at
+ * its default: 4-image Mosaic with probability 1, RandomPerspective with translate 0.1 / scale 0.5 / degrees 0, RandomHSV 0.015 / 0.7 / 0.4, fliplr
+ * 0.5), restated from recall: Ultralytics 8.3.x and cv2 are not installed, so parity with them is UNPINNED, like the criterion chain above; pinned
+ * is the device against this repository's numpy / fp64 restatement (tests/aug_ref.py).
+ *
+ * Both entries read one device TABLE of B records of OBB_AUG_REC_BYTES bytes, 8-byte aligned, one per output tile:
+ *   offset   0  double inv[6]    the map output pixel -> canvas, rows (m00 m01 m02) (m10 m11 m12); the host inverts M in double
+ *   offset  48  double fwd[6]    M, canvas -> output: M = T R C of RandomPerspective.affine_transform with shear and perspective at 0
+ *   offset  96  double scale     the scale factor inside R (box_candidates multiplies the boxes before the warp by it)
+ *   offset 104  int32  xc, yc    the mosaic centre on the canvas, 0 <= xc, yc <= 2 s
+ *   offset 112  int32  src[4]    pool tiles of the quadrants top-left, top-right, bottom-left, bottom-right; src[0] alone without mosaic
+ *   offset 128  uint32 flags     OBB_AUG_MOSAIC | OBB_AUG_FLIPLR | OBB_AUG_FLIPUD | OBB_AUG_HSV
+ *   offset 132  int32  reserved
+ *   offset 136  uint8  lut[768]  lut_h = (i r0) mod 180 | lut_s = clip(i r1, 0, 255) | lut_v = clip(i r2, 0, 255), float64 -> uint8 on the host
+ * The canvas is virtual: side S = 2 s with mosaic (pixel (u, v) belongs to the quadrant given by u < xc, v < yc and is pixel (u - padw, v - padh)
+ * of that quadrant's tile, pads (xc - s, yc - s), (xc, yc - s), (xc - s, yc), (xc, yc): `_mosaic4` for equal-sized images), S = s and canvas = tile
+ * src[0] without.  114 wherever that pixel is outside its tile, and outside the canvas.  The table is on the device, so the entries cannot look at
+ * it: a record with a source index outside [0, N) or a centre outside [0, 2 s] makes ITS tile a no-op (nothing of that tile is written).
+ *
+ * obb_aug_tiles: pool uint8 [N][s][s][C] (C = 3 or 4, 4-byte aligned at C = 4) -> out uint8 [B][s][s][C].  Per output pixel (x, y), mirrored first
+ * (x -> s - 1 - x, y -> s - 1 - y) under the flip bits: X = (rint(m00 x 1024) + rint((m01 y + m02) 1024) + 16) >> 5 and Y likewise (warpAffine's
+ * INTER_LINEAR fixed point), integer part X >> 5, fraction fx = X & 31, four canvas taps under the weights 32 (32 - fx)(32 - fy), 32 fx (32 - fy),
+ * 32 (32 - fx) fy, 32 fx fy, result (sum + 16384) >> 15.  With the HSV bit, channels 0..2 (channel 0 is B when bgr != 0, else R; channel 3 is
+ * warped only) go through cv2's 8-bit BGR -> HSV (H in 0..179), the three LUTs and the float HSV -> BGR with saturate(rint(255 x)); without it the
+ * warped bytes pass.  swap_rb != 0 swaps channels 0 and 2 on store.  2 <= s <= 16384, B <= 65535; a refused call writes nothing.
+ *
+ * obb_aug_labels: pool_labels double [N][Lmax][9] = class + 8 corner coordinates normalised to the tile (the tiler's rows), pool_counts int32 [N]
+ * -> what OBBCriterion reads: gt_labels int32 [B][n_cap], gt_bboxes float [B][n_cap][5] = (x, y, w, h, theta) in pixels, mask_gt uint8 [B][n_cap],
+ * count int32 [B].  Per candidate (quadrant q, label l), in fp64: corners to pixels, plus the quadrant's pad, clipped to [0, S]; M; the flips
+ * (x -> s - x, y -> s - y); box_candidates on the axis-aligned box before (times scale) and after (clipped to [0, s]): w, h > wh_thr, aspect <
+ * ar_thr, area after / before > area_thr; convex hull, clipped to [0, s]^2 (Sutherland-Hodgman, an empty result drops the label); the minimum-area
+ * enclosing rectangle over the hull's edge directions (what xyxyxyxy2xywhr gets from cv2.minAreaRect), theta in [0, pi/2), w the extent along
+ * (cos theta, sin theta), the first edge in hull order winning a tie; dropped when w < 2 or h < 2.  Survivors are compacted in (q, l) order; rows
+ * behind them are zero and masked out; count is the true number of survivors even past n_cap (rows past n_cap are dropped).
+ * Both entries only enqueue on the stream: no host read, no allocation, capturable. */
+#define OBB_AUG_REC_BYTES 904
+#define OBB_AUG_MOSAIC 1u
+#define OBB_AUG_FLIPLR 2u
+#define OBB_AUG_FLIPUD 4u
+#define OBB_AUG_HSV 8u
+int obb_aug_tiles(obb_ctx *ctx, const uint8_t *pool, int32_t N, int32_t s, int32_t C, const void *table, int32_t B, int32_t bgr, int32_t swap_rb,
+                  uint8_t *out, obb_stream_t st);
+int obb_aug_labels(obb_ctx *ctx, const double *pool_labels, const int32_t *pool_counts, int32_t N, int32_t Lmax, const void *table, int32_t B, int32_t s,
+                   double wh_thr, double ar_thr, double area_thr, int32_t n_cap, int32_t *gt_labels, float *gt_bboxes, uint8_t *mask_gt, int32_t *count,
+                   obb_stream_t st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,9 +109,12 @@ SIGNATURES = {
     "obb_adamw_step_multi": [_V, _V, _V, _V, _V, c_lp, c_fp, c_fp, C.c_int32, C.c_int64, C.c_double, C.c_double, C.c_float, _V, _V],
     "obb_grad_accumulate": [_V, _V, _V, c_lp, C.c_int32, C.c_int32, _V],
     "obb_ema_update": [_V, _V, _V, c_lp, C.c_int32, C.c_double, _V],
+    "obb_aug_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V],
+    "obb_aug_labels": [_V, _V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _V, _V, _V, _V, _V],
 }
 _RESTYPE = {"obb_last_error": C.c_char_p}
 PACK_TABLE_HEAD, PACK_TABLE_REC = 4, 8  # OBB_PACK_TABLE_HEAD / OBB_PACK_TABLE_REC: int64 words of obb_conv_pack_plan's table
+AUG_REC_BYTES = 904  # OBB_AUG_REC_BYTES: one record of the augmentation table (augment.REC is its numpy layout)
 
 
 class ObbHipError(RuntimeError):

@@ -443,6 +443,21 @@ def _ema_update(emas: List[T], srcs: List[T], decay: float) -> None:
     _call("obb_ema_update", ctx(emas[0].device), e, s, n, k, float(decay), _stream())
 
 
+# ---------------------------------------------------------------- f1 (training batches): augmentation (augment.py)
+@_op("aug_tiles", ("out",))
+def _aug_tiles(pool: T, table: T, bgr: bool, swap_rb: bool, out: T) -> None:
+    N, s, _, Cc = pool.shape
+    _call("obb_aug_tiles", ctx(pool.device), _p(pool), N, s, Cc, _p(table), table.shape[0], int(bool(bgr)), int(bool(swap_rb)), _p(out), _stream())
+
+
+@_op("aug_labels", ("gt_labels", "gt_bboxes", "mask_gt", "count"))
+def _aug_labels(pool_labels: T, pool_counts: T, table: T, s: int, wh_thr: float, ar_thr: float, area_thr: float, gt_labels: T, gt_bboxes: T, mask_gt: T,
+                count: T) -> None:
+    N, Lmax, _ = pool_labels.shape
+    _call("obb_aug_labels", ctx(pool_labels.device), _p(pool_labels), _p(pool_counts), N, Lmax, _p(table), table.shape[0], int(s), float(wh_thr), float(ar_thr),
+          float(area_thr), gt_labels.shape[1], _p(gt_labels), _p(gt_bboxes), _p(mask_gt), _p(count), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -1398,6 +1413,54 @@ def tile_labels(labels, rects, min_fraction=0.1):
     if lab.shape[0] and r.shape[0]:
         _O.tile_labels(lab, r, float(min_fraction), mask, out)
     return mask, out
+
+
+def _aug_table(table, fn):
+    t = _chk(table, torch.uint8, "table")
+    if t.dim() != 2 or t.shape[1] != _lib.AUG_REC_BYTES:
+        raise ValueError(f"{fn}: table must be uint8 [B, {_lib.AUG_REC_BYTES}] (augment.REC records), got {tuple(t.shape)}")
+    return t
+
+
+def aug_tiles(pool, table, bgr=True, swap_rb=False, out=None):
+    """The augmentation's pixel kernel (obb_aug_tiles): pool uint8 [N,s,s,C] (C = 3 or 4), table uint8 [B,904] (augment.REC records, on the device) ->
+    uint8 [B,s,s,C]: mosaic canvas, affine warp in warpAffine's fixed point, flips and HSV gains in one gather.  `out`: write into this buffer."""
+    p = _chk(pool, torch.uint8, "pool")
+    if p.dim() != 4:
+        raise ValueError("aug_tiles: pool must be [N, s, s, C]")
+    t = _aug_table(table, "aug_tiles")
+    N, s, s2, Cc = p.shape
+    if s != s2:
+        raise ValueError("aug_tiles: pool tiles must be square")
+    if out is None:
+        out = torch.empty((t.shape[0], s, s, Cc), dtype=torch.uint8, device=p.device)
+    elif _chk(out, torch.uint8, "out").shape != (t.shape[0], s, s, Cc):
+        raise ValueError(f"aug_tiles: out must be {(t.shape[0], s, s, Cc)}, got {tuple(out.shape)}")
+    _O.aug_tiles(p, t, bool(bgr), bool(swap_rb), out)
+    return out
+
+
+def aug_labels(pool_labels, pool_counts, table, s, n_cap, wh_thr=2.0, ar_thr=100.0, area_thr=0.01, out=None):
+    """The augmentation's label kernel (obb_aug_labels): pool_labels float64 [N,Lmax,9] (class + 8 normalised corners), pool_counts int32 [N], the same
+    table -> (gt_labels int32 [B,n_cap], gt_bboxes fp32 [B,n_cap,5], mask_gt bool [B,n_cap], count int32 [B]) as OBBCriterion reads them; count is the
+    true number of survivors per tile, also past n_cap.  `out`: the four buffers to write into.  No host read."""
+    pl = _chk(pool_labels, torch.float64, "pool_labels")
+    pc = _chk(pool_counts, torch.int32, "pool_counts")
+    t = _aug_table(table, "aug_labels")
+    if pl.dim() != 3 or pl.shape[2] != 9 or pc.shape != (pl.shape[0],):
+        raise ValueError("aug_labels: pool_labels must be [N, Lmax, 9] and pool_counts [N]")
+    B, n_cap = t.shape[0], int(n_cap)
+    if n_cap < 1:
+        raise ValueError("aug_labels: n_cap must be at least 1")
+    if out is None:
+        out = (torch.empty((B, n_cap), dtype=torch.int32, device=pl.device), torch.empty((B, n_cap, 5), dtype=torch.float32, device=pl.device),
+               torch.empty((B, n_cap), dtype=torch.bool, device=pl.device), torch.empty((B,), dtype=torch.int32, device=pl.device))
+    gl, gb, mk, cnt = out
+    _chk(gl, torch.int32, "gt_labels"); _chk(gb, torch.float32, "gt_bboxes"); _chk(mk, torch.bool, "mask_gt"); _chk(cnt, torch.int32, "count")
+    if gl.shape != (B, n_cap) or gb.shape != (B, n_cap, 5) or mk.shape != (B, n_cap) or cnt.shape != (B,):
+        raise ValueError("aug_labels: output buffers must be [B, n_cap], [B, n_cap, 5], [B, n_cap], [B]")
+    _O.aug_labels(pl, pc, t, int(s), float(wh_thr), float(ar_thr), float(area_thr), gl, gb, mk, cnt)
+    return gl, gb, mk, cnt
 
 
 def dfl_loss(pred_dist, target_ltrb, weight=None, target_scores_sum=1.0, reg_max=16):

@@ -1,0 +1,297 @@
+"""f1 (training batches) without a GPU: the new entry group is declared, bound, exported, registered and refuses host tensors; the reference of the GPU
+suite (tests/aug_ref.py) is itself checked -- pixels against plain array operations, the minimum-area rectangle against a brute-force angle scan, the
+label path against the pixel path (a painted label must land where its warped box says), with six planted mistakes each caught --; `sample_params`;
+and no committed GPU label case sits within rounding of a discrete decision."""
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+import aug_ref as R
+from conftest import ROOT
+
+ENTRIES = ("obb_aug_tiles", "obb_aug_labels")
+
+
+@pytest.fixture(scope="module")
+def A():
+    import __graft_entry__ as g
+    g._load_build_module().build()
+    import oriented_object_detection_amd  # noqa: F401
+    from oriented_object_detection_amd import augment
+    return augment
+
+
+# ---------------------------------------------------------------- the C ABI and its bindings
+def test_entries_declared_bound_exported_registered(A):
+    import torch
+    from oriented_object_detection_amd import _lib, ops
+    hdr = open(os.path.join(ROOT, "include", "obbhip.h")).read()
+    for name in ENTRIES:
+        assert re.search(r"\bint\s+%s\s*\(" % name, hdr), name
+        assert name in _lib.SIGNATURES and hasattr(_lib.lib(), name)
+        assert len(_lib.SIGNATURES[name]) == len(re.search(r"\bint\s+%s\s*\(([^;]*)\);" % name, hdr).group(1).split(","))
+    assert int(re.search(r"#define\s+OBB_AUG_REC_BYTES\s+(\d+)", hdr).group(1)) == _lib.AUG_REC_BYTES == A.REC.itemsize
+    for flag, val in (("MOSAIC", A.MOSAIC), ("FLIPLR", A.FLIPLR), ("FLIPUD", A.FLIPUD), ("HSV", A.HSV)):
+        assert int(re.search(r"#define\s+OBB_AUG_%s\s+(\d+)u" % flag, hdr).group(1)) == val
+    offs = {k: A.REC.fields[k][1] for k in A.REC.names}
+    assert offs == {"inv": 0, "fwd": 48, "scale": 96, "xc": 104, "yc": 108, "src": 112, "flags": 128, "reserved": 132, "lut": 136}
+    assert hasattr(torch.ops.obbhip, "aug_tiles") and hasattr(torch.ops.obbhip, "aug_labels")
+    assert callable(ops.aug_tiles) and callable(ops.aug_labels)
+    assert os.path.exists(os.path.join(ROOT, "oriented-object-detection_amd", "csrc", "augment.hip"))
+
+
+def test_no_cpu_path(A):
+    import torch
+    from oriented_object_detection_amd import ops
+    table = torch.zeros((1, A.REC.itemsize), dtype=torch.uint8)
+    with pytest.raises(ValueError, match="no CPU path"):
+        ops.aug_tiles(torch.zeros((2, 8, 8, 3), dtype=torch.uint8), table)
+    with pytest.raises(ValueError, match="no CPU path"):
+        ops.aug_labels(torch.zeros((2, 3, 9), dtype=torch.float64), torch.zeros(2, dtype=torch.int32), table, 8, 4)
+    with pytest.raises(ValueError, match="no CPU path"):
+        A.TrainBatcher(torch.zeros((2, 8, 8, 3), dtype=torch.uint8), torch.zeros((2, 3, 9), dtype=torch.float64), torch.zeros(2, dtype=torch.int32))
+
+
+# ---------------------------------------------------------------- reference sanity: pixels
+def _rec(A, M, s, **kw):
+    t = np.zeros(1, A.REC)
+    A.make_record(t[0], M, kw.pop("scale", 1.0), s, **kw)
+    return t
+
+
+@pytest.mark.parametrize("C", [3, 4])
+def test_reference_pixels_against_array_operations(A, C):
+    s = 24
+    pool = R.random_pool(7, s, C, 3)
+    assert np.array_equal(R.tiles_ref(pool, _rec(A, np.eye(3), s, src=(4, 0, 0, 0)))[0], pool[4])
+    T = np.eye(3)
+    T[0, 2], T[1, 2] = 5, -3  # output (x, y) shows input (x - 5, y + 3)
+    exp = np.full_like(pool[2], R.BORDER)
+    exp[:s - 3, 5:] = pool[2][3:, :s - 5]
+    assert np.array_equal(R.tiles_ref(pool, _rec(A, T, s, src=(2, 0, 0, 0)))[0], exp)
+    assert np.array_equal(R.tiles_ref(pool, _rec(A, np.eye(3), s, src=(1, 0, 0, 0), fliplr=True))[0], np.fliplr(pool[1]))
+    assert np.array_equal(R.tiles_ref(pool, _rec(A, np.eye(3), s, src=(1, 0, 0, 0), flipud=True))[0], np.flipud(pool[1]))
+    assert np.array_equal(R.tiles_ref(pool, _rec(A, np.eye(3), s, src=(1, 0, 0, 0)), swap_rb=True)[0][..., :3], pool[1][..., 2::-1])
+    # the mosaic with the identity map and the centre at (s, s): quadrant q of the canvas is tile src[q]
+    src = (3, 0, 6, 1)
+    cv = R.canvas_of(pool, _rec(A, np.eye(3), s, mosaic=True, centre=(s, s), src=src)[0])
+    assert cv.shape == (2 * s, 2 * s, C)
+    for q in range(4):
+        assert np.array_equal(cv[(q >> 1) * s:(q >> 1) * s + s, (q & 1) * s:(q & 1) * s + s], pool[src[q]])
+        Tq = np.eye(3)
+        Tq[0, 2], Tq[1, 2] = -(q & 1) * s, -(q >> 1) * s
+        assert np.array_equal(R.tiles_ref(pool, _rec(A, Tq, s, mosaic=True, centre=(s, s), src=src))[0], pool[src[q]])
+    # an off-centre mosaic: every quadrant shows its tile's corner that touches the centre, the rest of the canvas is border
+    xc, yc = s // 2 + 3, 3 * s // 2 - 2
+    cv = R.canvas_of(pool, _rec(A, np.eye(3), s, mosaic=True, centre=(xc, yc), src=src)[0])
+    assert np.array_equal(cv[yc - s:yc, :xc], pool[3][:, s - xc:]) and np.array_equal(cv[yc:, xc:xc + s], pool[1][:2 * s - yc])
+    assert (cv[:yc - s] == R.BORDER).all() and (cv[:, xc + s:] == R.BORDER).all()
+
+
+def test_reference_hsv_round_trip_and_extremes(A):
+    """unit gains: the integer BGR -> HSV -> fp32 BGR chain returns greys, primaries, 0 and 255 exactly and everything else within the quantisation of
+    H (180 steps) and S; the table forms of sdiv / hdiv equal the closed-form quotients of the kernel"""
+    i = np.arange(1, 256)
+    assert np.array_equal(R.SDIV[1:], (2088960 + i) // (2 * i)) and np.array_equal(R.HDIV[1:], (245760 + i) // (2 * i)) and R.SDIV[0] == 0 == R.HDIV[0]
+    g = np.arange(256, dtype=np.uint8)
+    for b, gg, r in ((g, g, g), (g * 0 + 255, g * 0, g * 0), (g * 0, g * 0 + 255, g * 0), (g * 0, g * 0, g * 0 + 255), (g * 0 + 255, g * 0 + 255, g * 0)):
+        out = R.hsv2bgr(*R.bgr2hsv(b, gg, r))
+        assert all(np.array_equal(o, e) for o, e in zip(out, (b, gg, r)))
+    rng = np.random.RandomState(0)
+    b, gg, r = (rng.randint(0, 256, 5000).astype(np.uint8) for _ in range(3))
+    h, sa, v = R.bgr2hsv(b, gg, r)
+    assert h.min() >= 0 and h.max() <= 179 and sa.max() <= 255 and np.array_equal(v, np.maximum(b, np.maximum(gg, r)))
+    out = R.hsv2bgr(h, sa, v)
+    assert max(int(np.abs(o.astype(int) - e.astype(int)).max()) for o, e in zip(out, (b, gg, r))) <= 6
+    lut = A.hsv_luts((1.015, 1.7, 0.6))
+    assert lut.dtype == np.uint8 and lut[:256].max() <= 179 and lut[256 + 200] == 255 and lut[512 + 255] == 153 and lut[100] == int(100 * 1.015)
+
+
+# ---------------------------------------------------------------- reference sanity: labels
+def _scan_area(P, step_deg=0.01):
+    a = np.deg2rad(np.arange(0.0, 90.0, step_deg))
+    c, s_ = np.cos(a)[:, None], np.sin(a)[:, None]
+    pu, pn = P[None, :, 0] * c + P[None, :, 1] * s_, P[None, :, 1] * c - P[None, :, 0] * s_
+    return ((pu.max(1) - pu.min(1)) * (pn.max(1) - pn.min(1))).min()
+
+
+def test_min_area_rect_against_brute_force():
+    rng = np.random.RandomState(0)
+    done = 0
+    while done < 2000:
+        P = np.array(R.hull(rng.uniform(0, 100, (4, 2))))
+        if len(P) < 4:
+            continue
+        done += 1
+        x, y, w, h, t = R.min_area_rect(P)
+        assert 0.0 <= t < math.pi / 2
+        assert w * h <= _scan_area(P) * (1 + R.TIE)  # (the tie slack lets a later, smaller edge within 1e-7 go)
+        c, s_ = math.cos(t), math.sin(t)
+        du, dn = (P[:, 0] - x) * c + (P[:, 1] - y) * s_, (P[:, 1] - y) * c - (P[:, 0] - x) * s_
+        assert np.abs(du).max() <= w / 2 + 1e-9 and np.abs(dn).max() <= h / 2 + 1e-9  # contains every vertex
+        assert abs(np.abs(du).max() - w / 2) <= 1e-9 and abs(np.abs(dn).max() - h / 2) <= 1e-9  # and is tight
+
+
+def test_rectangles_round_trip():
+    rng = np.random.RandomState(1)
+    for _ in range(500):
+        box = (rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(2, 80), rng.uniform(2, 80), rng.uniform(0.01, math.pi / 2 - 0.01))
+        got = R.min_area_rect(R.hull(R.xywhr_corners(box)))
+        assert np.allclose(got, box, rtol=0, atol=1e-9), (box, got)
+    # outside [0, pi/2) the same rectangle comes back in the convention: (w, h, theta) <-> (h, w, theta - pi/2)
+    got = R.min_area_rect(R.hull(R.xywhr_corners((5, 6, 30, 10, math.pi / 2 + 0.3))))
+    assert np.allclose(got, (5, 6, 10, 30, 0.3), atol=1e-9)
+
+
+def _painted_case(A, s, lr, ud, mosaic, q, seed):
+    """one label painted white on black into its tile, warped by the pixel reference: -> (mask of the bright output pixels, the label reference's inputs)"""
+    rng = np.random.RandomState(seed)
+    pool = np.zeros((4, s, s, 3), np.uint8)
+    row = R.rect_row(3, rng.uniform(0.3 * s, 0.7 * s), rng.uniform(0.3 * s, 0.7 * s), 0.42 * s, 0.2 * s, rng.uniform(0.2, 1.3), s)
+    corners = (row[1:].reshape(4, 2) * s)
+    yy, xx = np.mgrid[0:s, 0:s] + 0.0
+    inside = np.ones((s, s), bool)
+    for i in range(4):  # pixel centres (x, y) inside the convex quad: pixel i is the sample at coordinate i
+        a, b = corners[i], corners[(i + 1) % 4]
+        inside &= ((b[0] - a[0]) * (yy - a[1]) - (b[1] - a[1]) * (xx - a[0])) * np.sign(R._cross(corners[0], corners[1], corners[2])) >= 0
+    src = [0, 0, 0, 0]
+    src[q] = 1
+    pool[1][inside] = 255
+    S = 2 * s if mosaic else s
+    sc = 0.8
+    M = A.affine(S, s, 17.0, sc, 0.5, 0.5)
+    # bring the painted quadrant into view: its tile's centre goes to the output's centre
+    xc, yc = (s - 5, s + 7) if mosaic else (0, 0)
+    pad = np.array([(xc if q & 1 else xc - s), (yc if q & 2 else yc - s)]) if mosaic else np.zeros(2)
+    M = A.affine(S, s, 17.0, sc, 0.5, 0.5)
+    ctr = M[:2, :2] @ (pad + s / 2) + M[:2, 2]
+    M[:2, 2] += s / 2 - ctr
+    table = _rec(A, M, s, scale=sc, mosaic=mosaic, centre=(xc, yc), src=src if mosaic else (1, 0, 0, 0), fliplr=lr, flipud=ud)
+    lab, cnt = np.zeros((4, 1, 9)), np.array([0, 1, 0, 0], np.int32)
+    lab[1, 0] = row
+    img = R.tiles_ref(pool, table)[0][..., 0]
+    return img, lab, cnt, table
+
+
+def _label_matches_paint(A, bug, s=96):
+    """the label path against the pixel path: every painted label's box must cover the bright pixels it was warped to (area and centroid within a
+    pixel-quantisation bound).  -> number of mismatching cases"""
+    miss = 0
+    for k, (lr, ud, mosaic, q) in enumerate([(False, False, False, 0), (True, False, False, 0), (False, True, True, 0), (True, True, True, 1), (False, False, True, 2),
+                                             (True, False, True, 3)]):
+        img, lab, cnt, table = _painted_case(A, s, lr, ud, mosaic, q, k)
+        rows = R.labels_ref(lab, cnt, table, s, 4, bug=bug)[4]
+        bright = img > 127
+        if len(rows) != 1 or bright.sum() < 50:
+            miss += 1
+            continue
+        _, _, x, y, w, h, t = rows[0]
+        ys, xs = np.nonzero(bright)
+        # (a flipped image is mirrored about (s - 1) / 2 and its labels about s / 2, as np.fliplr and `w - x` do: one pixel apart)
+        ok = abs(xs.mean() - x) < 1.0 + lr and abs(ys.mean() - y) < 1.0 + ud and abs(bright.sum() - w * h) < 0.08 * w * h + 2 * (w + h) * 0.5
+        c, s_ = math.cos(t), math.sin(t)
+        du, dn = (xs - x) * c + (ys - y) * s_, (ys - y) * c - (xs - x) * s_
+        ok = ok and np.abs(du).max() <= w / 2 + 2.0 and np.abs(dn).max() <= h / 2 + 2.0  # w runs along (cos, sin): a swap without the quarter turn fails here
+        miss += not ok
+    return miss
+
+
+def _filter_case(A, bug):
+    """box_candidates: a label the warp leaves 0.5 % of is dropped and a whole one is kept -> True when the reference does exactly that"""
+    s = 64
+    lab, cnt = np.zeros((1, 2, 9)), np.array([2], np.int32)
+    lab[0, 0] = np.concatenate([[1], np.array([0, 10, 60, 10, 60, 50, 0, 50]) / s])  # 60 x 40, pushed out so that 3 x 4 px stay: 12 / 2400 = 0.5 %
+    lab[0, 1] = np.concatenate([[2], np.array([4, 52, 20, 52, 20, 60, 4, 60]) / s])
+    T = np.eye(3)
+    T[0, 2], T[1, 2] = -57, -46
+    t = _rec(A, T, s)
+    T2 = np.eye(3)
+    rows_out = R.labels_ref(lab, cnt, t, s, 4, bug=bug)[4]
+    rows_in = R.labels_ref(lab, cnt, _rec(A, T2, s), s, 4, bug=bug)[4]
+    return [r[1] for r in rows_out] == [] and [r[1] for r in rows_in] == [1, 2]
+
+
+def _canvas_clip_case(A, bug):
+    """a label that sticks out of the mosaic canvas (its tile hangs over the canvas edge) is cut at the edge: at scale 0.5 and a translation of
+    0.6 s the canvas edge lies 0.1 s inside the output, and the box must end where the painted pixels end"""
+    s = 64
+    pool = np.zeros((2, s, s, 3), np.uint8)
+    pool[1, 20:44, 0:40] = 255  # in quadrant 0 with xc = 40: tile columns [0, 24) fall left of the canvas
+    lab, cnt = np.zeros((2, 1, 9)), np.array([0, 1], np.int32)
+    lab[1, 0] = np.concatenate([[6], np.array([0, 20, 40, 20, 40, 44, 0, 44]) / s])
+    t = _rec(A, A.affine(2 * s, s, 0.0, 0.5, 0.6, 0.5), s, scale=0.5, mosaic=True, centre=(40, 70), src=(1, 0, 0, 0))
+    img = R.tiles_ref(pool, t)[0][..., 0] > 127
+    rows = R.labels_ref(lab, cnt, t, s, 4, bug=bug)[4]
+    if len(rows) != 1:
+        return False
+    _, _, x, y, w, h, th = rows[0]
+    ys, xs = np.nonzero(img)
+    return abs(xs.mean() - x) < 1.0 and abs(ys.mean() - y) < 1.0 and abs(img.sum() - w * h) < 0.25 * w * h
+
+
+def test_reference_labels_agree_with_reference_pixels(A):
+    assert _label_matches_paint(A, None) == 0
+    assert _filter_case(A, None)
+    assert _canvas_clip_case(A, None)
+
+
+@pytest.mark.parametrize("bug", R.BUGS)
+def test_planted_mistakes_are_caught(A, bug):
+    caught = _label_matches_paint(A, bug) > 0 or not _filter_case(A, bug) or not _canvas_clip_case(A, bug)
+    assert caught, bug
+
+
+# ---------------------------------------------------------------- sample_params
+def test_sample_params_ranges_seed_and_close_mosaic(A):
+    cfg = A.AugmentConfig()
+    assert (cfg.mosaic, cfg.translate, cfg.scale, cfg.degrees, cfg.hsv_h, cfg.hsv_s, cfg.hsv_v, cfg.fliplr, cfg.flipud) == (1.0, 0.1, 0.5, 0.0, 0.015, 0.7, 0.4, 0.5, 0.0)
+    s, N, B = 64, 9, 400
+    t = A.sample_params(cfg, B, N, s, np.random.RandomState(7), np.arange(B) % N)
+    assert t.dtype == A.REC and t.shape == (B,)
+    assert (t["flags"] & A.MOSAIC).all() and (t["flags"] & A.HSV).all() and not (t["flags"] & A.FLIPUD).any()
+    assert 0.4 < (t["flags"] & A.FLIPLR).astype(bool).mean() < 0.6
+    assert np.array_equal(t["src"][:, 0], np.arange(B) % N) and t["src"].min() >= 0 and t["src"].max() < N and len(np.unique(t["src"][:, 1:])) == N
+    for k in ("xc", "yc"):
+        assert t[k].min() >= s // 2 and t[k].max() < 3 * s // 2 and t[k].min() < s // 2 + 4 and t[k].max() > 3 * s // 2 - 5
+    assert t["scale"].min() >= 0.5 and t["scale"].max() <= 1.5 and t["scale"].min() < 0.55 and t["scale"].max() > 1.45
+    for r in t[:50]:
+        M = np.vstack([r["fwd"].reshape(2, 3), [0, 0, 1]])
+        assert np.allclose(M[:2, :2], r["scale"] * np.eye(2), atol=1e-12)  # degrees 0
+        assert np.allclose(np.vstack([r["inv"].reshape(2, 3), [0, 0, 1]]) @ M, np.eye(3), atol=1e-9)
+        centre = M @ [s, s, 1]  # the canvas centre lands at the translation: U(0.4, 0.6) s
+        assert 0.4 * s <= centre[0] <= 0.6 * s and 0.4 * s <= centre[1] <= 0.6 * s
+        lut = r["lut"]
+        assert lut[:256].max() <= 179 and lut[1] in (0, 1) and np.all(np.diff(lut[256:512].astype(int)) >= 0) and np.all(np.diff(lut[512:].astype(int)) >= 0)
+    # the LUTs of a record are RandomHSV's for some gains inside the ranges: 255 r_v clipped, 255 r_s clipped
+    assert t["lut"][:, 767].min() >= int(255 * 0.6) and (t["lut"][:, 511] >= int(255 * 0.3)).all()
+    again = A.sample_params(cfg, B, N, s, np.random.RandomState(7), np.arange(B) % N)
+    assert again.tobytes() == t.tobytes()
+    assert A.sample_params(cfg, B, N, s, np.random.RandomState(8), np.arange(B) % N).tobytes() != t.tobytes()
+    closed = A.sample_params(cfg.close_mosaic(True), 50, N, s, np.random.RandomState(7))
+    assert cfg.close_mosaic(True).mosaic == 0.0 and cfg.close_mosaic(False) is cfg and not (closed["flags"] & A.MOSAIC).any()
+    for r in closed[:10]:  # without mosaic the canvas is the tile: its centre (s/2, s/2) lands at the translation
+        centre = np.vstack([r["fwd"].reshape(2, 3), [0, 0, 1]]) @ [s / 2, s / 2, 1]
+        assert 0.4 * s <= centre[0] <= 0.6 * s
+    A.check_table(t, N, s)
+    with pytest.raises(ValueError):
+        A.check_table(t, N - 1, s)
+    with pytest.raises(ValueError):
+        A.sample_params(cfg, 2, N, s, np.random.RandomState(0), [0, N])
+    rot = A.sample_params(A.AugmentConfig(degrees=17.0, hsv_h=0, hsv_s=0, hsv_v=0), 20, N, s, np.random.RandomState(1))
+    assert not (rot["flags"] & A.HSV).any() and np.abs(rot["fwd"][:, 1]).max() > 0.01
+
+
+# ---------------------------------------------------------------- the committed GPU cases keep clear of every discrete decision
+def test_gpu_label_cases_have_margin(A):
+    seen = {}
+    for name, s, lab, cnt, table, n_cap in R.label_cases():
+        m = []
+        R.labels_ref(lab, cnt, table, s, n_cap, margins=m)
+        for kind, v in m:
+            assert v >= 1e-9, (name, kind, v)
+            seen[kind] = min(seen.get(kind, np.inf), v)
+    print({k: f"{v:.2e}" for k, v in seen.items()})
+    assert {"wh", "aspect", "area", "clip", "edge", "tie", "quadrant", "2px"} <= set(seen)
