@@ -567,6 +567,52 @@ int obb_aug_labels(obb_ctx *ctx, const double *pool_labels, const int32_t *pool_
                    double wh_thr, double ar_thr, double area_thr, int32_t n_cap, int32_t *gt_labels, float *gt_bboxes, uint8_t *mask_gt, int32_t *count,
                    obb_stream_t st);
 
+/* ------------------------------------------------------------------ validation of the net being trained */
+/* The `val` pass `model.train(...)` runs on the EMA model after every epoch (Train_OBB.py:792-841), Ultralytics 8.3.x restated from recall (the
+ * package is not installed: UNPINNED, like the schedule and the criterion above; pinned is the device against tests/val_ref.py in fp64).
+ *
+ * obb_fold_blob_f32: replaces `model.fuse()` (per layer: BatchNorm folded into its conv) + the host loop that lays the folded tensors out as a
+ * weight blob.  ONE launch turns the four flat fp32 buffers of the trainer's state -- w_flat (conv weights, parameter group 0), g_flat (BatchNorm
+ * gamma, group 1), b_flat (beta and the plain convs' biases, group 2), buffers (the running statistics); the live ones or the EMA's copies -- into
+ * the fp32 DATA SECTION of an "OBBW" blob: per record the OIHW weights, then the bias, records in table order, no padding.  `table` (device int64,
+ * table_words = OBB_FOLD_TABLE_HEAD + nrec * OBB_FOLD_TABLE_REC, written once by the host):
+ *     head   [0] magic "OBBFOLD1" (0x4f4242464f4c4431)  [1] nrec  [2] out_elems  [3..6] elements the records read up to in w_flat, g_flat, b_flat,
+ *            buffers (the caller holds buffers at least that long)  [7] 0
+ *     record [0] weight offset in w_flat  [1] gamma offset in g_flat  [2] beta / bias offset in b_flat  [3] running-mean offset and [4] running-
+ *            variance offset in buffers  [5] destination offset in out  [6] cout | (elements per output channel) << 32
+ *            [7] first workgroup | kind << 32; record i owns ceil(cout (per + 1) / 256) workgroups, first workgroups ascending from 0
+ * OBB_FOLD_BN: f = gamma / sqrt(var + eps), w' = w f, b' = beta - mean f, each operation rounded to fp32 on its own (correctly rounded IEEE division and square
+ * root, nothing contracted).  OBB_FOLD_PLAIN: weight and bias copied.  OBB_FOLD_QKV: OBB_FOLD_BN for the attention's qkv conv, whose rows the trainer
+ * holds as [q of all heads | k of all heads | v of all heads] (32, 32, 64 rows per head): output row c is read from that device row, so the
+ * blob is in checkpoint order ([q | k | v] per head).  The kernel compares the head with nrec and out_elems and every record with the head; on a
+ * mismatch nothing is stored.  No host read, no allocation, no synchronisation: capturable. */
+#define OBB_FOLD_TABLE_HEAD 8
+#define OBB_FOLD_TABLE_REC 8
+#define OBB_FOLD_BN 0
+#define OBB_FOLD_PLAIN 1
+#define OBB_FOLD_QKV 2
+int obb_fold_blob_f32(obb_ctx *ctx, const float *w_flat, const float *g_flat, const float *b_flat, const float *buffers, const int64_t *table,
+                      int64_t table_words, int32_t nrec, float eps, float *out, int64_t out_elems, obb_stream_t s);
+/* obb_val_match: replaces `OBBValidator._process_batch` = batch_probiou(gt, pred) + match_predictions.  det float [B][max_det][7] = (x, y, w, h,
+ * conf, cls, theta) and count int32 [B] as obb_decode_nms writes them (score order; rows at or past count[b] are ignored whatever they hold);
+ * gt_labels int32 [B][n_cap], gt_bboxes float [B][n_cap][5] = (x, y, w, h, theta), mask_gt uint8 [B][n_cap] (masked rows are ignored whatever
+ * they hold); thr DEVICE float [n_thr], ascending (the trainer's: float32(linspace(0.5, 0.95, 10))).  Per detection d: g(d) = the class-equal,
+ * unmasked ground truth with the largest ProbIoU (covariance form, eps 1e-7, fp32), ties to the lower index; d claims g(d) at threshold i iff
+ * that IoU >= thr[i]; of the detections claiming one ground truth at one threshold the lowest index is the true positive, the others are false
+ * positives (no fall-back to a second-best ground truth: the trainer's rule).  -> tp uint16 [B][max_det] (bit i = threshold i), best_iou float
+ * [B][max_det], best_gt int32 [B][max_det] (-1: none; rows at or past count[b]: 0, 0, -1).  A class outside [0, nc) or a non-finite box, in a
+ * detection or a ground truth, matches nothing and never forms an address.  One 256-lane workgroup per image.  Refused with nothing written:
+ * n_cap outside [1, OBB_VAL_MAX_GT], max_det < 1, n_thr outside [1, OBB_VAL_MAX_THR], nc < 1, a NULL buffer.  Enqueues only: capturable. */
+#define OBB_VAL_MAX_GT 512
+#define OBB_VAL_MAX_THR 16
+int obb_val_match(obb_ctx *ctx, const float *det, const int32_t *count, const int32_t *gt_labels, const float *gt_bboxes, const uint8_t *mask_gt,
+                  int32_t B, int32_t max_det, int32_t n_cap, int32_t nc, const float *thr, int32_t n_thr, uint16_t *tp, float *best_iou,
+                  int32_t *best_gt, obb_stream_t s);
+/* obb_get_option: reads back what obb_set_option set ("model_slot": the active slot), so that a component that loads a model of its own -- the
+ * validator's, next to whatever the application runs -- can put the context's slot and switches back as it found them.  Replaces nothing of the
+ * reference: Ultralytics' validator owns a deep copy of the model instead. */
+int obb_get_option(const obb_ctx *ctx, const char *key, int64_t *value);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,9 +111,15 @@ SIGNATURES = {
     "obb_ema_update": [_V, _V, _V, c_lp, C.c_int32, C.c_double, _V],
     "obb_aug_tiles": [_V, _V, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_int32, _V, _V],
     "obb_aug_labels": [_V, _V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _V, _V, _V, _V, _V],
+    "obb_fold_blob_f32": [_V, _V, _V, _V, _V, _V, C.c_int64, C.c_int32, C.c_float, _V, C.c_int64, _V],
+    "obb_val_match": [_V, _V, _V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, _V, _V],
+    "obb_get_option": [_V, C.c_char_p, c_lp],
 }
 _RESTYPE = {"obb_last_error": C.c_char_p}
 PACK_TABLE_HEAD, PACK_TABLE_REC = 4, 8  # OBB_PACK_TABLE_HEAD / OBB_PACK_TABLE_REC: int64 words of obb_conv_pack_plan's table
+FOLD_TABLE_HEAD, FOLD_TABLE_REC = 8, 8  # OBB_FOLD_TABLE_HEAD / OBB_FOLD_TABLE_REC: int64 words of obb_fold_blob_f32's table
+FOLD_MAGIC, FOLD_BN, FOLD_PLAIN, FOLD_QKV = 0x4f4242464f4c4431, 0, 1, 2  # the table's magic "OBBFOLD1" and the OBB_FOLD_* record kinds
+VAL_MAX_GT, VAL_MAX_THR = 512, 16  # OBB_VAL_MAX_GT / OBB_VAL_MAX_THR
 AUG_REC_BYTES = 904  # OBB_AUG_REC_BYTES: one record of the augmentation table (augment.REC is its numpy layout)
 
 

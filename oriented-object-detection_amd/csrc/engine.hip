@@ -275,6 +275,17 @@ __global__ void k_f32_slice_copy(const float *__restrict__ src, int64_t bs, int 
     dst[i] = blk > 0 ? src[b * bs + (int64_t)(c / blk) * npix_per_img * blk + pix * blk + c % blk] : src[b * bs + pix * cs + c];
 }
 
+// the boolean engine switch named `k` (obb_set_option / obb_get_option), or nullptr
+static bool *switch_of(obb_ctx *ctx, const std::string &k) {
+    struct { const char *key; bool *flag; } sw[] = {
+        {"tail", &ctx->opt.tail}, {"tail16", &ctx->opt.tail16}, {"bneck", &ctx->opt.bneck}, {"bneck_cv2", &ctx->opt.bneck_cv2},
+        {"c3kimg", &ctx->opt.c3kimg}, {"dwpw", &ctx->opt.dwpw}, {"upfold", &ctx->opt.upfold}, {"stem", &ctx->opt.stem}, {"front", &ctx->opt.front}, {"pair", &ctx->opt.pair},
+        {"hmerge", &ctx->opt.hmerge}, {"sppf_fuse", &ctx->opt.sppf_fuse}, {"attn_mfma", &ctx->opt.attn_mfma}, {"xtile", &ctx->opt.xtile}, {"nitile", &ctx->opt.nitile}, {"nc2", &ctx->opt.nc2}, {"blk32", &ctx->opt.blk32}, {"c3k2f", &ctx->opt.c3k2f}, {"pw32", &ctx->opt.pw32}, {"upacc", &ctx->opt.upacc}, {"graph", &ctx->opt.graph}};
+    for (auto &e : sw)
+        if (k == e.key) return e.flag;
+    return nullptr;
+}
+
 }  // namespace obb
 
 using namespace obb;
@@ -327,18 +338,12 @@ int obb_set_option(obb_ctx *ctx, const char *key, int64_t value) {
         ctx->opt_f32 = (value == 32);
         return OBB_OK;
     }
-    {   // engine switches: 1 = the fused form (default), 0 = its separate launches; all apply to the next obb_model_load, except
-        // "graph", "fwd_split" and "microbatch", which steer how obb_forward issues its launches from the next call on
-        struct { const char *key; bool *flag; } sw[] = {
-            {"tail", &ctx->opt.tail}, {"tail16", &ctx->opt.tail16}, {"bneck", &ctx->opt.bneck}, {"bneck_cv2", &ctx->opt.bneck_cv2},
-            {"c3kimg", &ctx->opt.c3kimg}, {"dwpw", &ctx->opt.dwpw}, {"upfold", &ctx->opt.upfold}, {"stem", &ctx->opt.stem}, {"front", &ctx->opt.front}, {"pair", &ctx->opt.pair},
-            {"hmerge", &ctx->opt.hmerge}, {"sppf_fuse", &ctx->opt.sppf_fuse}, {"attn_mfma", &ctx->opt.attn_mfma}, {"xtile", &ctx->opt.xtile}, {"nitile", &ctx->opt.nitile}, {"nc2", &ctx->opt.nc2}, {"blk32", &ctx->opt.blk32}, {"c3k2f", &ctx->opt.c3k2f}, {"pw32", &ctx->opt.pw32}, {"upacc", &ctx->opt.upacc}, {"graph", &ctx->opt.graph}};
-        for (auto &e : sw)
-            if (k == e.key) { *e.flag = value != 0; return OBB_OK; }
-        if (k == "fuse") return OBB_OK;  // (retired: the LDS-resident layer chains were slower than layer-by-layer on MI355X and are gone)
-        if (k == "fwd_split") { OBB_REQUIRE(ctx, value >= 0 && value <= 4, "obb_set_option: fwd_split must be 0 (auto) .. 4"); ctx->opt.fwd_split = (int)value; return OBB_OK; }
-        if (k == "microbatch") { OBB_REQUIRE(ctx, value >= 1 && value <= 1024, "obb_set_option: microbatch must be 1..1024"); ctx->opt.microbatch = (int)value; return OBB_OK; }
-    }
+    // engine switches: 1 = the fused form (default), 0 = its separate launches; all apply to the next obb_model_load, except
+    // "graph", "fwd_split" and "microbatch", which steer how obb_forward issues its launches from the next call on
+    if (bool *flag = switch_of(ctx, k)) { *flag = value != 0; return OBB_OK; }
+    if (k == "fuse") return OBB_OK;  // (retired: the LDS-resident layer chains were slower than layer-by-layer on MI355X and are gone)
+    if (k == "fwd_split") { OBB_REQUIRE(ctx, value >= 0 && value <= 4, "obb_set_option: fwd_split must be 0 (auto) .. 4"); ctx->opt.fwd_split = (int)value; return OBB_OK; }
+    if (k == "microbatch") { OBB_REQUIRE(ctx, value >= 1 && value <= 1024, "obb_set_option: microbatch must be 1..1024"); ctx->opt.microbatch = (int)value; return OBB_OK; }
     if (k == "model_slot") {  // several models per context (dual-scale 128 + 416): select which one load/forward address
         OBB_REQUIRE(ctx, value >= 0 && value < 64, "obb_set_option: model_slot must be in [0, 64)");
         if ((int)value != ctx->slot) {
@@ -349,6 +354,19 @@ int obb_set_option(obb_ctx *ctx, const char *key, int64_t value) {
         return OBB_OK;
     }
     return set_error(ctx, OBB_ERR_INVALID, "obb_set_option: unknown key '%s'", key);
+}
+
+int obb_get_option(const obb_ctx *cctx, const char *key, int64_t *value) {
+    obb_ctx *ctx = const_cast<obb_ctx *>(cctx);
+    OBB_REQUIRE(ctx, ctx && key && value, "obb_get_option: bad arguments");
+    std::string k(key);
+    if (k == "precision") { *value = ctx->opt_f32 ? 32 : (ctx->opt_f16 ? 16 : 1016); return OBB_OK; }
+    if (k == "model_slot") { *value = ctx->slot; return OBB_OK; }
+    if (k == "fwd_split") { *value = ctx->opt.fwd_split; return OBB_OK; }
+    if (k == "microbatch") { *value = ctx->opt.microbatch; return OBB_OK; }
+    if (k == "fuse") { *value = 0; return OBB_OK; }
+    if (const bool *flag = switch_of(ctx, k)) { *value = *flag ? 1 : 0; return OBB_OK; }
+    return set_error(ctx, OBB_ERR_INVALID, "obb_get_option: unknown key '%s'", key);
 }
 
 int obb_model_info(const obb_ctx *cctx, int32_t h, int32_t w, int32_t *nc, int32_t *ch, int32_t *anchors, int32_t *nconv) {

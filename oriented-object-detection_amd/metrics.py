@@ -112,6 +112,57 @@ def evaluate_map(dets_source, gt_source, iou_list=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# The TRAINER's AP (the `val` pass behind every epoch of `model.train(...)`, Train_OBB.py:792-841): Ultralytics 8.3.x `ap_per_class` / `compute_ap`,
+# restated from recall (the package is not installed: UNPINNED, like train.Schedule).  Another instrument than the one above: ProbIoU matches at ten
+# thresholds (train.Validator / ops.val_match produce them on the device) and a 101-point interpolated AP, where Detect_OBB.py's uses polygon IoU,
+# one threshold and the all-point AP.  Both stay.
+
+def compute_ap(recall, precision):
+    """AP of one precision / recall curve (numpy float64, in confidence order): sentinels mrec = [0, r, 1], mpre = [1, p, 0], the precision envelope
+    (running maximum from the right), then the trapezoid rule over interp(linspace(0, 1, 101), mrec, mpre) -- COCO's 101 points."""
+    mrec = np.concatenate(([0.0], np.asarray(recall, np.float64), [1.0]))
+    mpre = np.concatenate(([1.0], np.asarray(precision, np.float64), [0.0]))
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    x = np.linspace(0.0, 1.0, 101)
+    y = np.interp(x, mrec, mpre)
+    return float(np.sum((y[1:] + y[:-1]) * 0.5 * (x[1:] - x[:-1])))
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls, nc):
+    """tp bool [n, T] (true positive of detection d at threshold t: `ops.val_match`'s bits), conf [n], pred_cls [n], target_cls [m] (the class of
+    every ground truth), classes in [0, nc) -> {"ap": float64 [classes present in the targets, T], "classes": those classes, "map50": mean of
+    column 0, "map": mean of all, "fitness": 0.1 map50 + 0.9 map}.  Detections are put in descending confidence by a STABLE sort (equal
+    confidences keep their input order); per class present in the targets: cumulative TP and FP per threshold, recall = tpc / (n_gt + 1e-16),
+    precision = tpc / (tpc + fpc), `compute_ap`.  A class with targets and no detections scores 0; detections of a class without targets
+    count nowhere; no targets at all: every figure 0.  A perfect detector scores 0.995, not 1: the envelope's last sentinel pulls the 101st
+    point to 0."""
+    tp = np.asarray(tp).astype(bool)
+    if tp.ndim != 2:
+        raise ValueError("ap_per_class: tp must be [n, thresholds]")
+    conf, pred_cls, target_cls = np.asarray(conf, np.float64).reshape(-1), np.asarray(pred_cls).reshape(-1), np.asarray(target_cls).reshape(-1)
+    if len(conf) != len(tp) or len(pred_cls) != len(tp):
+        raise ValueError("ap_per_class: tp, conf and pred_cls differ in length")
+    if len(target_cls) and (target_cls.min() < 0 or target_cls.max() >= nc):
+        raise ValueError(f"ap_per_class: a target class outside [0, {nc})")
+    order = np.argsort(-conf, kind="stable")
+    tp, pred_cls = tp[order], pred_cls[order]
+    classes, n_gt = np.unique(target_cls.astype(np.int64), return_counts=True)
+    ap = np.zeros((len(classes), tp.shape[1]))
+    for ci, c in enumerate(classes):
+        sel = pred_cls == c
+        if not sel.any():
+            continue
+        tpc = tp[sel].cumsum(0).astype(np.float64)
+        fpc = (~tp[sel]).cumsum(0).astype(np.float64)
+        recall, precision = tpc / (n_gt[ci] + 1e-16), tpc / (tpc + fpc)
+        for j in range(tp.shape[1]):
+            ap[ci, j] = compute_ap(recall[:, j], precision[:, j])
+    map50 = float(ap[:, 0].mean()) if ap.size else 0.0
+    mean = float(ap.mean()) if ap.size else 0.0
+    return {"ap": ap, "classes": classes, "map50": map50, "map": mean, "fitness": 0.1 * map50 + 0.9 * mean}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # Fusion-evaluation metrics beyond mAP (SURVEY.md section 8 row f2).  dets: 11-tuples (x1..y4, cls, conf, angle) in pixels;
 # gts: [{"cls": int, "pts": 8 floats}].  All geometry runs on the GPU (one matrix launch per image); the greedy matching loops are
 # the reference's own sequential control flow over those matrices.

@@ -84,6 +84,8 @@ class YOLO:
             blob = weights.to_blob()
         elif isinstance(weights, (bytes, bytearray)):
             blob = bytes(weights)
+        elif isinstance(weights, memoryview):
+            blob = weights  # (read once, by obb_model_load, which keeps its own copy)
         else:
             if not os.path.exists(weights):
                 raise FileNotFoundError(f"{weights}: weight blob not found (no download is ever attempted)")
@@ -95,6 +97,8 @@ class YOLO:
         self.imgsz = int(imgsz)
         self.names = names or {}
         self._load()
+        if isinstance(blob, memoryview):  # (as in reload(): the library keeps its own copy; a buffer the caller rewrites must not pose as this model's weights)
+            self._blob = None
 
     _next_slot = {}   # per device: every YOLO object owns one model slot of the device's libobbhip context ...
     _free_slots = {}  # ... and hands it back in close() / __del__ (the library keeps 64 slots per context)
@@ -111,6 +115,21 @@ class YOLO:
             ops.select_model(self._slot, self.device)
             ops.model_load(self._blob, self.device, self.precision, **self.engine_options)
             info = ops.model_info(self.imgsz, self.imgsz, self.device)
+        self.nc, self.ch = info["nc"], info["ch"]
+
+    def reload(self, blob):
+        """New weights (an "OBBW" blob: bytes, or a buffer such as `train.FoldPlan.run()` returns) into this object's own slot; the plans, slabs and
+        graphs of the old weights are released first (obb_model_load replaces the active model, but a slot that was parked and selected again is
+        still held by the context's slot table until the next switch: obb_model_unload drops both).  Precision and engine options as constructed.
+        The slot stays the context's active one, as after any call of this object."""
+        if self._slot is None:
+            raise RuntimeError("YOLO: this model has been closed")
+        with torch.cuda.device(self.device):
+            ops.select_model(self._slot, self.device)
+            ops.model_unload(self._slot, self.device)
+            ops.model_load(blob, self.device, self.precision, **self.engine_options)
+            info = ops.model_info(self.imgsz, self.imgsz, self.device)
+        self._blob = None  # (the library keeps its own copy; a buffer the caller rewrites must not pose as this model's weights)
         self.nc, self.ch = info["nc"], info["ch"]
 
     def _ensure_active(self):

@@ -10,6 +10,7 @@ The plain functions below (`forward`, `decode_nms`, `merge_detections`, ...) are
 uses: they allocate the outputs and call `torch.ops.obbhip.*`.
 """
 import ctypes as C
+import contextlib
 import ctypes as _ct  # (for functions whose own argument is named C)
 import os
 from typing import List, Optional
@@ -456,6 +457,18 @@ def _aug_labels(pool_labels: T, pool_counts: T, table: T, s: int, wh_thr: float,
     N, Lmax, _ = pool_labels.shape
     _call("obb_aug_labels", ctx(pool_labels.device), _p(pool_labels), _p(pool_counts), N, Lmax, _p(table), table.shape[0], int(s), float(wh_thr), float(ar_thr),
           float(area_thr), gt_labels.shape[1], _p(gt_labels), _p(gt_bboxes), _p(mask_gt), _p(count), _stream())
+
+
+@_op("fold_blob", ("out",))
+def _fold_blob(w_flat: T, g_flat: T, b_flat: T, buffers: T, table: T, nrec: int, eps: float, out: T) -> None:
+    _call("obb_fold_blob_f32", ctx(w_flat.device), _p(w_flat), _p(g_flat), _p(b_flat), _p(buffers), _p(table), table.numel(), int(nrec), float(eps), _p(out),
+          out.numel(), _stream())
+
+
+@_op("val_match", ("tp", "best_iou", "best_gt"))
+def _val_match(det: T, count: T, gt_labels: T, gt_bboxes: T, mask_gt: T, nc: int, thr: T, tp: T, best_iou: T, best_gt: T) -> None:
+    _call("obb_val_match", ctx(det.device), _p(det), _p(count), _p(gt_labels), _p(gt_bboxes), _p(mask_gt), det.shape[0], det.shape[1], gt_labels.shape[1],
+          int(nc), _p(thr), thr.numel(), _p(tp), _p(best_iou), _p(best_gt), _stream())
 
 
 @_op("debug_activation", ("out",))
@@ -1227,6 +1240,28 @@ def select_model(slot, device=None):
     _call("obb_set_option", ctx(device), b"model_slot", int(slot))
 
 
+def get_option(key, device=None):
+    """What obb_set_option last set for `key` ("model_slot": the active slot; "precision": 16 / 1016 / 32; a switch of MODEL_OPTIONS: 0 / 1)."""
+    v = C.c_int64(0)
+    _call("obb_get_option", ctx(device), key.encode(), C.byref(v))
+    return v.value
+
+
+@contextlib.contextmanager
+def engine_state(device=None):
+    """Inside: load, select and run models freely; on exit the context's active model slot and every option are as they were on entry (a
+    component with a model of its own, like train.Validator, next to the application's models)."""
+    keys = ("precision",) + MODEL_OPTIONS[1:]  # what `select_model` / `model_load` set; the other options nobody inside touches
+    c = ctx(device)
+    slot, saved = get_option("model_slot", device), {k: get_option(k, device) for k in keys}
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            _call("obb_set_option", c, k.encode(), v)
+        _call("obb_set_option", c, b"model_slot", slot)
+
+
 def model_load(blob, device=None, precision="f16", fuse=False, tail=True, **options):
     """blob: bytes of an "OBBW" weight blob (host), loaded into the active model slot.  precision: "f16" / "bf16" = 16-bit storage with
     fp32 accumulation, "f32" = fp32 arithmetic end to end (what the reference computes; one kernel per layer).
@@ -1245,8 +1280,9 @@ def model_load(blob, device=None, precision="f16", fuse=False, tail=True, **opti
                 raise
     if options:
         raise TypeError(f"model_load: unknown options {sorted(options)}")
-    buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-    _call("obb_model_load", c, buf, len(blob))
+    mv = memoryview(blob)
+    buf = (C.c_char * mv.nbytes).from_buffer(mv) if not mv.readonly else (C.c_char * mv.nbytes).from_buffer_copy(mv)  # (the library copies it anyway)
+    _call("obb_model_load", c, buf, mv.nbytes)
 
 
 def model_unload(slot, device=None):
@@ -1461,6 +1497,100 @@ def aug_labels(pool_labels, pool_counts, table, s, n_cap, wh_thr=2.0, ar_thr=100
         raise ValueError("aug_labels: output buffers must be [B, n_cap], [B, n_cap, 5], [B, n_cap], [B]")
     _O.aug_labels(pl, pc, t, int(s), float(wh_thr), float(ar_thr), float(area_thr), gl, gb, mk, cnt)
     return gl, gb, mk, cnt
+
+
+class FoldTable:
+    """What `fold_blob_plan` returns: `table` (int64 device tensor: the head and records of csrc/foldblob.hip's k_fold_blob), `host` (its numpy
+    copy), `nrec`, `out_elems` (fp32 elements of the blob's data section) and `need` (elements read up to in w_flat, g_flat, b_flat, buffers)."""
+
+    def __init__(self, table, host, nrec, out_elems, need):
+        self.table, self.host, self.nrec, self.out_elems, self.need = table, host, nrec, out_elems, need
+
+
+def fold_blob_table(records):
+    """The host table of `fold_blob_f32` (include/obbhip.h), numpy int64: records = [(kind, w_off, g_off, b_off, mean_off, var_off, cout, per)] in
+    blob order, kind one of _lib.FOLD_BN / FOLD_PLAIN / FOLD_QKV, per = the weight elements per output channel; the destinations are dense: record
+    i's cout * per weights, then its cout biases, behind record i - 1's."""
+    import numpy as np
+    recs = [tuple(int(v) for v in r) for r in records]
+    if not recs or any(len(r) != 8 for r in recs):
+        raise ValueError("fold_blob_table: records is a non-empty list of (kind, w_off, g_off, b_off, mean_off, var_off, cout, per)")
+    H, R = _lib.FOLD_TABLE_HEAD, _lib.FOLD_TABLE_REC
+    tab = np.zeros(H + len(recs) * R, np.int64)
+    dst, wg, need = 0, 0, [0, 0, 0, 0]
+    for i, (kind, w_off, g_off, b_off, m_off, v_off, cout, per) in enumerate(recs):
+        if kind not in (_lib.FOLD_BN, _lib.FOLD_PLAIN, _lib.FOLD_QKV) or cout < 1 or per < 1 or (kind == _lib.FOLD_QKV and cout % 128):
+            raise ValueError(f"fold_blob_table: record {i}: kind {kind}, cout {cout}, {per} elements per channel")
+        plain = kind == _lib.FOLD_PLAIN
+        if min(w_off, b_off) < 0 or (not plain and min(g_off, m_off, v_off) < 0):
+            raise ValueError(f"fold_blob_table: record {i}: negative offset")
+        tab[H + i * R:H + (i + 1) * R] = (w_off, 0 if plain else g_off, b_off, 0 if plain else m_off, 0 if plain else v_off, dst, cout | (per << 32),
+                                          wg | (kind << 32))
+        need[0], need[2] = max(need[0], w_off + cout * per), max(need[2], b_off + cout)
+        if not plain:
+            need[1], need[3] = max(need[1], g_off + cout), max(need[3], m_off + cout, v_off + cout)
+        n = cout * (per + 1)
+        dst, wg = dst + n, wg + (n + 255) // 256
+    if wg >= 1 << 31:
+        raise ValueError("fold_blob_table: too many workgroups for one launch")
+    tab[:H] = (_lib.FOLD_MAGIC, len(recs), dst, *need, 0)
+    return tab
+
+
+def fold_blob_plan(device, records):
+    """`fold_blob_table` on the device -> a `FoldTable`.  Once per net; synchronises (the table is copied to the device)."""
+    tab = fold_blob_table(records)
+    return FoldTable(torch.from_numpy(tab).to(device), tab, int(tab[1]), int(tab[2]), [int(v) for v in tab[3:7]])
+
+
+def fold_blob_f32(w_flat, g_flat, b_flat, buffers, plan, eps=1e-3, out=None):
+    """The fp32 data section of the "OBBW" blob of `plan` (a `FoldTable`) from the four flat buffers of a train.ParamGroups (or a ModelEMA's copies
+    of them) by ONE kernel launch: BatchNorm folded into every conv in `train._BNBlock.fold()`'s fp32 operation order, the head's plain convs
+    copied, the qkv rows back in checkpoint order.  No host read, copy or synchronisation: it can sit inside a captured graph."""
+    srcs = [_chk(t, torch.float32, n) for t, n in zip((w_flat, g_flat, b_flat, buffers), ("w_flat", "g_flat", "b_flat", "buffers"))]
+    for t, need, n in zip(srcs, plan.need, ("w_flat", "g_flat", "b_flat", "buffers")):
+        if t.numel() < need or t.device != plan.table.device:
+            raise ValueError(f"fold_blob_f32: {n} holds {t.numel()} elements on {t.device}, the plan reads {need} on {plan.table.device}")
+    out = torch.empty(plan.out_elems, dtype=torch.float32, device=srcs[0].device) if out is None else _chk(out, torch.float32, "out")
+    if out.numel() != plan.out_elems or out.device != plan.table.device:
+        raise ValueError(f"fold_blob_f32: out holds {out.numel()} elements, the plan's data section {plan.out_elems}")
+    _O.fold_blob(*srcs, plan.table, plan.nrec, float(eps), out)
+    return out
+
+
+def val_thresholds(device):
+    """The validator's ten IoU thresholds, float32(linspace(0.5, 0.95, 10)), on the device"""
+    return torch.linspace(0.5, 0.95, 10, dtype=torch.float32).to(device)
+
+
+def val_match(det, count, gt_labels, gt_bboxes, mask_gt, nc, thr=None, out=None):
+    """The validator's matching (csrc/valmatch.hip): det [B,max_det,7] / count [B] of `decode_nms`, the padded ground truth of `pad_targets` /
+    `aug_labels` (pixels) -> (tp uint16 [B,max_det]: bit i = true positive at thr[i], best_iou fp32 [B,max_det], best_gt int32 [B,max_det], -1:
+    none).  thr: device fp32, ascending, at most 16 (default `val_thresholds`).  Rows at or past count[b]: (0, 0, -1)."""
+    d = _chk(det, torch.float32, "det")
+    if d.dim() != 3 or d.shape[2] != 7 or d.shape[1] < 1:
+        raise ValueError(f"val_match: det must be [B, max_det >= 1, 7], got {tuple(d.shape)}")
+    B, max_det = d.shape[0], d.shape[1]
+    cnt, gl, gb = _chk(count, torch.int32, "count"), _chk(gt_labels, torch.int32, "gt_labels"), _chk(gt_bboxes, torch.float32, "gt_bboxes")
+    mk = mask_gt.view(torch.uint8) if mask_gt.dtype == torch.bool else mask_gt
+    mk = _chk(mk, torch.uint8, "mask_gt")
+    n_cap = gl.shape[1] if gl.dim() == 2 else 0
+    if cnt.shape != (B,) or gl.shape != (B, n_cap) or gb.shape != (B, n_cap, 5) or mk.shape != (B, n_cap):
+        raise ValueError("val_match: count [B], gt_labels [B,n_cap], gt_bboxes [B,n_cap,5], mask_gt [B,n_cap] expected")
+    if not 1 <= n_cap <= _lib.VAL_MAX_GT or nc < 1:
+        raise ValueError(f"val_match: n_cap = {n_cap} outside [1, {_lib.VAL_MAX_GT}] or nc = {nc} < 1")
+    thr = val_thresholds(d.device) if thr is None else _chk(thr, torch.float32, "thr")
+    if thr.dim() != 1 or not 1 <= thr.numel() <= _lib.VAL_MAX_THR:
+        raise ValueError(f"val_match: 1..{_lib.VAL_MAX_THR} thresholds (one bit of tp each)")
+    if out is None:
+        out = (torch.empty((B, max_det), dtype=torch.uint16, device=d.device), torch.empty((B, max_det), dtype=torch.float32, device=d.device),
+               torch.empty((B, max_det), dtype=torch.int32, device=d.device))
+    tp, bi, bg = _chk(out[0], torch.uint16, "tp"), _chk(out[1], torch.float32, "best_iou"), _chk(out[2], torch.int32, "best_gt")
+    if not (tp.shape == bi.shape == bg.shape == (B, max_det)):
+        raise ValueError("val_match: out = (tp, best_iou, best_gt), each [B, max_det]")
+    if B:
+        _O.val_match(d, cnt, gl, gb, mk, int(nc), thr, tp, bi, bg)
+    return tp, bi, bg
 
 
 def dfl_loss(pred_dist, target_ltrb, weight=None, target_scores_sum=1.0, reg_max=16):

@@ -45,8 +45,13 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     bias group ramping DOWN from warmup_bias_lr) followed by the linear or cosine `lrf` decay, gradient accumulation up to the nominal batch size,
     and the EMA of the weights AND the BatchNorm running statistics (`ParamGroups.buffers`), the model the trainer validates and saves.  One update
     is a fixed handful of launches over the flat group buffers whatever the number of layers (accumulate, sum of squares, coefficient, step of all
-    three groups, EMA), none of which reads back to the host; `_Step.step(..., ni=, epoch=)` runs it when the module's `update` is set."""
+    three groups, EMA), none of which reads back to the host; `_Step.step(..., ni=, epoch=)` runs it when the module's `update` is set;
+  * `FoldPlan` / `Validator`: the `val` pass behind every epoch of `model.train(...)` -- the flat buffers (live or the EMA's) folded into an "OBBW"
+    weight blob by one launch (csrc/foldblob.hip), reloaded into an inference-engine slot of the validator's own (`model.YOLO.reload`), the pool's
+    tiles run through it unaugmented, the detections matched to the targets at ten ProbIoU thresholds (csrc/valmatch.hip) and cumulated to
+    mAP50 / mAP50-95 / fitness on the host (`metrics.ap_per_class`); `Net.validate` is the shorthand."""
 import math
+import struct
 
 import torch
 
@@ -1294,6 +1299,21 @@ class Net(_Step):
                 out[name] = b.fold() if isinstance(b, _BNBlock) else (b.w, b.b)
         return out
 
+    validator = None
+
+    def validate(self, pool, **kw):
+        """One validation of this net on `pool` (a `TrainBatcher`, or its three pool tensors) -> `Validator`'s result dict.  The `Validator` is kept
+        (`self.validator`, with its `best_fitness` / `is_best`) and reused while `pool` is the same object and the keyword arguments are equal.
+        Another pool or other arguments make a NEW one: the old one is closed (its engine slot released at once) and `best_fitness` starts over --
+        hold a `Validator` of your own where the best fitness has to outlive such a change."""
+        v = self.validator
+        if v is None or v.made_from[0] is not pool or v.made_from[1] != kw:
+            if v is not None:
+                v.close()
+            v = self.validator = Validator(self, pool, **kw)
+            v.made_from = (pool, dict(kw))
+        return v()
+
     def _attach(self, H, W):
         if not self.pack:
             return
@@ -1444,3 +1464,208 @@ class TrainerUpdate:
             self.ema.update()
         self.last_opt_step, self.n_acc = ni, 0
         return clip
+
+
+# yolo11-obb.yaml `scales`: depth, width, max_channels of the scales `Trunk` trains (the blob's header carries them)
+_YAML_SCALES = {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024)}
+_REG_MAX = 16
+
+
+class FoldPlan:
+    """The "OBBW" weight blob of a built `Net` (the format `obb_model_load` parses: header, record table, fp32 data section), refreshed from the
+    flat parameter buffers by ONE launch and ONE device-to-host copy.  The constructor writes the header and the record table once, on the host --
+    record names from `Net.named_blocks()` (the trunk's, then the head's, checkpoint order), c1 / c2 / k / s / g / act from the blocks -- into a
+    buffer that is pinned when the net lives on a device, and builds the kernel's table (ops.fold_blob_plan).  `run(ema=None)` folds the live
+    buffers, or `ema.ema` (a `ModelEMA`'s copies: no `ema.applied()` swap, nothing of the net is written), into the data section and returns the
+    whole blob as a memoryview of that buffer, valid until the next `run()`.  The arithmetic is `_BNBlock.fold()`'s in IEEE fp32; the qkv convs'
+    rows come back in checkpoint order.  On a CPU-built net the header and table are there (`blob`), `run()` raises: there is no CPU path."""
+
+    def __init__(self, net):
+        import numpy as np
+        from . import _lib
+        groups = net.groups
+        if groups.opts is None:
+            raise RuntimeError("FoldPlan: the net's groups are not built")
+        if net.scale not in _YAML_SCALES:
+            raise ValueError(f"FoldPlan: scale {net.scale!r}")
+        self.net, self.flats = net, [o.param for o in groups.opts] + [groups.buffers]
+
+        def off(t, k):
+            flat = self.flats[k]
+            if t.untyped_storage().data_ptr() != flat.untyped_storage().data_ptr() or not t.is_contiguous():
+                raise ValueError("FoldPlan: a layer's tensor is no view of the groups' flat buffers")
+            return t.storage_offset() - flat.storage_offset()
+
+        blocks = net.named_blocks()
+        qkv = {id(m.attn.qkv) for m in net.trunk.m[10].m}
+        eps = {b.eps for _, b in blocks if isinstance(b, _BNBlock)}
+        if len(eps) != 1:
+            raise ValueError(f"FoldPlan: the BatchNorm blocks carry different eps {sorted(eps)}: one launch folds with one")
+        self.eps = eps.pop()
+        depth, width, max_ch = _YAML_SCALES[net.scale]
+        hdr = struct.pack("<4sIIiiffii", b"OBBW", 1, len(blocks), net.nc, net.ch, width, depth, max_ch, _REG_MAX) + struct.pack("<8s", net.scale.encode())
+        rec_size = 64 + 6 * 4 + 2 * 8
+        self.data_off = (len(hdr) + rec_size * len(blocks) + 63) // 64 * 64
+        table, recs, o = b"", [], self.data_off
+        self.names = [name for name, _ in blocks]
+        for name, b in blocks:
+            if len(name.encode()) > 63:
+                raise ValueError(f"FoldPlan: record name too long: {name}")
+            bn = isinstance(b, _BNBlock)
+            g = b.c1 if isinstance(b, DWConvBN) else 1
+            k, st, act = (b.k, b.s, b.act) if bn else (1, 1, False)
+            per = (b.c1 // g) * k * k
+            if tuple(b.w.shape) != (b.c2, b.c1 // g, k, k):
+                raise ValueError(f"FoldPlan: {name}: weights {tuple(b.w.shape)}")
+            table += struct.pack("<64siiiiiiQQ", name.encode(), b.c1, b.c2, k, st, g, int(act), o, o + 4 * b.c2 * per)
+            o += 4 * b.c2 * (per + 1)
+            if bn:
+                kind = _lib.FOLD_QKV if id(b) in qkv else _lib.FOLD_BN
+                recs.append((kind, off(b.w, 0), off(b.gamma, 1), off(b.beta, 2), off(b.running_mean, 3), off(b.running_var, 3), b.c2, per))
+            else:
+                recs.append((_lib.FOLD_PLAIN, off(b.w, 0), 0, off(b.b, 2), 0, 0, b.c2, per))
+        self.nbytes = o
+        dev = self.flats[0].device
+        self._buf = torch.zeros(o, dtype=torch.uint8, pin_memory=dev.type == "cuda")
+        self._np = self._buf.numpy()
+        head = hdr + table
+        self._np[:self.data_off] = np.frombuffer(head + b"\0" * (self.data_off - len(head)), np.uint8)
+        self._data = self._buf[self.data_off:].view(torch.float32)
+        self.records = recs
+        self.table = ops.fold_blob_plan(dev, recs) if dev.type == "cuda" else None
+        self.host_table = ops.fold_blob_table(recs)
+        if 4 * int(self.host_table[2]) != o - self.data_off:
+            raise RuntimeError("FoldPlan: the kernel table and the blob's record table disagree about the data section")
+        self.out = torch.empty(int(self.host_table[2]), dtype=torch.float32, device=dev) if dev.type == "cuda" else None
+
+    @property
+    def blob(self):
+        """the whole blob (header, table, data section as of the last `run()`) as a memoryview of the plan's host buffer"""
+        return memoryview(self._np)
+
+    def fold(self, ema=None):
+        """the launch alone -> the data section on the device (fp32, `self.out`)"""
+        if self.table is None:
+            raise RuntimeError("FoldPlan: the net is on the CPU; the fold is a HIP kernel and has no CPU path")
+        srcs = self.flats if ema is None else ema.ema
+        if len(srcs) != 4 or any(a.shape != b.shape for a, b in zip(srcs, self.flats)):
+            raise ValueError("FoldPlan: `ema` is no ModelEMA over this net's groups")
+        return ops.fold_blob_f32(*srcs, self.table, self.eps, out=self.out)
+
+    def run(self, ema=None):
+        self._data.copy_(self.fold(ema), non_blocking=True)
+        torch.cuda.current_stream(self.out.device).synchronize()
+        return self.blob
+
+
+class Validator:
+    """The trainer's validation of the net being trained (Ultralytics 8.3.x `OBBValidator` behind `model.train(...)`, Train_OBB.py:792-841; restated
+    from recall: the package is not installed, so conf 0.001, iou 0.7, max_det 300, the matching rule, the 101-point AP and fitness = 0.1 mAP50 +
+    0.9 mAP50-95 are UNPINNED, like `Schedule` and `optimizer_config`).  Validator(net, pool, ...)() does, in order:
+        FoldPlan.run(ema)  ->  model.YOLO.reload(blob) into an engine slot of the validator's own  ->  per batch of `batch` pool tiles, in pool
+        order: the tiles and their `xywhr` targets from ops.aug_tiles / ops.aug_labels under IDENTITY records (no mosaic, affine, HSV or flip),
+        `YOLO.predict_tiles`, ops.val_match  ->  ONE read-back of confidences, classes, true-positive bits and target classes  ->
+        metrics.ap_per_class
+    and returns {"map50", "map", "fitness", "ap" [classes present, 10], "n_det", "n_gt"}; `best_fitness` / `is_best` follow the calls (is_best:
+    this call's fitness is at least every earlier one's, the trainer's rule for `best.pt`).  pool: a `TrainBatcher` or its three pool tensors
+    (tiles uint8 [N,s,s,C], labels fp64 [N,Lmax,9], counts int32 [N]); the tiles go to the engine as stored -- BGR, what `YOLO` expects -- unless
+    `swap_rb`.  ema: a `ModelEMA` over the net's groups (the model the trainer validates) or None for the live parameters.  Nothing of the net,
+    its optimiser state or the EMA is written, and the engine context's active slot and options are left as found (ops.engine_state).
+    `update(det, count, gt_labels, gt_bboxes, mask_gt)` adds given detections to the statistics and `result()` cumulates them: matching and AP
+    can be driven without the net's forward (`reset()` first).  `close()` releases the engine slot.
+    Targets: the label kernel runs with NEUTRAL candidate thresholds (no minimum side, aspect or area ratio: the training filter of
+    `AugmentConfig` is not applied), so every label of the pool counts, with two exceptions that are the trainer's own -- a label whose rectangle
+    clipped to the tile has a side under 2 px is dropped (`pad_targets`' rule, inside ops.aug_labels), and a tile with more than `n_cap` labels
+    raises ValueError at the read-back rather than losing ground truth silently."""
+
+    def __init__(self, net, pool, batch=16, conf=0.001, iou=0.7, max_det=300, precision="f32", ema=None, n_cap=64, swap_rb=False):
+        from .augment import TrainBatcher
+        if isinstance(pool, TrainBatcher):
+            pool = (pool.tiles, pool.labels, pool.counts)
+        from .augment import AugmentConfig
+        neutral = AugmentConfig(wh_thr=-1.0, ar_thr=float("inf"), area_thr=-1.0)  # box_candidates keeps everything: validation drops no target
+        self.batcher = TrainBatcher(*pool, cfg=neutral, n_cap=n_cap, bgr=True, swap_rb=swap_rb)
+        if self.batcher.tiles.shape[3] != net.ch or self.batcher.s % 32:
+            raise ValueError(f"Validator: the net reads {net.ch}-channel tiles with a side that is a multiple of 32, the pool holds "
+                             f"{tuple(self.batcher.tiles.shape[1:])}")
+        if batch < 1 or max_det < 1:
+            raise ValueError("Validator: batch and max_det are at least 1")
+        self.net, self.ema, self.batch, self.conf, self.iou, self.max_det, self.precision = net, ema, int(batch), float(conf), float(iou), int(max_det), precision
+        self.plan = FoldPlan(net)
+        self.device = self.batcher.tiles.device
+        self.model, self.thr = None, ops.val_thresholds(self.device)
+        self.table = self._identity_table()
+        self.bufs = self.batcher.buffers(min(self.batch, self.batcher.N))
+        self.tiles = None  # the tiles of the latest batch as the engine read them
+        self.best_fitness, self.is_best, self.last = None, False, None
+        self.reset()
+
+    def _identity_table(self):
+        import numpy as np
+        from . import augment
+        t = np.zeros(self.batcher.N, augment.REC)
+        for i in range(self.batcher.N):
+            augment.make_record(t[i], np.eye(3), 1.0, self.batcher.s, src=(i, 0, 0, 0))
+        augment.check_table(t, self.batcher.N, self.batcher.s)
+        return augment.table_to_device(t, self.device)
+
+    def reset(self):
+        self.stats, self._label_counts = [], []
+
+    def close(self):
+        """releases the validator's engine slot (weights, plans, slabs); the next call loads a model again"""
+        if self.model is not None:
+            self.model.close()
+            self.model = None
+
+    def update(self, det, count, gt_labels, gt_bboxes, mask_gt):
+        """det [B,max_det,7] / count [B] as `YOLO.predict_tiles` returns them, the padded targets in pixels (device) -> (tp, best_iou, best_gt) of
+        ops.val_match; the batch joins the statistics `result()` cumulates (device tensors: nothing is read back here)."""
+        tp, bi, bg = ops.val_match(det, count, gt_labels, gt_bboxes, mask_gt, self.net.nc, self.thr)
+        self.stats.append((tp, det[:, :, 4:6].contiguous(), count.clone(), gt_labels.clone(), mask_gt.clone()))
+        return tp, bi, bg
+
+    def result(self):
+        """the statistics since `reset()` -> {"map50", "map", "fitness", "ap", "n_det", "n_gt"} (the one read-back, then numpy float64)"""
+        import numpy as np
+        from . import metrics
+        nt = self.thr.numel()
+        if self.stats:
+            tp, cc, cnt, gl, mk = (torch.cat(ts).cpu() for ts in zip(*self.stats))
+            live = (torch.arange(tp.shape[1])[None, :] < cnt.clamp(0, tp.shape[1])[:, None]).numpy()
+            bits = tp.numpy()[live]
+            tpb = ((bits[:, None].astype(np.int64) >> np.arange(nt)[None, :]) & 1).astype(bool)
+            conf, cls = cc[..., 0].numpy()[live], cc[..., 1].numpy()[live]
+            target = gl.numpy()[mk.numpy().astype(bool)]
+            if self._label_counts and int(torch.cat(self._label_counts).max()) > self.batcher.n_cap:  # (read back with the rest)
+                raise ValueError(f"Validator: a tile has {int(torch.cat(self._label_counts).max())} labels, n_cap = {self.batcher.n_cap}: ground truth would be lost; "
+                                 "raise n_cap (at most 512)")
+        else:
+            tpb, conf, cls, target = np.zeros((0, nt), bool), np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32)
+        r = metrics.ap_per_class(tpb, conf, cls, target, self.net.nc)
+        return {"map50": r["map50"], "map": r["map"], "fitness": r["fitness"], "ap": r["ap"], "n_det": int(len(conf)), "n_gt": int(len(target))}
+
+    def __call__(self):
+        from .model import YOLO
+        b, N = self.batcher, self.batcher.N
+        with torch.cuda.device(self.device), ops.engine_state(self.device):
+            blob = self.plan.run(self.ema)
+            if self.model is None:
+                self.model = YOLO(blob, imgsz=b.s, device=self.device, precision=self.precision)
+            else:
+                self.model.reload(blob)
+            self.reset()
+            for b0 in range(0, N, self.batch):
+                nb = min(self.batch, N - b0)
+                tiles, gl, gb, mk, cnt = (t[:nb] for t in self.bufs[1:])
+                b.batch_into(self.table[b0:b0 + nb], tiles, gl, gb, mk, cnt)
+                self._label_counts.append(cnt.clone())
+                det, count = self.model.predict_tiles(tiles, self.conf, self.iou, self.max_det)
+                self.update(det, count, gl, gb, mk)
+                self.tiles = tiles
+            out = self.result()
+        self.is_best = self.best_fitness is None or out["fitness"] >= self.best_fitness
+        if self.is_best:
+            self.best_fitness = out["fitness"]
+        self.last = out
+        return out

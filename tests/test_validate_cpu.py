@@ -1,0 +1,152 @@
+"""The host side of the trainer's validation (no GPU): metrics.ap_per_class against tests/val_ref.py's plain-loop restatement and hand cases,
+train.FoldPlan's header and record table against tools/export_obbw.blob_from_records on a CPU-built net, and the margins of the matching cases the
+GPU test uses (so that it can demand exact equality of every true-positive bit)."""
+import numpy as np
+import pytest
+import torch
+
+import net_ref as NR
+import val_ref as VR
+
+
+def _metrics():
+    import oriented_object_detection_amd  # noqa: F401
+    from oriented_object_detection_amd import metrics
+    return metrics
+
+
+# ------------------------------------------------------------------------------------------------------------ 1. AP
+def _random_case(seed, n, m, nc, absent=None, undetected=None, ties=False):
+    rng = np.random.RandomState(seed)
+    target = rng.randint(0, nc, m)
+    if absent is not None:
+        target = target[target != absent]
+    pred = rng.randint(0, nc, n)
+    if undetected is not None:
+        pred = pred[pred != undetected]
+        target = np.concatenate([target, [undetected, undetected]])
+    conf = rng.uniform(0, 1, len(pred))
+    if ties:
+        conf = np.round(conf * 8) / 8
+    iou = rng.uniform(0.3, 1.0, len(pred))
+    tp = iou[:, None] >= VR.THR[None, :]
+    for c in range(nc):  # a class has at most as many true positives as targets (recall <= 1), the most confident first
+        idx = [i for i in np.argsort(-conf, kind="stable") if pred[i] == c]
+        for j in range(tp.shape[1]):
+            hits = [i for i in idx if tp[i, j]]
+            tp[hits[int((target == c).sum()):], j] = False
+    return tp, conf, pred, target
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(absent=2), dict(undetected=1), dict(ties=True), dict(absent=0, undetected=3, ties=True)], ids=str)
+def test_ap_per_class_equals_reference(kw):
+    M = _metrics()
+    for seed in range(4):
+        tp, conf, pred, target = _random_case(seed, 120, 40, 5, **kw)
+        got, ref = M.ap_per_class(tp, conf, pred, target, 5), VR.ap_per_class(tp, conf, pred, target, 5)
+        assert got["ap"].shape == ref["ap"].shape == (len(set(target.tolist())), 10)
+        assert np.abs(got["ap"] - ref["ap"]).max() <= 1e-12
+        for k in ("map50", "map", "fitness"):
+            assert abs(got[k] - ref[k]) <= 1e-12, k
+        assert abs(got["fitness"] - (0.1 * got["map50"] + 0.9 * got["map"])) <= 1e-15
+        if kw.get("undetected") is not None:
+            assert (got["ap"][list(got["classes"]).index(kw["undetected"])] == 0).all()
+        if kw.get("absent") is not None:
+            assert kw["absent"] not in got["classes"]
+
+
+def test_ap_hand_cases():
+    M = _metrics()
+    # perfect detections: every recall point has precision 1, so the envelope is 1 on [0, 1) and the 101-point curve is 1 except its last point,
+    # which the closing sentinel (recall 1, precision 0) pulls to 0: trapezoid = 1 - 0.01 / 2 = 0.995
+    target = np.array([0, 0, 1, 2, 2, 2])
+    r = M.ap_per_class(np.ones((6, 10), bool), np.linspace(0.9, 0.4, 6), target, target, 3)
+    assert np.abs(r["ap"] - 0.995).max() <= 1e-12 and abs(r["map"] - 0.995) <= 1e-12 and abs(r["fitness"] - 0.995) <= 1e-12
+    # no detections
+    r = M.ap_per_class(np.zeros((0, 10), bool), np.zeros(0), np.zeros(0), target, 3)
+    assert r["ap"].shape == (3, 10) and not r["ap"].any() and r["map50"] == r["map"] == r["fitness"] == 0.0
+    # no targets at all
+    r = M.ap_per_class(np.ones((2, 10), bool), np.array([0.5, 0.4]), np.array([0, 1]), np.zeros(0, int), 3)
+    assert r["ap"].shape == (0, 10) and r["map"] == 0.0
+    # two detections of descending confidence on a class with two targets, the FIRST a true positive, the second not:
+    #   recall = (0.5, 0.5), precision = (1, 0.5);  mrec = (0, 0.5, 0.5, 1), mpre = (1, 1, 0.5, 0) -> envelope (1, 1, 0.5, 0)
+    #   interp at x = 0, 0.01, ..., 1: 1 for x <= 0.5 (np.interp takes the LAST of the repeated points at 0.5: 0.5 -- so y(0.5) = 0.5),
+    #   then the line from (0.5, 0.5) to (1, 0): y = 1 - x.
+    #   trapezoid: 49 intervals of height 1 (x in [0, 0.49]) = 0.49; [0.49, 0.5]: (1 + 0.5) / 2 * 0.01 = 0.0075;
+    #   [0.5, 1]: the triangle-plus-nothing under y = 1 - x = 0.5 * 0.5 / 2 = 0.125  ->  0.6225
+    tp = np.zeros((2, 10), bool)
+    tp[0] = True
+    r = M.ap_per_class(tp, np.array([0.9, 0.8]), np.array([1, 1]), np.array([1, 1]), 3)
+    assert np.abs(r["ap"] - 0.6225).max() <= 1e-12
+    # the same with the true positive SECOND: precision (0, 0.5), recall (0, 0.5): envelope (1, 0.5, 0.5, 0) over mrec (0, 0, 0.5, 1):
+    #   y(0) = 0.5 (last repeat), 0.5 on [0, 0.5], then 1 - x: 0.25 + 0.125 = 0.375
+    r = M.ap_per_class(tp[::-1], np.array([0.9, 0.8]), np.array([1, 1]), np.array([1, 1]), 3)
+    assert np.abs(r["ap"] - 0.375).max() <= 1e-12
+    # equal confidences keep their input order (stable sort): the two orders above with conf equal give the two values above
+    r1 = M.ap_per_class(tp, np.array([0.5, 0.5]), np.array([1, 1]), np.array([1, 1]), 3)
+    r2 = M.ap_per_class(tp[::-1], np.array([0.5, 0.5]), np.array([1, 1]), np.array([1, 1]), 3)
+    assert abs(r1["map"] - 0.6225) <= 1e-12 and abs(r2["map"] - 0.375) <= 1e-12
+
+
+# ------------------------------------------------------------------------------------------------------------ 2. FoldPlan on a CPU-built net
+@pytest.mark.parametrize("scale,ch", [("n", 3), ("n", 4), ("s", 3)], ids=["n-ch3", "n-ch4", "s-ch3"])
+def test_fold_plan_header_and_table(scale, ch):
+    import oriented_object_detection_amd  # noqa: F401
+    from oriented_object_detection_amd import _lib, train
+    from tools.export_obbw import blob_from_records
+    net = train.Net.from_state(NR.make_state(scale, 12, ch, seed=5), scale, 12, ch)
+    plan = train.FoldPlan(net)
+    table = NR.conv_table(scale, 12, ch)
+    fold = net.fold()
+    assert set(plan.names) == set(table) == set(fold) and len(plan.names) == len(table)
+    recs = [(name, table[name].c1, table[name].c2, table[name].k, table[name].s, table[name].g, table[name].act, w.detach(), b.detach())
+            for name, (w, b) in fold.items()]
+    ref = blob_from_records(recs, 12, ch, scale)
+    got = bytes(plan.blob)
+    assert len(got) == len(ref) and plan.data_off % 64 == 0
+    assert got[:plan.data_off] == ref[:plan.data_off]
+    # the kernel's table describes the same data section: dense, record after record, weights then bias
+    H, R = _lib.FOLD_TABLE_HEAD, _lib.FOLD_TABLE_REC
+    t = plan.host_table
+    assert t[0] == _lib.FOLD_MAGIC and t[1] == len(recs) and 4 * t[2] == len(ref) - plan.data_off
+    dst = wg = 0
+    for i, (name, c1, c2, k, s, g, act, w, b) in enumerate(recs):
+        r = t[H + i * R:H + (i + 1) * R]
+        assert r[5] == dst and (r[6] & 0xffffffff) == c2 and (r[6] >> 32) == w[0].numel() and (r[7] & 0xffffffff) == wg, name
+        kind = r[7] >> 32
+        assert kind == (_lib.FOLD_PLAIN if NR.is_plain(name) else _lib.FOLD_QKV if name.endswith("attn.qkv") else _lib.FOLD_BN), name
+        dst, wg = dst + w.numel() + c2, wg + (w.numel() + c2 + 255) // 256
+    with pytest.raises((RuntimeError, ValueError)):
+        plan.run()  # no CPU path
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. the matching cases' margins
+def test_matching_cases_have_margins():
+    cases = [VR.match_cases(), VR.tiny_case()]
+    band, p64s = VR.band(cases)
+    print(f"ProbIoU fp32 vs fp64 over the matching cases: band = 4 x max |diff| = {band:.3e}")
+    assert 0 < band < 1e-4
+    thr = VR.THR.astype(np.float64)
+    n_pairs = spread = 0
+    for pairs in p64s:
+        for b, d, gs, iou in pairs:
+            n_pairs += len(gs)
+            top = np.sort(iou)[::-1]
+            assert np.abs(top[0] - thr).min() > band, (b, d, top[0])
+            if len(top) > 1:
+                assert top[0] - top[1] > band, (b, d, top[:2])
+            spread = max(spread, top[0])
+    assert n_pairs > 5000 and spread > 0.95
+    # the cases contain what they are meant to contain
+    det, count, gl, gb, mk, nc = cases[0]
+    tp, bi, bg = VR.match(det, count, gl, gb, mk, nc)
+    live0 = bi[0, :300]
+    assert live0.min() < 0.4 and live0.max() > 0.95 and ((live0 >= 0.5) & (tp[0, :300] & 1 == 0)).any()  # IoU 0.3 .. 1; a claim lost to an earlier one
+    assert bg[1, 0] == 0 and tp[1, 0] & 1                      # d0 takes g0
+    assert bg[1, 1] == 0 and tp[1, 1] == 0 and bi[1, 1] > 0.5  # d1 loses g0 ...
+    assert VR.probiou(gb[1, 1:2], det[1, 1:2, [0, 1, 2, 3, 6]].reshape(1, 5))[0, 0] > 0.5  # ... and its second best lies above 0.5: stays unmatched
+    assert bg[1, 2] == 2 and tp[1, 2] == 0 and VR.probiou(gb[1, 3:4], det[1, 2:3, [0, 1, 2, 3, 6]].reshape(1, 5))[0, 0] > 0.8  # wrong class, high IoU
+    assert bg[1, 3] == bg[1, 4] == 3 and tp[1, 3] & 1 and not tp[1, 4] & 1   # two on one
+    assert bg[1, 5] == 4 and tp[1, 5] == 0 and 0.2 < bi[1, 5] < 0.5
+    assert bg[2, 0] == -1 and tp[2].sum() == 0 and (bg[3] == -1).all()
+    assert (bg[0, 300:] == -1).all() if det.shape[1] > 300 else True
