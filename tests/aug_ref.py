@@ -4,7 +4,11 @@ in float64 with np.rint as cv2 builds them, where the device uses closed-form in
 Ultralytics 8.3.x and cv2 restated from recall (neither is installed): UNPINNED.  The record layout is read from the product's own `augment.REC`.
 
 `label_ref(..., bug=...)` plants one of six mistakes (BUGS) for the tests that show the sanity checks catch them; `margins=` collects, per discrete
-decision, (kind, relative margin) so that the CPU suite can assert no committed GPU case sits within rounding of a decision."""
+decision, (kind, relative margin) so that the CPU suite can assert no committed GPU case sits within rounding of a decision.
+
+`label_cases()` and `label_edge_cases()` are the label cases of the GPU suite (the second: the label kernel's launch and domain edges); the builders
+beside them (`centre_table`, `offcanvas_table`, `colour_pool` / `colour_table`) are the pixel cases of tests/test_gpu_batch_edges.py."""
+import functools
 import math
 
 import numpy as np
@@ -84,6 +88,15 @@ def hsv2bgr(h, sat, v):
     return out
 
 
+def hsv_apply(img, lut, bgr=True):
+    """the HSV gains on [..., C >= 3] uint8 in place: integer BGR -> HSV, the three tables, fp32 HSV -> BGR; a fourth channel stays"""
+    cb, cr = (0, 2) if bgr else (2, 0)
+    h, sa, v = bgr2hsv(img[..., cb], img[..., 1], img[..., cr])
+    nb, ng, nr = hsv2bgr(lut[h], lut[256 + sa], lut[512 + v])
+    img[..., cb], img[..., 1], img[..., cr] = nb, ng, nr
+    return img
+
+
 def tiles_ref(pool, table, bgr=True, swap_rb=False):
     """-> uint8 [B, s, s, C]: what obb_aug_tiles must give, bit for bit"""
     s = pool.shape[1]
@@ -96,11 +109,7 @@ def tiles_ref(pool, table, bgr=True, swap_rb=False):
             img = img[::-1]
         img = img.copy()
         if rec["flags"] & 8:
-            lut = rec["lut"]
-            cb, cr = (0, 2) if bgr else (2, 0)
-            h, sa, v = bgr2hsv(img[..., cb], img[..., 1], img[..., cr])
-            nb, ng, nr = hsv2bgr(lut[h], lut[256 + sa], lut[512 + v])
-            img[..., cb], img[..., 1], img[..., cr] = nb, ng, nr
+            hsv_apply(img, rec["lut"], bgr)
         if swap_rb:
             img[..., [0, 2]] = img[..., [2, 0]]
         out[b] = img
@@ -206,6 +215,17 @@ def _rel(a, b):
     return abs(a - b) / max(abs(a), abs(b), 1e-300)
 
 
+def _separation(H, s):
+    """the widest gap between the convex hull H (counter-clockwise) and [0, s]^2 along the tile's axes and the hull's edge normals: positive exactly
+    when the two are disjoint (separating axes of two convex polygons).  The hull's box alone says nothing about a turned label beside a tile corner."""
+    gap = max(0.0 - H[:, 0].max(), H[:, 0].min() - s, 0.0 - H[:, 1].max(), H[:, 1].min() - s)
+    corners = np.array([(0.0, 0.0), (s, 0.0), (s, s), (0.0, s)])
+    for i in range(len(H)):
+        d = H[(i + 1) % len(H)] - H[i]
+        gap = max(gap, float(((corners - H[i]) @ (np.array([d[1], -d[0]]) / math.hypot(d[0], d[1]))).min()))  # (dy, -dx): the outward normal
+    return gap
+
+
 def candidate_ref(rec, q, row, s, wh_thr=2.0, ar_thr=100.0, area_thr=0.01, margins=None, bug=None):
     """one (quadrant, label row) -> (class, (x, y, w, h, theta)) or None"""
     mosaic = bool(rec["flags"] & 1)
@@ -246,11 +266,10 @@ def candidate_ref(rec, q, row, s, wh_thr=2.0, ar_thr=100.0, area_thr=0.01, margi
     if len(hl) < 3:
         return None
     poly = clip_square(hl, s)
-    if margins is not None:  # an empty clip: the gap between the hull's box and the tile, or the area that is left, over the tile's
+    if margins is not None:  # an empty clip: the gap between the hull and the tile, or the area that is left, over the tile's
         H = np.array(hl)
         if len(poly) < 3:
-            gap = max(0.0 - H[:, 0].max(), H[:, 0].min() - s, 0.0 - H[:, 1].max(), H[:, 1].min() - s)
-            margins.append(("clip", max(gap, 0.0) / s))
+            margins.append(("clip", max(_separation(H, s), 0.0) / s))
         else:
             Q = np.array(poly)
             margins.append(("clip", 0.5 * abs(np.dot(Q[:, 0], np.roll(Q[:, 1], -1)) - np.dot(Q[:, 1], np.roll(Q[:, 0], -1))) / (s * s)))
@@ -329,13 +348,14 @@ def rect_row(cls, cx, cy, w, h, theta, s):
     return np.concatenate([[cls], np.clip(xywhr_corners((cx, cy, w, h, theta)), 0, s).reshape(8) / s])
 
 
-def label_pool(N, Lmax, s, seed, empty=()):
+def label_pool(N, Lmax, s, seed, empty=(), counts=None):
+    """counts: the number of rows per tile where the caller sets it (None or a negative entry: drawn from 1 .. Lmax)"""
     rng = np.random.RandomState(seed)
     lab, cnt = np.zeros((N, Lmax, 9)), np.zeros(N, np.int32)
     for t in range(N):
         if t in empty:
             continue
-        cnt[t] = rng.randint(1, Lmax + 1)
+        cnt[t] = rng.randint(1, Lmax + 1) if counts is None or counts[t] < 0 else counts[t]
         for l in range(cnt[t]):
             lab[t, l] = rect_row(rng.randint(0, 12), rng.uniform(0, s), rng.uniform(0, s), rng.uniform(3, s / 2), rng.uniform(3, s / 2), rng.uniform(-1.5, 1.5), s)
     return lab, cnt
@@ -370,4 +390,126 @@ def label_cases():
     cases.append(("n_cap-2", s, lab3, cnt3, A.sample_params(A.AugmentConfig(scale=0.1), 3, 4, s, np.random.RandomState(77)), 2))
     # every source empty
     cases.append(("empty-pool", s, np.zeros((3, 4, 9)), np.zeros(3, np.int32), A.sample_params(A.AugmentConfig(), 2, 3, s, np.random.RandomState(5)), 3))
+    return cases
+
+
+# ---------------------------------------------------------------- the cases at the kernels' launch and domain edges
+def centre_ends(s):
+    """mosaic centres at the ends of what the kernels accept ([0, 2 s] each way): one or two quadrants of the canvas are empty"""
+    return [(0, 0), (2 * s, 2 * s), (0, 2 * s), (2 * s, 0), (s, 0), (0, s), (2 * s, s)]
+
+
+def centre_table(s, centre, src, hsv=True):
+    """three mosaic records around one centre: scale 0.5 (all of the canvas in view), the identity scale with translation 0.5 (the canvas' middle),
+    scale 0.5 flipped both ways"""
+    A = _aug()
+    t = np.zeros(3, A.REC)
+    for b, (sc, flip, gains) in enumerate([(0.5, False, (1.015, 1.7, 1.4)), (1.0, False, (0.985, 0.3, 0.6)), (0.5, True, (1.0, 1.0, 1.0))]):
+        A.make_record(t[b], A.affine(2 * s, s, 0.0, sc, 0.5, 0.5), sc, s, True, centre, src, flip, flip, gains if hsv else None)
+    return t
+
+
+OFF_BORDER = 3  # the first records of offcanvas_table leave the whole tile on the border value
+
+
+def offcanvas_table(N, s, mosaic, hsv, seed):
+    """maps that leave the canvas.  0: a translation by five tile sides; 1, 2: every `inv` entry +-1e7, written into the record (no matrix the
+    sampler draws gives it): both fixed-point terms saturate at +-2^29 and their sum stays outside the canvas; 3: +-1e7 with opposite signs: the
+    saturated terms cancel wherever x, y >= 1, so those pixels show canvas(0, 0) -- only with the saturation; the rest of row and column 0 stays outside"""
+    A = _aug()
+    rng = np.random.RandomState(seed)
+    S, gains = (2 * s if mosaic else s), ((1.015, 1.7, 1.4) if hsv else None)
+    t = np.zeros(4, A.REC)
+    A.make_record(t[0], A.affine(S, s, 0.0, 1.0, 5.5, 0.5), 1.0, s, mosaic, (s, s), rng.randint(0, N, 4), False, False, gains)
+    for b, inv in ((1, [1e7] * 6), (2, [-1e7] * 6), (3, [1e7, -1e7, 0.0, -1e7, 1e7, 0.0])):
+        A.make_record(t[b], np.eye(3), 1.0, s, mosaic, (s, s), rng.randint(0, N, 4), False, b == 2, gains)
+        t["inv"][b] = inv
+    return t
+
+
+def colour_pool():
+    """all 2^24 colours as 16 tiles of side 1024, C = 3: colour c = t << 20 | y << 10 | x with b = c & 255, g = (c >> 8) & 255, r = c >> 16"""
+    c = np.arange(1 << 24, dtype=np.uint32)
+    return np.stack([c & 255, (c >> 8) & 255, c >> 16], -1).astype(np.uint8).reshape(16, 1024, 1024, 3)
+
+
+HUE_LUT_OUT_OF_RANGE = "hue>=180"
+
+
+def colour_table(gains, tiles=range(16)):
+    """identity records (no mosaic) with the HSV bit set, one per tile of `colour_pool`.  gains = HUE_LUT_OUT_OF_RANGE: a hand-written table whose hue
+    entries run from 76 to 255 over the hues 0 .. 179 (those of 104 and above are no hue: the sector falls outside 0 .. 5), unit saturation / value"""
+    A = _aug()
+    t = np.zeros(len(tiles), A.REC)
+    for b, tile in enumerate(tiles):
+        A.make_record(t[b], np.eye(3), 1.0, 1024, src=(tile, 0, 0, 0), hsv_gains=(1.0, 1.0, 1.0) if isinstance(gains, str) else gains)
+        if isinstance(gains, str):
+            t["lut"][b, :256] = np.minimum(76 + np.arange(256), 255)
+    return t
+
+
+def pass_survivors(lab, cnt, table, s):
+    """per output tile, the survivors among the candidates [256 k, 256 k + 256), k = 0, 1, ..., in the label kernel's candidate order q * Lmax + l
+    (it takes 256 candidates per pass of its prefix sum)"""
+    Lmax, out = lab.shape[1], []
+    for rec in table:
+        nq = 4 if rec["flags"] & 1 else 1
+        per = [0] * max(1, -(-nq * Lmax // 256))
+        for q in range(nq):
+            t = int(rec["src"][q])
+            for l in range(min(max(int(cnt[t]), 0), Lmax)):
+                per[(q * Lmax + l) // 256] += candidate_ref(rec, q, lab[t, l], s) is not None
+        out.append(per)
+    return out
+
+
+def canvas_extent(rec, q, row, s):
+    """-> (w, h, w0, h0): a label's axis-aligned extent on the mosaic canvas after and before the cut at the canvas"""
+    padx, pady = float(rec["xc"] if q & 1 else rec["xc"] - s), float(rec["yc"] if q & 2 else rec["yc"] - s)
+    P = np.asarray(row[1:], np.float64).reshape(4, 2) * s + [padx, pady]
+    Q = np.clip(P, 0.0, 2.0 * s)
+    return (np.ptp(Q[:, 0]), np.ptp(Q[:, 1]), np.ptp(P[:, 0]), np.ptp(P[:, 1]))
+
+
+EDGE_LMAX = ((65, "fits", 0), (100, "inside", 0), (256, "boundary", 0))  # (Lmax, where n_cap falls, seed): re-seeded until the margins hold
+EDGE_SEEDS = {"n_cap": 0, "counts": 0, "centre": 0}
+CENTRE_EXTRA = lambda s: (s // 4, 2 * s - s // 4)  # (not an end: here the canvas cuts labels in part)
+
+
+def _lmax_case(Lmax, mode, seed, s=64):
+    A = _aug()
+    lab, cnt = label_pool(5, Lmax, s, 300 + seed, empty=(1,), counts=[Lmax, 0, Lmax - 1, -1, -1])
+    table = A.sample_params(A.AugmentConfig(scale=0.1), 3, 5, s, np.random.RandomState(400 + seed), [0, 2, 3])
+    table["src"][0] = (0, 2, 3, 0)  # the full tile in the last quadrant too: the candidates run up to 4 Lmax - 1
+    table["src"][1] = (2, 1, 0, 0)  # the empty tile in the middle of the candidate list
+    per = pass_survivors(lab, cnt, table, s)
+    if mode == "fits":
+        n_cap = max(sum(p) for p in per) + 3
+    elif mode == "inside":  # n_cap is reached inside the second pass of the tile with the most survivors in both of its first two
+        p = max(per, key=lambda p: min(p[0], p[1]))
+        n_cap = p[0] + max(p[1] // 2, 1)
+    else:  # n_cap = the survivors of the first pass of the tile with the most survivors behind it
+        n_cap = max(per, key=lambda p: sum(p[1:]))[0]
+    return f"Lmax{Lmax}-{mode}", s, lab, cnt, table, n_cap
+
+
+@functools.lru_cache(maxsize=None)
+def label_edge_cases():
+    """[(name, s, pool_labels, pool_counts, table, n_cap)] like label_cases(): several passes of the label kernel's prefix sum, n_cap reached in a later
+    pass and at a pass boundary, a zero-fill that strides, pool counts outside [0, Lmax], Lmax = 0, mosaic centres at the ends.  All at s = 64.
+    Built once per process; nobody writes into them."""
+    A = _aug()
+    s, cases = 64, [_lmax_case(L, mode, seed) for L, mode, seed in EDGE_LMAX]
+    lab, cnt = label_pool(7, 6, s, 500 + EDGE_SEEDS["n_cap"], empty=(3,))
+    table = A.sample_params(A.AugmentConfig(), 3, 7, s, np.random.RandomState(510 + EDGE_SEEDS["n_cap"]))
+    cases += [(f"few-n_cap{n}", s, lab, cnt, table, n) for n in (1, 257, 600)]
+    lab, cnt = label_pool(5, 6, s, 520 + EDGE_SEEDS["counts"], counts=[6] * 5)
+    cnt[1], cnt[3] = 6 + 5, -3  # every row of both tiles holds a label: the first must give 6 candidates, the second none
+    table = A.sample_params(A.AugmentConfig(scale=0.1), 3, 5, s, np.random.RandomState(530 + EDGE_SEEDS["counts"]))
+    table["src"][0], table["src"][1] = (1, 3, 0, 2), (1, 1, 3, 1)
+    cases.append(("counts-outside", s, lab, cnt, table, 40))
+    cases.append(("Lmax0", s, np.zeros((3, 0, 9)), np.array([0, 3, -1], np.int32), A.sample_params(A.AugmentConfig(), 2, 3, s, np.random.RandomState(540)), 5))
+    for k, centre in enumerate(centre_ends(s) + [CENTRE_EXTRA(s)]):
+        lab, cnt = label_pool(4, 6, s, 550 + 10 * EDGE_SEEDS["centre"] + k, counts=[6] * 4)
+        cases.append((f"centre-{centre[0]}-{centre[1]}", s, lab, cnt, centre_table(s, centre, (0, 1, 2, 3)), 24))
     return cases

@@ -286,12 +286,80 @@ def test_sample_params_ranges_seed_and_close_mosaic(A):
 
 # ---------------------------------------------------------------- the committed GPU cases keep clear of every discrete decision
 def test_gpu_label_cases_have_margin(A):
-    seen = {}
-    for name, s, lab, cnt, table, n_cap in R.label_cases():
+    seen, n = {}, 0
+    for name, s, lab, cnt, table, n_cap in R.label_cases() + R.label_edge_cases():
         m = []
         R.labels_ref(lab, cnt, table, s, n_cap, margins=m)
         for kind, v in m:
-            assert v >= 1e-9, (name, kind, v)
+            assert v >= 1e-9, (name, kind, v)  # every committed candidate is compared: none is left out
             seen[kind] = min(seen.get(kind, np.inf), v)
-    print({k: f"{v:.2e}" for k, v in seen.items()})
+        n += len(m)
+    print(n, "decisions;", {k: f"{v:.2e}" for k, v in seen.items()})
     assert {"wh", "aspect", "area", "clip", "edge", "tie", "quadrant", "2px"} <= set(seen)
+
+
+def test_separation_of_hull_and_tile():
+    """the margin of an empty clip: a turned label beside a tile corner, its box over the tile and itself clear of it"""
+    s = 64
+    H = np.array(R.hull(R.xywhr_corners((-6.0, -6.0, 40.0, 6.0, -math.pi / 4))))
+    assert H[:, 0].max() > 0 and H[:, 1].max() > 0 and len(R.clip_square([tuple(p) for p in H], s)) < 3
+    assert abs(R._separation(H, s) - (6.0 * math.sqrt(2.0) - 3.0)) < 1e-9  # the corner (0, 0) lies 6 sqrt 2 from the centre line, the label is 3 thick
+    assert R._separation(np.array(R.hull(R.xywhr_corners((2.0, 2.0, 40.0, 6.0, -math.pi / 4)))), s) < 0  # overlapping: no gap on any axis
+    assert abs(R._separation(np.array([(-9.0, 3.0), (-5.0, 3.0), (-5.0, 8.0), (-9.0, 8.0)]), s) - 5.0) < 1e-12
+
+
+def test_label_edge_cases_hold_what_they_claim(A):
+    """from the reference's own output: which passes of the kernel's prefix sum (256 candidates each) hold survivors, where n_cap falls, what the
+    canvas cuts"""
+    cases = {c[0]: c for c in R.label_edge_cases()}
+    assert all(c[1] == 64 for c in cases.values())
+    info = {}
+    for name in ("Lmax65-fits", "Lmax100-inside", "Lmax256-boundary"):
+        _, s, lab, cnt, table, n_cap = cases[name]
+        Lmax = lab.shape[1]
+        assert len(table) == 3 and lab.shape[0] == 5 and (table["flags"] & A.MOSAIC).all()
+        assert sorted(cnt.tolist())[0] == 0 and Lmax in cnt and Lmax - 1 in cnt
+        per = R.pass_survivors(lab, cnt, table, s)
+        count = R.labels_ref(lab, cnt, table, s, n_cap)[3]
+        assert [sum(p) for p in per] == count.tolist() and all(len(p) == -(-4 * Lmax // 256) for p in per)
+        assert any(sum(1 for v in p if v) >= 2 for p in per)  # survivors in at least two passes of one output tile
+        info[name] = (per, n_cap)
+        if name.endswith("fits"):
+            assert n_cap >= count.max()
+        elif name.endswith("inside"):  # some tile: the first pass leaves room, the second overfills
+            assert any(0 < p[0] < n_cap < p[0] + p[1] for p in per)
+        else:  # some tile: the first pass fills n_cap exactly and survivors follow, in the second AND the third pass
+            assert any(p[0] == n_cap and p[1] > 0 and p[2] > 0 for p in per) and (count > n_cap).any()
+    print(info)
+    for n_cap in (1, 257, 600):
+        _, s, lab, cnt, table, cap = cases[f"few-n_cap{n_cap}"]
+        count = R.labels_ref(lab, cnt, table, s, cap)[3]
+        assert cap == n_cap and 0 < count.max() < 24 and (n_cap == 1) == bool((count > n_cap).any())
+    _, s, lab, cnt, table, n_cap = cases["counts-outside"]
+    Lmax = lab.shape[1]
+    assert cnt[1] == Lmax + 5 and cnt[3] == -3 and lab[3].any() and lab[1, Lmax - 1].any() and all(1 in r["src"] and 3 in r["src"] for r in table[:2])
+    clamped = np.clip(cnt, 0, Lmax)
+    a, b = R.labels_ref(lab, cnt, table, s, n_cap), R.labels_ref(lab, clamped, table, s, n_cap)
+    assert all(np.array_equal(x, y) for x, y in zip(a[:4], b[:4])) and a[3][:2].min() > 0
+    _, s, lab, cnt, table, n_cap = cases["Lmax0"]
+    assert lab.shape == (3, 0, 9) and cnt.any() and not R.labels_ref(lab, cnt, table, s, n_cap)[3].any()
+    # the centres: a quadrant wholly off the canvas leaves its labels zero width or height there and none of them survives; the others do
+    for centre in R.centre_ends(64) + [R.CENTRE_EXTRA(64)]:
+        _, s, lab, cnt, table, n_cap = cases[f"centre-{centre[0]}-{centre[1]}"]
+        assert len(table) == 3 and all((r["xc"], r["yc"]) == centre and r["flags"] & A.MOSAIC for r in table)
+        zero = part = kept_part = kept = 0
+        for rec in table:
+            for q in range(4):
+                for l in range(cnt[rec["src"][q]]):
+                    w, h, w0, h0 = R.canvas_extent(rec, q, lab[rec["src"][q], l], s)
+                    r = R.candidate_ref(rec, q, lab[rec["src"][q], l], s)
+                    zero += w == 0 or h == 0
+                    assert not ((w == 0 or h == 0) and r is not None)
+                    cut = w > 0 and h > 0 and (w < w0 or h < h0)
+                    part, kept_part, kept = part + cut, kept_part + (cut and r is not None), kept + (r is not None)
+        print(centre, "labels of zero extent on the canvas", zero, "cut in part", part, "of those kept", kept_part, "kept in all", kept)
+        assert kept > 0
+        if centre == R.CENTRE_EXTRA(64):
+            assert part > 0 and kept_part > 0
+        else:
+            assert zero >= 3 * 6 and part == 0  # at least one whole quadrant (6 labels) in each of the three records

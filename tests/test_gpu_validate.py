@@ -217,7 +217,7 @@ def _dev(case):
 def test_val_match_exact(which):
     _lib, _, _, ops, _ = _mods()
     case = VR.match_cases() if which == "cases" else VR.tiny_case()
-    band, _ = VR.band([VR.match_cases(), VR.tiny_case()])
+    band, _ = VR.all_band()  # over every committed case, those of test_gpu_batch_edges.py included
     det, count, gl, gb, mk, nc = case
     B, M = det.shape[:2]
     if which == "cases":

@@ -6,7 +6,11 @@ Written from the rules (Ultralytics 8.3.x restated from recall, UNPINNED), not f
                                   index), claim iff IoU >= threshold, the lowest claiming index per (ground truth, threshold) is the true positive
   compute_ap / ap_per_class       the 101-point AP, plain Python loops in float
   match_cases(seed)               the data of the matching tests, shared by the CPU margin test and the GPU test
+  edge_cases()                    more of them at the kernel's edges: sizes up to the declared limits, 1 and 16 thresholds, forced ties, invalid live
+                                  rows, counts outside [0, max_det]; all_cases() / all_band(): old and new together and their band
   pair_ious(case, dtype)          the ProbIoU of every candidate pair (live detection, unmasked class-equal ground truth) of a case"""
+import functools
+
 import numpy as np
 
 THR = np.linspace(0.5, 0.95, 10).astype(np.float32)
@@ -44,12 +48,13 @@ def _valid_det(row, nc):
 def candidates(det_b, count_b, gl_b, gb_b, mk_b, nc):
     """-> [(d, [g, ...])]: per live, valid detection the unmasked, valid, class-equal ground truths"""
     out = []
+    gl_b = np.asarray(gl_b)
+    ok_g = np.asarray(mk_b, bool) & (gl_b >= 0) & (gl_b < nc) & np.isfinite(np.asarray(gb_b)).all(1)  # (once per image: the rule is per ground truth)
     for d in range(min(max(int(count_b), 0), len(det_b))):
         if not _valid_det(det_b[d], nc):
             continue
         c = int(det_b[d, 5])
-        gs = [g for g in range(len(gl_b)) if mk_b[g] and 0 <= gl_b[g] < nc and gl_b[g] == c and np.isfinite(gb_b[g]).all()]
-        out.append((d, gs))
+        out.append((d, np.flatnonzero(ok_g & (gl_b == c)).tolist()))
     return out
 
 
@@ -80,7 +85,7 @@ def match(det, count, gl, gb, mk, nc, thr=THR):
 
 def pair_ious(case, dtype):
     """every candidate pair's ProbIoU in `dtype` -> [(b, d, [g...], iou [len])]"""
-    det, count, gl, gb, mk, nc = case
+    det, count, gl, gb, mk, nc = case[:6]
     out = []
     for b in range(det.shape[0]):
         for d, gs in candidates(det[b], count[b], gl[b], gb[b], mk[b], nc):
@@ -200,3 +205,167 @@ def band(cases):
             worst = max(worst, float(np.abs(a - b).max()))
         p64s.append(p64)
     return 4.0 * worst, p64s
+
+
+# ---------------------------------------------------------------------------------------------------------------- matching cases at the edges
+def _blank(B, max_det, n_cap):
+    """every row dead: NaN boxes, classes far outside [0, nc), nothing unmasked"""
+    det = np.full((B, max_det, 7), np.nan, np.float32)
+    det[:, :, 5] = 1e9
+    gl, gb, mk = np.full((B, n_cap), -7, np.int32), np.full((B, n_cap, 5), np.nan, np.float32), np.zeros((B, n_cap), bool)
+    gl[:, 1::2] = 10 ** 6
+    return det, gl, gb, mk
+
+
+def _grid(rng, n, nc, cols):
+    """n ground truths far apart: 100 px pitch, sides 20 .. 60 px"""
+    return [(np.array([50 + 100 * (i % cols) + rng.uniform(-5, 5), 50 + 100 * (i // cols) + rng.uniform(-5, 5), rng.uniform(20, 60), rng.uniform(20, 60),
+                       rng.uniform(0, np.pi / 2)]), int(rng.randint(0, nc))) for i in range(n)]
+
+
+def _put_det(rng, det, b, rows):
+    conf = np.sort(rng.uniform(0.01, 0.99, len(rows)))[::-1]
+    for d, (box, c) in enumerate(rows):
+        det[b, d] = (box[0], box[1], box[2], box[3], conf[d], c, box[4])
+
+
+def _put_gt(gl, gb, mk, b, gs):
+    for i, (box, c) in enumerate(gs):
+        gl[b, i], gb[b, i], mk[b, i] = c, box, True
+
+
+def _on(rng, gs, n, tmax, pick=None):
+    """n detections, each a jittered copy of one of `gs` (of those listed in `pick`) with its class"""
+    pick = list(range(len(gs))) if pick is None else pick
+    return [(_jitter(rng, gs[g][0], rng.uniform(0.0, tmax)), gs[g][1]) for g in (pick[rng.randint(0, len(pick))] for _ in range(n))]
+
+
+def size_case(n_cap, max_det, thr, seed, tmax=0.67, nc=3):
+    """B = 2.  Image 0: every one of the n_cap rows an unmasked ground truth on a grid, max_det live detections (a lane of the kernel owns
+    ceil(max_det / 256) of them); image 1: 7 ground truths, max_det // 2 detections, the rest dead rows."""
+    rng = np.random.RandomState(seed)
+    det, gl, gb, mk = _blank(2, max_det, n_cap)
+    g0, g1 = _grid(rng, n_cap, nc, 32), _grid(rng, min(7, n_cap), nc, 4)
+    rows = _on(rng, g0, max_det, tmax)
+    rows[-1] = (_jitter(rng, g0[-1][0], 0.1), g0[-1][1])  # the last detection row on the last ground-truth row
+    _put_det(rng, det, 0, rows)
+    _put_det(rng, det, 1, _on(rng, g1, max_det // 2, tmax))
+    _put_gt(gl, gb, mk, 0, g0)
+    _put_gt(gl, gb, mk, 1, g1)
+    return det, np.array([max_det, max_det // 2], np.int32), gl, gb, mk, nc, np.asarray(thr, np.float32), f"size-{n_cap}x{max_det}-thr{len(thr)}"
+
+
+TIE_GT = (3, 9)              # two ground truths with identical rows and class
+TIE_DETS = (40, 90, 140, 190)  # detections placed on them
+TIE_NEXT = (20, 30)         # detections 20 and 21 identical, on ground truth 30 alone
+TIE_LANE = (5, 261, 31)      # detections 5 and 261 identical (one lane of the kernel, successive passes), on ground truth 31 alone
+
+
+def ties_case(seed):
+    """B = 1, 300 detection rows (270 live) on 40 ground truths.  The ties are exact by construction: equal rows give equal fp32 results."""
+    rng = np.random.RandomState(seed)
+    det, gl, gb, mk = _blank(1, 300, 64)
+    gs = _grid(rng, 40, 3, 8)
+    gs[TIE_GT[1]] = (gs[TIE_GT[0]][0].copy(), gs[TIE_GT[0]][1])
+    free = [g for g in range(40) if g not in (TIE_NEXT[1], TIE_LANE[2])]
+    rows = _on(rng, gs, 270, 0.67, free)
+    for k, d in enumerate(TIE_DETS):  # at least these sit on the twin ground truths
+        rows[d] = (_jitter(rng, gs[TIE_GT[k % 2]][0], 0.05 * (k + 1)), gs[TIE_GT[0]][1])
+    rows[TIE_NEXT[0]] = rows[TIE_NEXT[0] + 1] = (_jitter(rng, gs[TIE_NEXT[1]][0], 0.1), gs[TIE_NEXT[1]][1])
+    rows[TIE_LANE[0]] = rows[TIE_LANE[1]] = (_jitter(rng, gs[TIE_LANE[2]][0], 0.1), gs[TIE_LANE[2]][1])
+    _put_det(rng, det, 0, rows)
+    _put_gt(gl, gb, mk, 0, gs)
+    return det, np.array([270], np.int32), gl, gb, mk, 3, THR, "ties"
+
+
+BAD_DET = {3: "nan-x", 10: "inf-w", 17: "class--1", 24: "class-nc", 31: "class-nan", 38: "class-1e9", 45: "nan-theta"}
+BAD_GT = {20: "nan-x", 21: "label--1", 22: "label-nc"}
+
+
+def invalid_case(seed, bad=True):
+    """B = 1, 64 detection rows (50 live) on 20 ground truths of classes 0..2, nc = 4.  bad: the live rows BAD_DET and the unmasked rows BAD_GT are
+    invalid, each sitting exactly on a valid ground truth (the class -1 / nc detections on the label -1 / nc ground truths).  not bad: the same data
+    with those detections in class 3, which no ground truth has, and those ground truths masked out: every row's result must be the same."""
+    rng = np.random.RandomState(seed)
+    nc = 4
+    det, gl, gb, mk = _blank(1, 64, 32)
+    gs = _grid(rng, 20, 3, 5)
+    rows = _on(rng, gs, 50, 0.67)
+    for k, d in enumerate(BAD_DET):
+        rows[d] = (gs[k][0].copy(), gs[k][1])
+    rows[17], rows[24] = (gs[1][0].copy(), gs[1][1]), (gs[2][0].copy(), gs[2][1])
+    _put_det(rng, det, 0, rows)
+    _put_gt(gl, gb, mk, 0, gs + [(gs[0][0].copy(), gs[0][1]), (gs[1][0].copy(), -1), (gs[2][0].copy(), nc)])
+    gb[0, 20, 0] = np.nan
+    if bad:
+        det[0, 3, 0], det[0, 10, 2], det[0, 45, 6] = np.nan, np.inf, np.nan
+        det[0, 17, 5], det[0, 24, 5], det[0, 31, 5], det[0, 38, 5] = -1.0, nc, np.nan, 1e9
+    else:
+        det[0, list(BAD_DET), 5] = 3.0
+        mk[0, list(BAD_GT)] = False
+    return det, np.array([50], np.int32), gl, gb, mk, nc, THR, "invalid-rows" if bad else "invalid-rows-clean"
+
+
+def counts_case(seed, clamped=False):
+    """B = 2, every row of both images valid: count = max_det + 7 behaves as max_det, count = -4 as 0 (clamped: the same data with those counts)"""
+    rng = np.random.RandomState(seed)
+    det, gl, gb, mk = _blank(2, 40, 16)
+    for b in range(2):
+        gs = _grid(rng, 12, 3, 4)
+        _put_det(rng, det, b, _on(rng, gs, 40, 0.67))
+        _put_gt(gl, gb, mk, b, gs)
+    return det, np.array([40, 0] if clamped else [47, -4], np.int32), gl, gb, mk, 3, THR, "counts-clamped" if clamped else "counts"
+
+
+THR16 = np.linspace(0.2, 0.95, 16).astype(np.float32)
+EDGE_SEEDS = {"size0": 21, "size1": 12, "size2": 13, "size3": 51, "ties": 15, "invalid": 16, "counts": 17}  # re-seeded until test_validate_cpu's margins hold
+
+
+@functools.lru_cache(maxsize=None)
+def edge_cases():
+    """[(det, count, gt_labels, gt_bboxes, mask_gt, nc, thr, name)]: the matching cases at the kernel's launch and domain edges (the first six as
+    `match_cases()` returns them).  Built once per process; nobody writes into them."""
+    S = EDGE_SEEDS
+    return [size_case(256, 255, THR[:1], S["size0"]), size_case(257, 256, THR, S["size1"]), size_case(512, 257, THR, S["size2"]),
+            size_case(512, 1000, THR16, S["size3"], tmax=0.95), ties_case(S["ties"]), invalid_case(S["invalid"]), counts_case(S["counts"])]
+
+
+@functools.lru_cache(maxsize=None)
+def all_cases():
+    return [match_cases() + (THR, "cases"), tiny_case() + (THR, "tiny")] + edge_cases()
+
+
+@functools.lru_cache(maxsize=None)
+def all_band():
+    """`band` over the committed cases, old and new -> (band, fp64 pair list per case of all_cases())"""
+    return band(all_cases())
+
+
+def same_rows(gl_b, gb_b, g, h):
+    """two ground-truth rows bit-identical (class and box): the one condition under which two candidates may tie"""
+    return gl_b[g] == gl_b[h] and gb_b[g].tobytes() == gb_b[h].tobytes()
+
+
+def edge_claims(case, tp, bi, bg):
+    """what an edge case is there to show, asserted on a result (the reference's on the CPU, the device's on the GPU)"""
+    det, count, gl, gb, mk, nc, thr, name = case
+    full = (1 << len(thr)) - 1
+    if name.startswith("size"):
+        n_cap, max_det = gl.shape[1], det.shape[1]
+        assert mk[0].all() and count[0] == max_det and (bg[0] >= 0).all() and bg[0, max_det - 1] == n_cap - 1 and (tp[0] == full).any()
+        assert (bg[1, count[1]:] == -1).all() and not tp[1, count[1]:].any() and not bi[1, count[1]:].any() and tp.max() <= full
+    elif name == "ties":
+        assert same_rows(gl[0], gb[0], *TIE_GT) and all(bg[0, d] == TIE_GT[0] for d in TIE_DETS) and (bg[0] != TIE_GT[1]).all()
+        for d, e, g in ((TIE_NEXT[0], TIE_NEXT[0] + 1, TIE_NEXT[1]), TIE_LANE):
+            assert det[0, d, [0, 1, 2, 3, 5, 6]].tobytes() == det[0, e, [0, 1, 2, 3, 5, 6]].tobytes()
+            assert bg[0, d] == bg[0, e] == g and bi[0, d] == bi[0, e] > 0.5 and tp[0, d] & 1 and tp[0, e] == 0
+        assert TIE_LANE[0] % 256 == TIE_LANE[1] % 256
+    elif name == "invalid-rows":
+        for d in BAD_DET:
+            assert d < count[0] and (bg[0, d], bi[0, d], tp[0, d]) == (-1, 0, 0), BAD_DET[d]
+        assert mk[0, list(BAD_GT)].all() and not np.isin(bg[0], list(BAD_GT)).any()
+        live = [d for d in range(count[0]) if d not in BAD_DET]
+        assert (bg[0, live] >= 0).all() and tp[0, live].any()
+    elif name == "counts":
+        assert count.tolist() == [det.shape[1] + 7, -4] and (bg[0] >= 0).all() and tp[0].any()
+        assert (bg[1] == -1).all() and not tp[1].any() and not bi[1].any()
