@@ -20,6 +20,10 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     0 / 1 / 2, the running statistics, the parameter and gradient views, `fold()`, and `forward` / `backward` as a conv half around
     ops.bn_fwd_bf16 / ops.bn_bwd_bf16 (`act`: with or without SiLU).  A subclass is its shape check and its two conv halves.  `_bn_block` builds
     one from a parameter tuple (w, gamma, beta[, running_mean, running_var]): every composite below takes its blocks as such tuples;
+  * `_Composite`: every module that owns layers states `children()` = [(checkpoint-relative name, child)] once; `named_blocks()` (the leaves under
+    dotted names), `fold()`, `Net.pack_layers` (the dense layers with their input maps, the stride known per top-level child) and `FoldPlan` are
+    that one walk.  The leaves -- the three _BNBlocks and the two plain convs -- describe themselves: c1, c2, k, s, g, act, `fold()`, and `order`
+    on a block held in another row order than the checkpoint's (Attention's qkv);
   * `StemConvBN` / `HeadOut`: the two layer kinds outside the multiples of 8 (csrc/narrowgrad.hip) -- model.0 on the 3- or 4-channel uint8 tile under
     ConvBN's contract, and the head's plain `Conv2d` 1x1 + bias outputs (nc class logits, 1 angle logit) with fp32 logits and a fused dx + dW + db
     backward; `BoxOut` is the box branch's 64-channel output under the same contract, on the dense kernels and with bf16 logits;
@@ -32,9 +36,9 @@ kernels (loss.py, ops.conv_dgrad_bf16 / conv_wgrad_bf16, ops.rotated_tal_assign)
     fan-outs as ops.add_bf16;
   * `Bottleneck` / `C3k` / `C3k2` / `C2PSA`: the composite blocks of the trunk (models 2, 4, 6, 8, 10, 13, 16, 19, 22) assembled from the blocks above;
     `chunk` / `split` / `cat` and the gradient sums at the concat members are channel-window copies and adds (ops.chanwin_bf16, csrc/routegrad.hip);
-  * `_Chain`: layers in a row, forward in order and backward reversed -- `ClassBranchPair` and the head's three branches `_DetectBoxBranch`
-    (Detect.cv2[i]: two ConvBN, BoxOut), `_DetectClassBranch` (Detect.cv3[i]: two ClassBranchPairs, HeadOut) and `DetectAngleBranch` (OBB.cv4[i]: two
-    ConvBN, HeadOut; no loss of its own);
+  * `_Chain`: layers in a row, forward in order and backward reversed -- `ClassBranchPair` and the head's branches: `_DetectBoxBranch`
+    (Detect.cv2[i]: two ConvBN, BoxOut), `DetectAngleBranch` (OBB.cv4[i]: the same ending in HeadOut; no loss of its own) and `_DetectClassBranch`
+    (Detect.cv3[i]: two ClassBranchPairs, HeadOut);
   * `DetectBoxBranchStep` / `DetectClassBranchStep`: thin wrappers -- a box / class branch on parameter groups of its own under the DFL / BCE term
     (`_BranchStep`), with the one `step()` (`_Step`: forward_backward, DDP gradient average, optimiser step) that `DetectHead` uses too;
   * `pad_targets` / `OBBCriterion` / `DetectHead`: the criterion chain (csrc/criterion.hip) -- the host-side padding of the labels, v8OBBLoss from the
@@ -310,7 +314,10 @@ class _BNBlock:
     """What ConvBN, DWConvBN and StemConvBN share: a conv without bias -> BatchNorm2d (batch statistics, running statistics updated) [-> SiLU] over
     fp32 master parameters held in `groups` (conv weight in group 0, gamma in 1, beta in 2; running statistics are buffers of the block, not
     parameters: `groups.add_buffer`).  `forward` is the subclass's `_conv_fwd`, then ops.bn_fwd_bf16; `backward` is ops.bn_bwd_bf16, then the subclass's `_conv_bwd`,
-    which writes dW and returns dx.  A subclass checks its weight's shape, names (c1, c2, k, s, act) and supplies the two conv halves."""
+    which writes dW and returns dx.  A subclass checks its weight's shape, names (c1, c2, k, s, act) and supplies the two conv halves.  `g`: the
+    conv's groups; `order`: None, or the row permutation `fold()` applies (a block held in another channel order than the checkpoint's)."""
+
+    g, order = 1, None
 
     def __init__(self, groups, w, gamma, beta, c1, c2, k, s, act, running_mean, running_var, eps, momentum):
         self.c1, self.c2, self.k, self.s, self.act, self.eps, self.momentum = c1, c2, k, s, bool(act), eps, momentum
@@ -347,9 +354,10 @@ class _BNBlock:
         return self._conv_bwd(x, dz, **conv_args)
 
     def fold(self):
-        """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32."""
+        """-> (w, b): the eval-mode BN folded into the conv (what model.fuse() and tools/export_obbw.py expect), fp32, rows in `order`."""
         f = self.gamma / torch.sqrt(self.running_var + self.eps)
-        return self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+        w, b = self.w * f.view(-1, 1, 1, 1), self.beta - self.running_mean * f
+        return (w, b) if self.order is None else (w[self.order], b[self.order])
 
 
 class ConvBN(_BNBlock):
@@ -399,6 +407,8 @@ class DWConvBN(_BNBlock):
             raise ValueError(f"DWConvBN: w must be the depthwise 3x3 weights [C,1,3,3], got {tuple(w.shape)}")
         super().__init__(groups, w, gamma, beta, w.shape[0], w.shape[0], 3, 1, act, running_mean, running_var, eps, momentum)
 
+    g = property(lambda self: self.c1)
+
     def _conv_fwd(self, x):
         return ops.dwconv3_fwd_bf16(x, self.w)
 
@@ -413,8 +423,31 @@ def _bn_block(cls, groups, t, eps, momentum, **kw):
     return cls(groups, w, gamma, beta, running_mean=running_mean, running_var=running_var, eps=eps, momentum=momentum, **kw)
 
 
-class _Chain:
-    """Layers in a row, `self.chain`: forward through them in order, backward through them reversed."""
+class _Composite:
+    """A module that owns layers states them ONCE: `children()` -> [(checkpoint-relative name, child)] in checkpoint order, a child being a leaf
+    (a _BNBlock or a _ConvBias: a layer with parameters of its own, no children) or another _Composite.  Everything that needs "every layer
+    under its name" is this one walk."""
+
+    def named_blocks(self):
+        """[(checkpoint-relative name, leaf)]: the children flattened, names joined with "." -- registration order, but for a DetectHead on groups
+        of its own"""
+        return [nb for name, c in self.children() for nb in _flatten(name, c)]
+
+    def fold(self):
+        """-> {name: (w, b)} per leaf of named_blocks(): eval-mode BN folded into each conv, fp32, checkpoint channel order."""
+        return {name: b.fold() for name, b in self.named_blocks()}
+
+
+def _flatten(name, m):
+    """[(name, leaf)] of the subtree `m` that its parent lists as `name`"""
+    return [(f"{name}.{n}", b) for n, b in m.named_blocks()] if isinstance(m, _Composite) else [(name, m)]
+
+
+class _Chain(_Composite):
+    """Layers in a row, `self.chain`: forward through them in order, backward through them reversed; the checkpoint names them 0, 1, ..."""
+
+    def children(self):
+        return [(str(j), m) for j, m in enumerate(self.chain)]
 
     def forward(self, x):
         for m in self.chain:
@@ -452,14 +485,14 @@ def qkv_device_order(nh, kd=32, hd=64):
     return torch.tensor(perm, dtype=torch.long)
 
 
-class Attention:
+class Attention(_Composite):
     """Ultralytics `Attention(dim, num_heads, attn_ratio=0.5)` (model.10.m.i.attn; key_dim 32, head_dim 64, nh = dim / 64) in training mode:
         qkv = Conv 1x1 (dim -> 2 dim, no act);  out = softmax(scale q^T k) applied to v per head;  y = proj(out + pe(v)),
     pe = depthwise Conv 3x3 (no act), proj = Conv 1x1 (no act).  qkv / proj / pe: (w, gamma, beta[, running_mean, running_var]) of the three
     blocks in CHECKPOINT channel order, registered in `groups` in that order.  The qkv block is HELD in device order (`qkv_device_order`: its
     rows of w, gamma, beta and the running statistics are permuted once, here), so its parameters, gradients and running statistics in `groups`
-    are in device order; `fold()` hands every block back in checkpoint order.  The v slice of qkv that pe reads is a channel-window copy
-    (ops.chanwin_bf16).  bf16 [B,H,W,dim] in and out, H W <= 192."""
+    are in device order; its `order` is set, so that its `fold()` hands the rows back in checkpoint order.  The v slice of qkv that pe reads is
+    a channel-window copy (ops.chanwin_bf16).  bf16 [B,H,W,dim] in and out, H W <= 192."""
 
     def __init__(self, groups, qkv, proj, pe, nh, eps=1e-3, momentum=0.03):
         self.nh = int(nh)
@@ -470,6 +503,7 @@ class Attention:
         self.perm = qkv_device_order(self.nh).to(qkv[0].device)
         self.inv = torch.argsort(self.perm)
         self.qkv = _bn_block(ConvBN, groups, [None if t is None else t[self.perm].contiguous() for t in qkv], eps, momentum, act=False)
+        self.qkv.order = self.inv
         self.proj = _bn_block(ConvBN, groups, proj, eps, momentum, act=False)
         self.pe = _bn_block(DWConvBN, groups, pe, eps, momentum, act=False)
         self.saved = None
@@ -490,13 +524,11 @@ class Attention:
         dqkv = ops.attn_bwd_bf16(qkv, out, lse, ds, self.nh, dv_add=self.pe.backward(ds))
         return self.qkv.backward(dqkv)
 
-    def fold(self):
-        """-> {"qkv": (w, b), "proj": (w, b), "pe": (w, b)}: eval-mode BN folded into each conv, fp32, checkpoint channel order."""
-        wq, bq = self.qkv.fold()
-        return {"qkv": (wq[self.inv], bq[self.inv]), "proj": self.proj.fold(), "pe": self.pe.fold()}
+    def children(self):
+        return [("qkv", self.qkv), ("proj", self.proj), ("pe", self.pe)]
 
 
-class PSABlock:
+class PSABlock(_Composite):
     """Ultralytics `PSABlock(c, attn_ratio=0.5, num_heads=c // 64)` (model.10.m.i) in training mode:
         x = x + attn(x);  x = x + ffn1(ffn0(x)),   ffn0 = Conv 1x1 (c -> 2 c, SiLU), ffn1 = Conv 1x1 (2 c -> c, no act).
     qkv / proj / pe as for `Attention`, ffn0 / ffn1: (w, gamma, beta[, running_mean, running_var]); registered in `groups` in the order qkv,
@@ -510,9 +542,10 @@ class PSABlock:
         if (self.ffn0.k, self.ffn0.c1, self.ffn1.k, self.ffn1.c1, self.ffn1.c2) != (1, c, 1, self.ffn0.c2, c):
             raise ValueError(f"PSABlock: ffn0 and ffn1 are 1x1 convs {c} -> m -> {c}, got {tuple(ffn0[0].shape)}, {tuple(ffn1[0].shape)}")
 
-    qkv = property(lambda self: self.attn.qkv)    # the five blocks under the keys of fold()
-    proj = property(lambda self: self.attn.proj)
-    pe = property(lambda self: self.attn.pe)
+    NAMES = ("attn.qkv", "attn.proj", "attn.pe", "ffn.0", "ffn.1")  # the checkpoint's names of the constructor's five blocks, in its order
+
+    def children(self):
+        return [("attn", self.attn), ("ffn.0", self.ffn0), ("ffn.1", self.ffn1)]
 
     def forward(self, x):
         """x bf16 [B,H,W,c] -> bf16 [B,H,W,c]."""
@@ -524,12 +557,8 @@ class PSABlock:
         d1 = ops.add_bf16(dy, self.ffn0.backward(self.ffn1.backward(dy)))
         return ops.add_bf16(d1, self.attn.backward(d1))
 
-    def fold(self):
-        """-> Attention.fold() plus {"ffn0": (w, b), "ffn1": (w, b)}."""
-        return {**self.attn.fold(), "ffn0": self.ffn0.fold(), "ffn1": self.ffn1.fold()}
 
-
-class SPPF:
+class SPPF(_Composite):
     """Ultralytics `SPPF(c1, c2, k=5)` (yolo11 model 9) in training mode: cv1 = Conv 1x1 (c1 -> c1 / 2), three chained 5x5 max pools (stride 1,
     pad 2), cv2 = Conv 1x1 over cat([a1, y1, y2, y3]) (2 c1 -> c2).  cv1 / cv2: (w, gamma, beta[, running_mean, running_var]) of the two ConvBN
     blocks, registered in `groups` in that order.  `forward` / `backward` follow ConvBN's contract; the only tensor kept for the pools' backward
@@ -541,6 +570,9 @@ class SPPF:
             raise ValueError(f"SPPF: cv1 and cv2 are 1x1 convs with cv2 reading 4 x cv1's {self.cv1.c2} channels, got k = {self.cv1.k}, {self.cv2.k}, "
                              f"cv2 c1 = {self.cv2.c1}")
         self.cat = None
+
+    def children(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2)]
 
     def forward(self, x):
         """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
@@ -570,7 +602,7 @@ class UpCat:
         return ops.upcat_bwd_bf16(dout, self.ca, self.up, da=da, db=db)
 
 
-class Bottleneck:
+class Bottleneck(_Composite):
     """Ultralytics `Bottleneck(c1, c2, shortcut=True, k=(3, 3), e)` with c1 == c2 (every use in YOLO11) in training mode: out = x + cv2(cv1(x)), two
     3x3 ConvBN.  cv1 / cv2: (w, gamma, beta[, running_mean, running_var]), registered in `groups` in that order.  The residual add and the gradient
     sum at x's fan-out are ops.add_bf16 (fp32 add, one rounding).  ConvBN's contract: bf16 NHWC in and out, `forward` / `backward` / `fold`."""
@@ -582,8 +614,7 @@ class Bottleneck:
                              f"{tuple(cv2[0].shape)}")
         self.c1 = self.c2 = self.cv1.c1
 
-    def named_blocks(self):
-        """[(checkpoint-relative name, ConvBN)] in registration order"""
+    def children(self):
         return [("cv1", self.cv1), ("cv2", self.cv2)]
 
     def forward(self, x):
@@ -594,12 +625,8 @@ class Bottleneck:
         """dy bf16 like the forward's output -> dx bf16 like its input; the six parameter gradients go into the groups' gradient buffers."""
         return ops.add_bf16(dy, self.cv1.backward(self.cv2.backward(dy)))
 
-    def fold(self):
-        """-> {"cv1": (w, b), "cv2": (w, b)}: eval-mode BN folded into each conv, fp32."""
-        return {n: b.fold() for n, b in self.named_blocks()}
 
-
-class C3k:
+class C3k(_Composite):
     """Ultralytics `C3k(c1, c2, n, e=0.5, k=3)` (the members of the deeper C3k2 blocks) in training mode: cv3(cat(m(cv1(x)), cv2(x))), cv1 / cv2 =
     Conv 1x1 (c1 -> c_), m = n Bottlenecks c_ -> c_ -> c_ (e = 1.0), cv3 = Conv 1x1 (2 c_ -> c2).  cv1 / cv2 / cv3: parameter tuples as for
     Bottleneck; m: a list of (cv1, cv2) pairs.  Registered in `groups` in the order cv1, cv2, cv3, m.0.cv1, m.0.cv2, m.1.cv1, ...  The concat and
@@ -616,8 +643,8 @@ class C3k:
             raise ValueError(f"C3k: m is at least one Bottleneck on cv1's {c_} channels, got {[b.c1 for b in self.m]}")
         self.c1, self.c2, self.c_ = self.cv1.c1, self.cv3.c2, c_
 
-    def named_blocks(self):
-        return [("cv1", self.cv1), ("cv2", self.cv2), ("cv3", self.cv3)] + [(f"m.{i}.{n}", b) for i, m in enumerate(self.m) for n, b in m.named_blocks()]
+    def children(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2), ("cv3", self.cv3)] + [(f"m.{i}", m) for i, m in enumerate(self.m)]
 
     def forward(self, x):
         """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
@@ -633,12 +660,8 @@ class C3k:
             da = m.backward(da)
         return ops.add_bf16(self.cv1.backward(da), self.cv2.backward(db))
 
-    def fold(self):
-        """-> {"cv1": (w, b), "cv2": ..., "cv3": ..., "m.0.cv1": ..., "m.0.cv2": ..., ...}"""
-        return {n: b.fold() for n, b in self.named_blocks()}
 
-
-class C3k2:
+class C3k2(_Composite):
     """Ultralytics `C3k2(c1, c2, n, c3k, e)` (yolo11 models 2, 4, 6, 8, 13, 16, 19, 22) in training mode, any n >= 1:
         t = cv1(x) (2 c channels);  y0, y1 = t.chunk(2);  y_{i+2} = m_i(y_{i+1});  out = cv2(cat(y0, y1, y2, ..., y_{n+1})),
     cv1 = Conv 1x1 (c1 -> 2 c), cv2 = Conv 1x1 ((2 + n) c -> c2), m_i = Bottleneck c -> c/2 -> c (c3k False; m: a list of (cv1, cv2) pairs) or
@@ -657,8 +680,8 @@ class C3k2:
             raise ValueError(f"C3k2: every member maps c = {c} channels to c, got {[(b.c1, b.c2) for b in self.m]}")
         self.c1, self.c2, self.c = self.cv1.c1, self.cv2.c2, c
 
-    def named_blocks(self):
-        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}.{n}", b) for i, m in enumerate(self.m) for n, b in m.named_blocks()]
+    def children(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}", m) for i, m in enumerate(self.m)]
 
     def forward(self, x):
         """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]."""
@@ -684,16 +707,12 @@ class C3k2:
         ops.chanwin_bf16(g, 0, c, dst=dt, d0=c)
         return self.cv1.backward(dt)
 
-    def fold(self):
-        """-> {"cv1": (w, b), "cv2": ..., "m.0.cv1": ..., ...} (C3k members: "m.0.cv1", "m.0.cv3", "m.0.m.1.cv2", ...)"""
-        return {n: b.fold() for n, b in self.named_blocks()}
 
-
-class C2PSA:
+class C2PSA(_Composite):
     """Ultralytics `C2PSA(c1, c1, n, e=0.5)` (yolo11 model 10) in training mode: a, b = cv1(x).split((c, c));  b = m(b);  out = cv2(cat(a, b)),
     cv1 = Conv 1x1 (c1 -> 2 c), cv2 = Conv 1x1 (2 c -> c1), m = n PSABlocks on c = 64 nh channels.  cv1 / cv2: parameter tuples as for Bottleneck;
-    blocks: a list of (qkv, proj, pe, ffn0, ffn1) as `PSABlock` takes them.  Registered in `groups` in the order cv1, cv2, then the blocks.  The
-    split is two channel-window copies, the concat and its backward the upcat ops with up = 1; dt = cat(da, db') again by upcat."""
+    blocks: a list of (qkv, proj, pe, ffn0, ffn1) as `PSABlock` takes them (`PSABlock.NAMES`).  Registered in `groups` in the order cv1, cv2, then
+    the blocks.  The split is two channel-window copies, the concat and its backward the upcat ops with up = 1; dt = cat(da, db') again by upcat."""
 
     def __init__(self, groups, cv1, cv2, blocks, nh, eps=1e-3, momentum=0.03):
         self.cv1, self.cv2 = _bn_block(ConvBN, groups, cv1, eps, momentum), _bn_block(ConvBN, groups, cv2, eps, momentum)
@@ -704,10 +723,8 @@ class C2PSA:
                              f"PSABlock, got {tuple(cv1[0].shape)}, {tuple(cv2[0].shape)}, {len(self.m)} blocks")
         self.c1, self.c2, self.c = self.cv1.c1, self.cv2.c2, c
 
-    PSA_NAMES = (("attn.qkv", "qkv"), ("attn.proj", "proj"), ("attn.pe", "pe"), ("ffn.0", "ffn0"), ("ffn.1", "ffn1"))  # (checkpoint name, PSABlock attribute = fold() key)
-
-    def named_blocks(self):
-        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}.{n}", getattr(m, a)) for i, m in enumerate(self.m) for n, a in self.PSA_NAMES]
+    def children(self):
+        return [("cv1", self.cv1), ("cv2", self.cv2)] + [(f"m.{i}", m) for i, m in enumerate(self.m)]
 
     def forward(self, x):
         """x bf16 [B,H,W,c1] -> bf16 [B,H,W,c2]; H W <= 192 (the attention core)."""
@@ -723,15 +740,6 @@ class C2PSA:
         for m in reversed(self.m):
             db = m.backward(db)
         return self.cv1.backward(ops.upcat_fwd_bf16(da, db, 1))
-
-    def fold(self):
-        """-> {"cv1": (w, b), "cv2": ..., "m.0.attn.qkv": ..., "m.0.attn.proj": ..., "m.0.attn.pe": ..., "m.0.ffn.0": ..., "m.0.ffn.1": ...}, the qkv
-        block in checkpoint channel order (PSABlock.fold)."""
-        out = {"cv1": self.cv1.fold(), "cv2": self.cv2.fold()}
-        for i, m in enumerate(self.m):
-            f = m.fold()
-            out.update({f"m.{i}.{n}": f[a] for n, a in self.PSA_NAMES})
-        return out
 
 
 class StemConvBN(_BNBlock):
@@ -757,6 +765,8 @@ class StemConvBN(_BNBlock):
 class _ConvBias:
     """A plain 1x1 `nn.Conv2d` with bias at the end of a head branch: w [cout,c,1,1] in group 0 of `groups`, b [cout] in group 2."""
 
+    k, s, g, act = 1, 1, 1, False
+
     def __init__(self, groups, w, b):
         self.c2, self.c1 = w.shape[0], w.shape[1]
         self.groups = groups
@@ -767,6 +777,10 @@ class _ConvBias:
     b = property(lambda self: self.groups.param[self._ib])
     dw = property(lambda self: self.groups.grad[self._iw])
     db = property(lambda self: self.groups.grad[self._ib])
+
+    def fold(self):
+        """-> (w, b) as they are: there is no BatchNorm to fold"""
+        return self.w, self.b
 
 
 class HeadOut(_ConvBias):
@@ -796,7 +810,7 @@ class BoxOut(_ConvBias):
     with BF16 logits: forward(x bf16 [B,H,W,c]) -> bf16 [B,H,W,cout] = pack + conv + bias; backward(dy bf16) -> dx bf16 = weight gradient and bias
     gradient into the groups' gradient views, then the conv on the dgrad-form pack."""
 
-    k, s, pack = 1, 1, None  # (pack: as ConvBN's)
+    pack = None  # (as ConvBN's)
 
     def _packed(self, H, W, dgrad_form=False):
         if self.pack is not None:
@@ -815,12 +829,13 @@ class BoxOut(_ConvBias):
 
 
 class _DetectBoxBranch(_Chain):
-    """Detect.cv2[i]: ConvBN 3x3 -> ConvBN 3x3 -> BoxOut -> bf16 [B,H,W,64] DFL logits.  convs: two (w, gamma, beta) triples (gamma / beta None:
-    1 / 0), registered in `groups` before w3 [c_out,c,1,1] (group 0) and b3 [c_out] (group 2), which read through as w3 / b3 / dw3 / db3."""
+    """Detect.cv2[i]: ConvBN 3x3 -> ConvBN 3x3 -> `OUT` = BoxOut -> bf16 [B,H,W,64] DFL logits.  convs: two (w, gamma, beta) triples (gamma / beta
+    None: 1 / 0), registered in `groups` before w3 [c_out,c,1,1] (group 0) and b3 [c_out] (group 2), which read through as w3 / b3 / dw3 / db3."""
+    OUT = BoxOut
 
-    def __init__(self, groups, convs, w3, b3, eps, momentum):
+    def __init__(self, groups, convs, w3, b3, eps=1e-3, momentum=0.03):
         self.blocks = [_bn_block(ConvBN, groups, t, eps, momentum) for t in convs]
-        self.out = BoxOut(groups, w3, b3)
+        self.out = self.OUT(groups, w3, b3)
         self.chain = self.blocks + [self.out]
 
     w3 = property(lambda self: self.out.w)
@@ -840,15 +855,10 @@ class _DetectClassBranch(_Chain):
         self.chain = self.pairs + [self.out]
 
 
-class DetectAngleBranch(_Chain):
-    """Ultralytics OBB.cv4[i]: ConvBN 3x3 -> ConvBN 3x3 -> HeadOut(1), as forward(x bf16) -> fp32 angle logits [B,H,W,1] and backward(dangle fp32) ->
-    dx bf16.  There is no loss here: the angle's gradient arrives through ProbIoU on the decoded boxes.  convs: two (w, gamma, beta) triples
-    (gamma / beta None: 1 / 0), registered in `groups` before w3 [ne,c,1,1] and b3 [ne]."""
-
-    def __init__(self, groups, convs, w3, b3, eps=1e-3, momentum=0.03):
-        self.blocks = [_bn_block(ConvBN, groups, t, eps, momentum) for t in convs]
-        self.out = HeadOut(groups, w3, b3)
-        self.chain = self.blocks + [self.out]
+class DetectAngleBranch(_DetectBoxBranch):
+    """Ultralytics OBB.cv4[i]: the box branch's chain ending in HeadOut(1): forward(x bf16) -> fp32 angle logits [B,H,W,1], backward(dangle fp32) ->
+    dx bf16.  There is no loss here: the angle's gradient arrives through ProbIoU on the decoded boxes.  w3 [ne,c,1,1], b3 [ne]."""
+    OUT = HeadOut
 
 
 class _Step:
@@ -971,7 +981,7 @@ class OBBCriterion:
         return items, (d_box, d_cls, d_angle)
 
 
-class DetectHead(_Step):
+class DetectHead(_Step, _Composite):
     """The three levels of Ultralytics `Detect` / `OBB` (model.23: cv2 box, cv3 class, cv4 angle branches on P3, P4, P5) in training mode over ONE
     `ParamGroups`, trained under `OBBCriterion`.  levels: three dicts {"box": (convs, w3, b3), "cls": (pairs, w3, b3), "angle": (convs, w3, b3)} with
     convs / pairs as DetectBoxBranchStep / DetectClassBranchStep / DetectAngleBranch take them; per level the parameters are registered in the order
@@ -1005,6 +1015,14 @@ class DetectHead(_Step):
             self.groups.build()
         self.criterion = OBBCriterion(nc, gains)
         self.record_taps, self.taps = False, None
+
+    def children(self):
+        """checkpoint order, whichever order the branches registered in"""
+        return [(f"{cv}.{i}", b) for cv, fam in (("cv2", self.box), ("cv3", self.cls), ("cv4", self.angle)) for i, b in enumerate(fam)]
+
+    def child_strides(self):
+        """the input stride of every child: P3, P4, P5 per family"""
+        return [8, 16, 32] * 3
 
     def forward(self, feats):
         out = ([b.forward(x) for b, x in zip(self.box, feats)], [c.forward(x) for c, x in zip(self.cls, feats)],
@@ -1083,7 +1101,7 @@ def _state_block(params, name):
     return (params[name + ".conv.weight"],) + tuple(params.get(f"{name}.bn.{k}") for k in ("weight", "bias", "running_mean", "running_var"))
 
 
-class Trunk:
+class Trunk(_Composite):
     """Models 0-22 of yolo11-obb.yaml (backbone + FPN / PAN neck) in training mode over ONE `ParamGroups` (the caller builds it after the
     constructor).  params: a dict keyed by Ultralytics state-dict names (`model.2.m.0.cv1.conv.weight`, `...bn.weight`, `...bn.bias`,
     `...bn.running_mean`, `...bn.running_var`); scale "n" or "s".  The parameters are registered in checkpoint order: model.0, model.1,
@@ -1102,7 +1120,7 @@ class Trunk:
     concat modules under 12, 15, 18, 21 with "in" = (a, b), "din" = (da, db)) and taps["fan"][i] = (first, second, sum) per fan-out tensor."""
 
     SCALES = {"n": 16, "s": 32}  # stem width = make_divisible(64 * width, 8): the scales `train_kernel_of` and the shape catalogue cover
-    IN_LEVEL = {1: 2, 2: 4, 3: 4, 4: 8, 5: 8, 6: 16, 7: 16, 8: 32, 9: 32, 10: 32, 13: 16, 16: 8, 17: 8, 19: 16, 20: 16, 22: 32}  # input stride per module
+    IN_LEVEL = {0: 1, 1: 2, 2: 4, 3: 4, 4: 8, 5: 8, 6: 16, 7: 16, 8: 32, 9: 32, 10: 32, 13: 16, 16: 8, 17: 8, 19: 16, 20: 16, 22: 32}  # input stride per module that owns layers
     CONVS, C3K2S = (1, 3, 5, 7, 17, 20), (2, 4, 6, 8, 13, 16, 19, 22)
 
     def __init__(self, groups, params, scale="n", eps=1e-3, momentum=0.03):
@@ -1143,7 +1161,7 @@ class Trunk:
                 blocks = []
                 while f"model.10.m.{len(blocks)}.attn.qkv.conv.weight" in params:
                     q = f"model.10.m.{len(blocks)}"
-                    blocks.append(tuple(t(f"{q}.{n}") for n, _ in C2PSA.PSA_NAMES))
+                    blocks.append(tuple(t(f"{q}.{n}") for n in PSABlock.NAMES))
                 nh = params["model.10.cv1.conv.weight"].shape[0] // 128
                 self.m[10] = C2PSA(groups, t("model.10.cv1"), t("model.10.cv2"), blocks, nh, eps, momentum)
             elif i in (12, 15):
@@ -1152,40 +1170,13 @@ class Trunk:
                 self.m[i] = UpCat(1)
         self.ch = self.m[0].c1
 
-    def named_blocks(self):
-        """[(state-dict name, block)] of every Conv block (a _BNBlock) in registration = checkpoint order"""
-        out = []
-        for i in sorted(self.m):
-            m = self.m[i]
-            if isinstance(m, _BNBlock):
-                out.append((f"model.{i}", m))
-            elif isinstance(m, SPPF):
-                out += [(f"model.{i}.cv1", m.cv1), (f"model.{i}.cv2", m.cv2)]
-            elif hasattr(m, "named_blocks"):
-                out += [(f"model.{i}.{n}", b) for n, b in m.named_blocks()]
-        return out
+    def children(self):
+        """the modules that own layers under their state-dict names, checkpoint = registration order (the concat modules own none)"""
+        return [(f"model.{i}", self.m[i]) for i in sorted(self.IN_LEVEL)]
 
-    def fold(self):
-        """-> {state-dict name: (w, b)}: eval-mode BN folded into every conv, fp32, the qkv convs in checkpoint channel order."""
-        out = {}
-        for i in sorted(self.m):
-            m = self.m[i]
-            if isinstance(m, _BNBlock):
-                out[f"model.{i}"] = m.fold()
-            elif isinstance(m, SPPF):
-                out.update({f"model.{i}.cv1": m.cv1.fold(), f"model.{i}.cv2": m.cv2.fold()})
-            elif hasattr(m, "fold"):
-                out.update({f"model.{i}.{n}": wb for n, wb in m.fold().items()})
-        return out
-
-    def pack_layers(self, H, W):
-        """-> (layers, shapes) for a `PackPlan`: every dense conv with its input map at H x W tiles"""
-        layers, shapes = [], []
-        for name, b in self.named_blocks():
-            if isinstance(b, ConvBN):
-                lv = self.IN_LEVEL[int(name.split(".")[1])]
-                layers.append(b); shapes.append((H // lv, W // lv))
-        return layers, shapes
+    def child_strides(self):
+        """the input stride of every child"""
+        return [self.IN_LEVEL[i] for i in sorted(self.IN_LEVEL)]
 
     def _f(self, i, *xs):
         y = self.m[i].forward(*xs)
@@ -1236,7 +1227,7 @@ class Trunk:
             g = self._b(i, g)
 
 
-class Net(_Step):
+class Net(_Step, _Composite):
     """The whole YOLO11-OBB training iteration: `Trunk` (models 0-22) + the branches of `DetectHead` (model.23) + `OBBCriterion` over ONE
     `ParamGroups`, the parameters registered in checkpoint order (the trunk's, then model.23.cv2.0-2, cv3.0-2, cv4.0-2).  params: a dict keyed by
     Ultralytics state-dict names (`Trunk`; the head's plain convs as `model.23.cv2.0.2.weight` / `.bias`); scale "n" or "s" (anything else:
@@ -1276,28 +1267,15 @@ class Net(_Step):
 
     criterion = property(lambda self: self.head.criterion)
 
-    def named_blocks(self):
-        """[(state-dict name, layer)] in registration order: the trunk's Conv blocks, then per head branch its Conv blocks and its plain output conv"""
-        out = self.trunk.named_blocks()
-        h = self.head
-        for i in range(3):
-            out += [(f"model.23.cv2.{i}.{j}", b) for j, b in enumerate(h.box[i].chain)]
-        for i in range(3):
-            for j, p in enumerate(h.cls[i].pairs):
-                out += [(f"model.23.cv3.{i}.{j}.0", p.dw), (f"model.23.cv3.{i}.{j}.1", p.pw)]
-            out.append((f"model.23.cv3.{i}.2", h.cls[i].out))
-        for i in range(3):
-            out += [(f"model.23.cv4.{i}.{j}", b) for j, b in enumerate(h.angle[i].chain)]
-        return out
+    def children(self):
+        """the trunk's modules, then the head's branches as model.23.*: named_blocks() lists every layer under its state-dict name in registration
+        order, fold() every conv of the model (the head's plain output convs as they are)"""
+        return self.trunk.children() + [(f"model.23.{n}", b) for n, b in self.head.children()]
 
-    def fold(self):
-        """-> {state-dict name: (w, b)} of every conv of the model, fp32: eval-mode BN folded (the qkv convs in checkpoint channel order), the head's
-        plain output convs as they are."""
-        out = self.trunk.fold()
-        for name, b in self.named_blocks():
-            if name.startswith("model.23."):
-                out[name] = b.fold() if isinstance(b, _BNBlock) else (b.w, b.b)
-        return out
+    def pack_layers(self, H, W):
+        """[(layer, (h, w))] for a `PackPlan`: every leaf with `_packed` and its input map at H x W tiles -- the stride is its top-level module's"""
+        strides = self.trunk.child_strides() + self.head.child_strides()
+        return [(b, (H // lv, W // lv)) for (name, m), lv in zip(self.children(), strides) for _, b in _flatten(name, m) if hasattr(b, "_packed")]
 
     validator = None
 
@@ -1320,12 +1298,7 @@ class Net(_Step):
         if self._plan_hw != (H, W):
             if self.plan is not None:
                 self.plan.detach()
-            layers, shapes = self.trunk.pack_layers(H, W)
-            for name, b in self.named_blocks():
-                if name.startswith("model.23.") and hasattr(b, "_packed"):
-                    lv = (8, 16, 32)[int(name.split(".")[3])]
-                    layers.append(b); shapes.append((H // lv, W // lv))
-            self.plan, self._plan_hw = PackPlan(self.groups, layers, shapes), (H, W)
+            self.plan, self._plan_hw = PackPlan(self.groups, *zip(*self.pack_layers(H, W))), (H, W)
         self.plan.run()
 
     def forward_backward(self, tiles, gt_labels, gt_bboxes, mask_gt):
@@ -1477,8 +1450,8 @@ class FoldPlan:
     record names from `Net.named_blocks()` (the trunk's, then the head's, checkpoint order), c1 / c2 / k / s / g / act from the blocks -- into a
     buffer that is pinned when the net lives on a device, and builds the kernel's table (ops.fold_blob_plan).  `run(ema=None)` folds the live
     buffers, or `ema.ema` (a `ModelEMA`'s copies: no `ema.applied()` swap, nothing of the net is written), into the data section and returns the
-    whole blob as a memoryview of that buffer, valid until the next `run()`.  The arithmetic is `_BNBlock.fold()`'s in IEEE fp32; the qkv convs'
-    rows come back in checkpoint order.  On a CPU-built net the header and table are there (`blob`), `run()` raises: there is no CPU path."""
+    whole blob as a memoryview of that buffer, valid until the next `run()`.  The arithmetic is `_BNBlock.fold()`'s in IEEE fp32: a leaf without
+    BatchNorm is copied, one with `order` set (the qkv convs; the kernel knows that one permutation) comes back in checkpoint order.  On a CPU-built net the header and table are there (`blob`), `run()` raises: there is no CPU path."""
 
     def __init__(self, net):
         import numpy as np
@@ -1497,8 +1470,7 @@ class FoldPlan:
             return t.storage_offset() - flat.storage_offset()
 
         blocks = net.named_blocks()
-        qkv = {id(m.attn.qkv) for m in net.trunk.m[10].m}
-        eps = {b.eps for _, b in blocks if isinstance(b, _BNBlock)}
+        eps = {b.eps for _, b in blocks if hasattr(b, "gamma")}
         if len(eps) != 1:
             raise ValueError(f"FoldPlan: the BatchNorm blocks carry different eps {sorted(eps)}: one launch folds with one")
         self.eps = eps.pop()
@@ -1511,19 +1483,18 @@ class FoldPlan:
         for name, b in blocks:
             if len(name.encode()) > 63:
                 raise ValueError(f"FoldPlan: record name too long: {name}")
-            bn = isinstance(b, _BNBlock)
-            g = b.c1 if isinstance(b, DWConvBN) else 1
-            k, st, act = (b.k, b.s, b.act) if bn else (1, 1, False)
-            per = (b.c1 // g) * k * k
-            if tuple(b.w.shape) != (b.c2, b.c1 // g, k, k):
+            per = (b.c1 // b.g) * b.k * b.k
+            if tuple(b.w.shape) != (b.c2, b.c1 // b.g, b.k, b.k):
                 raise ValueError(f"FoldPlan: {name}: weights {tuple(b.w.shape)}")
-            table += struct.pack("<64siiiiiiQQ", name.encode(), b.c1, b.c2, k, st, g, int(act), o, o + 4 * b.c2 * per)
+            table += struct.pack("<64siiiiiiQQ", name.encode(), b.c1, b.c2, b.k, b.s, b.g, int(b.act), o, o + 4 * b.c2 * per)
             o += 4 * b.c2 * (per + 1)
-            if bn:
-                kind = _lib.FOLD_QKV if id(b) in qkv else _lib.FOLD_BN
-                recs.append((kind, off(b.w, 0), off(b.gamma, 1), off(b.beta, 2), off(b.running_mean, 3), off(b.running_var, 3), b.c2, per))
-            else:
+            if not hasattr(b, "gamma"):  # no BatchNorm: a plain conv with bias
                 recs.append((_lib.FOLD_PLAIN, off(b.w, 0), 0, off(b.b, 2), 0, 0, b.c2, per))
+                continue
+            if b.order is not None and not torch.equal(b.order.cpu(), torch.argsort(qkv_device_order(b.c2 // 128))):
+                raise ValueError(f"FoldPlan: {name}: the fold kernel knows one row order, the inverse of qkv_device_order({b.c2 // 128})")
+            kind = _lib.FOLD_BN if b.order is None else _lib.FOLD_QKV
+            recs.append((kind, off(b.w, 0), off(b.gamma, 1), off(b.beta, 2), off(b.running_mean, 3), off(b.running_var, 3), b.c2, per))
         self.nbytes = o
         dev = self.flats[0].device
         self._buf = torch.zeros(o, dtype=torch.uint8, pin_memory=dev.type == "cuda")

@@ -104,7 +104,7 @@ KINDS = {
 
 
 def layout_of(kind):
-    """-> {"items": [[group, shape]], "param_sha256": [three hex digests], "named_blocks": [names] or None}"""
+    """-> {"items": [[group, shape]], "param_sha256": [three hex digests], "named_blocks": [names], or None for a single layer: a leaf lists nothing}"""
     import oriented_object_detection_amd.train as TR
     mod, groups = KINDS[kind](TR, _Draw(kind))
     named = [n for n, _ in mod.named_blocks()] if hasattr(mod, "named_blocks") else None

@@ -34,6 +34,7 @@ import types
 import torch.nn as nn
 
 import attn_ref as AR
+import block_ref as BR
 import dw_ref as DR
 import narrow_ref as NR
 import route_ref as RR
@@ -253,9 +254,14 @@ def _attn(kind, B, H, W, C):
         assert torch.equal(att.perm.cpu(), AR.qkv_perm(nh))
         dev = {"qkv": att.qkv, "proj": att.proj, "pe": att.pe, **({} if kind == "attn" else {"ffn0": mod.ffn0, "ffn1": mod.ffn1})}
         blocks = [(t + ".", dev[t], ref[t], att.inv if t == "qkv" else None) for t in tags]
+
+        def fold():
+            f = mod.fold()  # (PSABlock: keyed by checkpoint-relative names)
+            return {t + ".": f[t if kind == "attn" else BR.PSA_NAMES[t]] for t in tags}
+
         return Built(env, "Attention" if kind == "attn" else "PSABlock", mod, blocks, lambda g: (_x(g, B, H, W, C), DR._grad_in(g, B, H, W, C)),
                      lambda inp, r: AR.run_block((kind, nh, ref, inp[0], inp[1]), r), dist=AR.block_dist,
-                     fold=lambda: {t + ".": v for t, v in mod.fold().items()})
+                     fold=fold)
     return build
 
 
