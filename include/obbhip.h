@@ -608,6 +608,30 @@ int obb_fold_blob_f32(obb_ctx *ctx, const float *w_flat, const float *g_flat, co
 int obb_val_match(obb_ctx *ctx, const float *det, const int32_t *count, const int32_t *gt_labels, const float *gt_bboxes, const uint8_t *mask_gt,
                   int32_t B, int32_t max_det, int32_t n_cap, int32_t nc, const float *thr, int32_t n_thr, uint16_t *tp, float *best_iou,
                   int32_t *best_gt, obb_stream_t s);
+/* The validation report (csrc/valreport.hip; Ultralytics 8.3.x restated from recall, parity UNPINNED).
+ * obb_val_crit_decode / obb_val_crit_items: forward-only twins of obb_crit_decode / obb_crit_loss that read obb_forward's head float [B][A][NO] of
+ * an h x w input in place (NO = 64 + nc + 1 rounded up to a multiple of 4; levels = strides 8, 16, 32; anchors in the head's own order; the
+ * padding is never read; head 16-byte aligned).  obb_val_crit_decode: the same outputs and the same arithmetic as obb_crit_decode (bit-equal on
+ * equal logits).  obb_val_crit_items: tss[0] = max(sum target_scores, 1); items[3] = (g_box L_box, g_cls L_cls, g_dfl L_dfl) as obb_crit_loss
+ * defines them, gains a HOST array of three; no gradient is written; accumulate != 0 ADDS the three items to what items holds (a whole validation
+ * pass needs no host read per batch; tss is always overwritten).  The sums run in a fixed order without floating-point atomics: two runs give the
+ * same bits.  Refused with nothing written: B < 1, nc outside [1, 64], h or w no positive multiple of 32, B A nc > 2^24, a NULL or misaligned
+ * buffer.  Enqueue only (the first call may grow the context's workspace). */
+int obb_val_crit_decode(obb_ctx *ctx, const float *head, int32_t B, int32_t h, int32_t w, int32_t nc, float *pd_scores, float *pd_bboxes,
+                        float *anc_points, float *stride, obb_stream_t s);
+int obb_val_crit_items(obb_ctx *ctx, const float *head, int32_t B, int32_t h, int32_t w, int32_t nc, const float *target_bboxes,
+                       const float *target_scores, const uint8_t *fg_mask, const float *gains, float *items, float *tss, int32_t accumulate,
+                       obb_stream_t s);
+/* obb_val_confusion: `ConfusionMatrix.process_batch` for OBB.  det, count, gt_labels, gt_bboxes, mask_gt as obb_val_match reads them.  Candidates =
+ * the detections below min(count, max_det) with conf > conf_thr; IoU = obb_val_match's ProbIoU, CLASS-AGNOSTIC.  Each candidate picks the unmasked
+ * ground truth with the largest IoU > iou_thr (ties: the lower index); of the candidates that picked one ground truth the one with the largest IoU
+ * keeps it (ties: the lower index).  matrix int32 [nc + 1][nc + 1] is ADDED to (the caller zeroes it once per pass): [pred_cls][gt_cls] per kept
+ * pair, [pred_cls][nc] per candidate left without a ground truth, [nc][gt_cls] per unmasked ground truth left without a detection.  A class outside
+ * [0, nc) or a non-finite box, in a detection or a ground truth, matches nothing, counts nowhere and forms no address.  Integer adds only: the
+ * result does not depend on scheduling.  One 256-lane workgroup per image.  Refused with nothing written: n_cap outside [1, OBB_VAL_MAX_GT],
+ * max_det < 1, nc outside [1, 32766], a NaN threshold, a NULL buffer.  Enqueues only: capturable. */
+int obb_val_confusion(obb_ctx *ctx, const float *det, const int32_t *count, const int32_t *gt_labels, const float *gt_bboxes, const uint8_t *mask_gt,
+                      int32_t B, int32_t max_det, int32_t n_cap, int32_t nc, float conf_thr, float iou_thr, int32_t *matrix, obb_stream_t s);
 /* obb_get_option: reads back what obb_set_option set ("model_slot": the active slot), so that a component that loads a model of its own -- the
  * validator's, next to whatever the application runs -- can put the context's slot and switches back as it found them.  Replaces nothing of the
  * reference: Ultralytics' validator owns a deep copy of the model instead. */

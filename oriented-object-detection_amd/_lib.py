@@ -113,6 +113,9 @@ SIGNATURES = {
     "obb_aug_labels": [_V, _V, _V, C.c_int32, C.c_int32, _V, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _V, _V, _V, _V, _V],
     "obb_fold_blob_f32": [_V, _V, _V, _V, _V, _V, C.c_int64, C.c_int32, C.c_float, _V, C.c_int64, _V],
     "obb_val_match": [_V, _V, _V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, C.c_int32, _V, _V, _V, _V],
+    "obb_val_crit_decode": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, _V, _V],
+    "obb_val_crit_items": [_V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _V, _V, _V, c_fp, _V, _V, C.c_int32, _V],
+    "obb_val_confusion": [_V, _V, _V, _V, _V, _V, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, _V, _V],
     "obb_get_option": [_V, C.c_char_p, c_lp],
 }
 _RESTYPE = {"obb_last_error": C.c_char_p}

@@ -21,8 +21,6 @@
 namespace obb {
 
 constexpr int kCritLevels = 3;
-constexpr int kCritReg = 16;
-constexpr float kCritPi = 3.14159265358979323846f;
 
 struct CritLevels {
     const void *box[kCritLevels];    // [B,H,W,64] bf16 or fp32
@@ -53,52 +51,9 @@ __device__ __forceinline__ void crit_load_side<unsigned short>(const void *base,
     for (int k = 0; k < 2; ++k) unpack8_bf16(p[k], x + 8 * k);
 }
 
-// where an (image, anchor) lives: its level, its row in the level's [B*H*W] tensors, its anchor point and stride
-struct CritAnchor {
-    int lv;
-    int64_t row;
-    float ax, ay, s;
-};
 // (the level table is read through its constant indices only: a run-time index or a reference to it would copy the kernel argument to scratch)
 #define CRIT_PICK(L, f, lv) ((lv) == 0 ? (L).f[0] : ((lv) == 1 ? (L).f[1] : (L).f[2]))
-__device__ __forceinline__ CritAnchor crit_anchor(int a0, int a1, int H0, int H1, int H2, int W0, int W1, int W2, int b, int j) {
-    CritAnchor r;
-    r.lv = j < a0 ? 0 : (j < a1 ? 1 : 2);
-    const int jj = j - (r.lv == 0 ? 0 : (r.lv == 1 ? a0 : a1));
-    const int H = r.lv == 0 ? H0 : (r.lv == 1 ? H1 : H2);
-    const int W = r.lv == 0 ? W0 : (r.lv == 1 ? W1 : W2);
-    const int y = jj / W, x = jj - y * W;
-    r.row = (int64_t)b * H * W + jj;
-    r.ax = (float)x + 0.5f; r.ay = (float)y + 0.5f;
-    r.s = r.lv == 0 ? 8.0f : (r.lv == 1 ? 16.0f : 32.0f);
-    return r;
-}
 #define CRIT_ANCHOR(L, b, j) crit_anchor((L).a0, (L).a1, (L).H[0], (L).H[1], (L).H[2], (L).W[0], (L).W[1], (L).W[2], b, j)
-
-// the decode of one anchor, as every lane of its quad holds it after the exchange
-struct CritBox {
-    float l, t, r, b, sig, th, c, s, xf, yf, x, y, w, h;
-};
-// x: this lane's side logits -> softmax pieces (e, m, se, left for the DFL term), p = e / se, E = sum_k k p_k; the quad's four E by __shfl
-__device__ __forceinline__ CritBox crit_decode_quad(const float (&x)[kCritReg], float (&e)[kCritReg], float &m, float &se, float &E, float a,
-                                                    float ax, float ay) {
-    softmax_parts<kCritReg>(x, e, m, se);
-    const float inv_se = 1.0f / se;
-    E = 0.f;
-#pragma unroll
-    for (int k = 0; k < kCritReg; ++k) E += (float)k * (e[k] * inv_se);
-    CritBox d;
-    d.l = __shfl(E, 0, 4); d.t = __shfl(E, 1, 4); d.r = __shfl(E, 2, 4); d.b = __shfl(E, 3, 4);
-    const float ea = expf(-fabsf(a));
-    d.sig = a >= 0.0f ? 1.0f / (1.0f + ea) : ea / (1.0f + ea);
-    d.th = (d.sig - 0.25f) * kCritPi;
-    d.c = cosf(d.th); d.s = sinf(d.th);
-    d.xf = (d.r - d.l) * 0.5f; d.yf = (d.b - d.t) * 0.5f;
-    d.x = ax + (d.xf * d.c - d.yf * d.s);
-    d.y = ay + (d.xf * d.s + d.yf * d.c);
-    d.w = d.l + d.r; d.h = d.t + d.b;
-    return d;
-}
 
 template <typename TB>
 __global__ __launch_bounds__(256) void k_crit_decode(CritLevels L, int B, int nc, float *__restrict__ pd_scores, float *__restrict__ pd_bboxes,

@@ -1,5 +1,5 @@
-// Per-pair / per-side bodies of the OBB loss terms, shared by the stand-alone loss kernels (loss.hip) and the fused criterion
-// (criterion.hip): the same fp32 operations in the same order in both, so the two agree bit for bit on equal inputs.
+// Per-pair / per-side bodies of the OBB loss terms, shared by the stand-alone loss kernels (loss.hip), the fused criterion (criterion.hip) and
+// the validation criterion (valreport.hip): the same fp32 operations in the same order in all, so they agree bit for bit on equal inputs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -85,6 +85,55 @@ __device__ __forceinline__ float bce_elem(float x, float t, float &sig) {
     const float ea = expf(-fabsf(x));
     sig = x >= 0.0f ? 1.0f / (1.0f + ea) : ea / (1.0f + ea);
     return fmaxf(x, 0.0f) - x * t + log1pf(ea);
+}
+
+// ---- the head's decode, shared by the training criterion (criterion.hip: per-level tensors) and the validation criterion (valreport.hip: the
+// engine's head rows): the same fp32 operations in the same order in both, so the two agree bit for bit on equal logits.
+constexpr int kCritReg = 16;
+constexpr float kCritPi = 3.14159265358979323846f;
+
+// where an (image, anchor) lives: its level, its row in the level's [B*H*W] tensors, its anchor point and stride
+struct CritAnchor {
+    int lv;
+    int64_t row;
+    float ax, ay, s;
+};
+__device__ __forceinline__ CritAnchor crit_anchor(int a0, int a1, int H0, int H1, int H2, int W0, int W1, int W2, int b, int j) {
+    CritAnchor r;
+    r.lv = j < a0 ? 0 : (j < a1 ? 1 : 2);
+    const int jj = j - (r.lv == 0 ? 0 : (r.lv == 1 ? a0 : a1));
+    const int H = r.lv == 0 ? H0 : (r.lv == 1 ? H1 : H2);
+    const int W = r.lv == 0 ? W0 : (r.lv == 1 ? W1 : W2);
+    const int y = jj / W, x = jj - y * W;
+    r.row = (int64_t)b * H * W + jj;
+    r.ax = (float)x + 0.5f; r.ay = (float)y + 0.5f;
+    r.s = r.lv == 0 ? 8.0f : (r.lv == 1 ? 16.0f : 32.0f);
+    return r;
+}
+
+// the decode of one anchor, as every lane of its quad holds it after the exchange
+struct CritBox {
+    float l, t, r, b, sig, th, c, s, xf, yf, x, y, w, h;
+};
+// x: this lane's side logits -> softmax pieces (e, m, se, left for the DFL term), p = e / se, E = sum_k k p_k; the quad's four E by __shfl
+__device__ __forceinline__ CritBox crit_decode_quad(const float (&x)[kCritReg], float (&e)[kCritReg], float &m, float &se, float &E, float a,
+                                                    float ax, float ay) {
+    softmax_parts<kCritReg>(x, e, m, se);
+    const float inv_se = 1.0f / se;
+    E = 0.f;
+#pragma unroll
+    for (int k = 0; k < kCritReg; ++k) E += (float)k * (e[k] * inv_se);
+    CritBox d;
+    d.l = __shfl(E, 0, 4); d.t = __shfl(E, 1, 4); d.r = __shfl(E, 2, 4); d.b = __shfl(E, 3, 4);
+    const float ea = expf(-fabsf(a));
+    d.sig = a >= 0.0f ? 1.0f / (1.0f + ea) : ea / (1.0f + ea);
+    d.th = (d.sig - 0.25f) * kCritPi;
+    d.c = cosf(d.th); d.s = sinf(d.th);
+    d.xf = (d.r - d.l) * 0.5f; d.yf = (d.b - d.t) * 0.5f;
+    d.x = ax + (d.xf * d.c - d.yf * d.s);
+    d.y = ay + (d.xf * d.s + d.yf * d.c);
+    d.w = d.l + d.r; d.h = d.t + d.b;
+    return d;
 }
 
 }  // namespace obb

@@ -162,6 +162,53 @@ def ap_per_class(tp, conf, pred_cls, target_cls, nc):
     return {"ap": ap, "classes": classes, "map50": map50, "map": mean, "fitness": 0.1 * map50 + 0.9 * mean}
 
 
+def smooth_box(y, f=0.1):
+    """Ultralytics' `smooth(y, f)`: a box filter of nf = round(2 f len(y)) // 2 + 1 taps (101 for 1000 points and f = 0.1) over y padded by nf // 2
+    copies of its first and of its last value -> the same length"""
+    y = np.asarray(y, np.float64)
+    nf = round(len(y) * f * 2) // 2 + 1
+    yp = np.concatenate((np.full(nf // 2, y[0]), y, np.full(nf // 2, y[-1])))
+    return np.convolve(yp, np.ones(nf) / nf, mode="valid")
+
+
+def pr_curves(tp, conf, pred_cls, target_cls, nc):
+    """The P / R / F1 curves over confidence and the operating point the trainer reports as `metrics/precision` / `metrics/recall` (the curve half
+    of Ultralytics 8.3.x `ap_per_class`, restated from recall: the package is not installed, UNPINNED like `ap_per_class` above).  Arguments as
+    `ap_per_class`; column 0 of tp (IoU 0.5) is read, the detections go through the same stable sort.  x = linspace(0, 1, 1000); per class present
+    in the targets, with conf_c / recall / precision its detections' confidences and cumulative curves: r = interp(-x, -conf_c, recall, left=0),
+    p = interp(-x, -conf_c, precision, left=1) (below the least confidence: the last value; among equal confidences numpy reads the LAST of
+    them, the state after all of the tie), f1 = 2 p r / (p + r + 1e-16).  The operating index is the argmax of the class-mean F1 smoothed by
+    `smooth_box` (101 taps).  -> {"x", "p_curve", "r_curve", "f1_curve" [classes present, 1000], "classes", "conf_best" = x[index], "p", "r", "f1"
+    [classes present] at the index, "mp", "mr" their means}.  A class with targets and no detections scores 0 on all three curves; no targets
+    at all: empty curves, every figure and conf_best 0."""
+    tp = np.asarray(tp).astype(bool)
+    if tp.ndim != 2 or tp.shape[1] < 1:
+        raise ValueError("pr_curves: tp must be [n, thresholds >= 1]")
+    conf, pred_cls, target_cls = np.asarray(conf, np.float64).reshape(-1), np.asarray(pred_cls).reshape(-1), np.asarray(target_cls).reshape(-1)
+    if len(conf) != len(tp) or len(pred_cls) != len(tp):
+        raise ValueError("pr_curves: tp, conf and pred_cls differ in length")
+    if len(target_cls) and (target_cls.min() < 0 or target_cls.max() >= nc):
+        raise ValueError(f"pr_curves: a target class outside [0, {nc})")
+    order = np.argsort(-conf, kind="stable")
+    tp0, conf, pred_cls = tp[order, 0], conf[order], pred_cls[order]
+    classes, n_gt = np.unique(target_cls.astype(np.int64), return_counts=True)
+    x = np.linspace(0.0, 1.0, 1000)
+    p_curve, r_curve = np.zeros((len(classes), x.size)), np.zeros((len(classes), x.size))
+    for ci, c in enumerate(classes):
+        sel = pred_cls == c
+        if not sel.any():
+            continue
+        tpc = tp0[sel].cumsum().astype(np.float64)
+        fpc = (~tp0[sel]).cumsum().astype(np.float64)
+        r_curve[ci] = np.interp(-x, -conf[sel], tpc / (n_gt[ci] + 1e-16), left=0.0)
+        p_curve[ci] = np.interp(-x, -conf[sel], tpc / (tpc + fpc), left=1.0)
+    f1_curve = 2 * p_curve * r_curve / (p_curve + r_curve + 1e-16)
+    i = int(np.argmax(smooth_box(f1_curve.mean(0), 0.1))) if len(classes) else 0
+    p, r, f1 = p_curve[:, i], r_curve[:, i], f1_curve[:, i]
+    return {"x": x, "p_curve": p_curve, "r_curve": r_curve, "f1_curve": f1_curve, "classes": classes, "conf_best": float(x[i]) if len(classes) else 0.0,
+            "p": p, "r": r, "f1": f1, "mp": float(p.mean()) if len(classes) else 0.0, "mr": float(r.mean()) if len(classes) else 0.0}
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Fusion-evaluation metrics beyond mAP (SURVEY.md section 8 row f2).  dets: 11-tuples (x1..y4, cls, conf, angle) in pixels;
 # gts: [{"cls": int, "pts": 8 floats}].  All geometry runs on the GPU (one matrix launch per image); the greedy matching loops are

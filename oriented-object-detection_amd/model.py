@@ -153,8 +153,9 @@ class YOLO:
         self.close()
 
     # ------------------------------------------------------------------ batched device API
-    def predict_tiles(self, tiles, conf=0.25, iou=0.7, max_det=300, zero=True):
-        """tiles uint8 [B,h,w,ch] on device, already letterboxed -> (det [B,max_det,7] (x,y,w,h,conf,cls,theta), count [B])"""
+    def predict_tiles(self, tiles, conf=0.25, iou=0.7, max_det=300, zero=True, return_head=False):
+        """tiles uint8 [B,h,w,ch] on device, already letterboxed -> (det [B,max_det,7] (x,y,w,h,conf,cls,theta), count [B]); with `return_head`
+        -> (det, count, head): the raw head rows [B,A,NO] the detections were decoded from (what ops.val_crit_* read), otherwise dropped here"""
         self._ensure_active()
         B, h, w, ch = tiles.shape
         # cmax: the largest class logit per anchor -- the dense candidate gate of the NMS kernel.  Only the fp32 plan writes it inside its
@@ -163,7 +164,8 @@ class YOLO:
         if self.precision in ("f32", "fp32"):
             cmax = torch.empty((B, ops.model_info(h, w, tiles.device)["anchors"]), dtype=torch.float32, device=tiles.device)
         head = ops.forward(tiles, cmax=cmax)
-        return ops.decode_nms(head, h, w, conf, iou, max_det, zero=zero, cmax=cmax)
+        det, count = ops.decode_nms(head, h, w, conf, iou, max_det, zero=zero, cmax=cmax)
+        return (det, count, head) if return_head else (det, count)
 
     # ------------------------------------------------------------------ Ultralytics-shaped API
     def __call__(self, source, conf=0.25, iou=0.7, max_det=300, **kwargs):

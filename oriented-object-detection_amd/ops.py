@@ -471,6 +471,25 @@ def _val_match(det: T, count: T, gt_labels: T, gt_bboxes: T, mask_gt: T, nc: int
           int(nc), _p(thr), thr.numel(), _p(tp), _p(best_iou), _p(best_gt), _stream())
 
 
+@_op("val_crit_decode", ("pd_scores", "pd_bboxes", "anc_points", "stride"))
+def _val_crit_decode(head: T, h: int, w: int, nc: int, pd_scores: T, pd_bboxes: T, anc_points: T, stride: T) -> None:
+    _call("obb_val_crit_decode", ctx(head.device), _p(head), head.shape[0], int(h), int(w), int(nc), _p(pd_scores), _p(pd_bboxes), _p(anc_points), _p(stride),
+          _stream())
+
+
+@_op("val_crit_items", ("items", "tss"))
+def _val_crit_items(head: T, h: int, w: int, nc: int, target_bboxes: T, target_scores: T, fg_mask: T, g_box: float, g_cls: float, g_dfl: float, items: T,
+                    tss: T, accumulate: bool) -> None:
+    _call("obb_val_crit_items", ctx(head.device), _p(head), head.shape[0], int(h), int(w), int(nc), _p(target_bboxes), _p(target_scores), _p(fg_mask),
+          (C.c_float * 3)(g_box, g_cls, g_dfl), _p(items), _p(tss), int(bool(accumulate)), _stream())
+
+
+@_op("val_confusion", ("matrix",))
+def _val_confusion(det: T, count: T, gt_labels: T, gt_bboxes: T, mask_gt: T, nc: int, conf_thr: float, iou_thr: float, matrix: T) -> None:
+    _call("obb_val_confusion", ctx(det.device), _p(det), _p(count), _p(gt_labels), _p(gt_bboxes), _p(mask_gt), det.shape[0], det.shape[1], gt_labels.shape[1],
+          int(nc), float(conf_thr), float(iou_thr), _p(matrix), _stream())
+
+
 @_op("debug_activation", ("out",))
 def _debug_activation(name: str, B: int, h: int, w: int, out: T) -> None:
     n = C.c_int64(0)
@@ -1591,6 +1610,86 @@ def val_match(det, count, gt_labels, gt_bboxes, mask_gt, nc, thr=None, out=None)
     if B:
         _O.val_match(d, cnt, gl, gb, mk, int(nc), thr, tp, bi, bg)
     return tp, bi, bg
+
+
+def _val_head_check(head, h, w, nc, fn):
+    """the engine's head rows of an h x w input as obb_val_crit_* read them -> (B, A); ValueError otherwise"""
+    hd = _chk(head, torch.float32, "head")
+    if not 1 <= nc <= 64:
+        raise ValueError(f"{fn}: nc = {nc}: 1..64")
+    if h < 32 or w < 32 or h % 32 or w % 32:
+        raise ValueError(f"{fn}: input {h} x {w}: h and w are positive multiples of 32")
+    A, NO = sum((h // s) * (w // s) for s in (8, 16, 32)), (64 + nc + 1 + 3) // 4 * 4
+    if hd.dim() != 3 or hd.shape[0] < 1 or tuple(hd.shape[1:]) != (A, NO):
+        raise ValueError(f"{fn}: head must be [B >= 1, {A}, {NO}] for a {h} x {w} input with nc = {nc}, got {tuple(hd.shape)}")
+    if hd.shape[0] * A * nc > 1 << 24:
+        raise ValueError(f"{fn}: B A nc = {hd.shape[0] * A * nc} exceeds 2^24 elements")
+    return hd.shape[0], A
+
+
+def val_crit_decode(head, h, w, nc, out=None):
+    """`crit_decode` on the engine's raw head rows (`forward`'s [B,A,NO] of an h x w input), read in place: -> (pd_scores [B,A,nc], pd_bboxes
+    [B,A,5], anc_points [A,2], stride [A]), the same arithmetic -- bit-equal on equal logits.  csrc/valreport.hip; one launch."""
+    B, A = _val_head_check(head, h, w, nc, "val_crit_decode")
+    d = head.device
+    if out is None:
+        out = (torch.empty((B, A, nc), dtype=torch.float32, device=d), torch.empty((B, A, 5), dtype=torch.float32, device=d),
+               torch.empty((A, 2), dtype=torch.float32, device=d), torch.empty((A,), dtype=torch.float32, device=d))
+    ps, pb, ap, st = (_chk(t, torch.float32, n) for t, n in zip(out, ("pd_scores", "pd_bboxes", "anc_points", "stride")))
+    if tuple(ps.shape) != (B, A, nc) or tuple(pb.shape) != (B, A, 5) or tuple(ap.shape) != (A, 2) or tuple(st.shape) != (A,):
+        raise ValueError("val_crit_decode: out = (pd_scores [B,A,nc], pd_bboxes [B,A,5], anc_points [A,2], stride [A])")
+    _O.val_crit_decode(head, int(h), int(w), int(nc), ps, pb, ap, st)
+    return ps, pb, ap, st
+
+
+def val_crit_items(head, h, w, nc, target_bboxes, target_scores, fg_mask, gains=(7.5, 0.5, 1.5), items=None, tss=None, accumulate=False):
+    """`crit_loss` without the gradients, on the engine's raw head rows: -> (items fp32[3] = (box, cls, dfl) times their gains, tss fp32[1]).
+    `accumulate` adds the three items to what `items` holds (a validation pass sums its batches on the device); fixed-order sums, no
+    floating-point atomics: two runs give the same bits.  Nothing is read back to the host."""
+    B, A = _val_head_check(head, h, w, nc, "val_crit_items")
+    tb = _chk(target_bboxes, torch.float32, "target_bboxes")
+    ts = _chk(target_scores, torch.float32, "target_scores")
+    fg = fg_mask.view(torch.uint8) if fg_mask.dtype == torch.bool else fg_mask
+    fg = _chk(fg, torch.uint8, "fg_mask")
+    if tuple(tb.shape) != (B, A, 5) or tuple(ts.shape) != (B, A, nc) or tuple(fg.shape) != (B, A):
+        raise ValueError(f"val_crit_items: targets {tuple(tb.shape)}, {tuple(ts.shape)}, {tuple(fg.shape)} do not match B = {B}, A = {A}, nc = {nc}")
+    if len(gains) != 3:
+        raise ValueError("val_crit_items: gains = (box, cls, dfl)")
+    if accumulate and items is None:
+        raise ValueError("val_crit_items: accumulate adds to `items`: pass the buffer")
+    items = torch.empty(3, dtype=torch.float32, device=head.device) if items is None else _chk(items, torch.float32, "items")
+    tss = torch.empty(1, dtype=torch.float32, device=head.device) if tss is None else _chk(tss, torch.float32, "tss")
+    if items.numel() != 3 or tss.numel() != 1:
+        raise ValueError("val_crit_items: items holds 3 values, tss 1")
+    _O.val_crit_items(head, int(h), int(w), int(nc), tb, ts, fg, float(gains[0]), float(gains[1]), float(gains[2]), items, tss, bool(accumulate))
+    return items, tss
+
+
+def val_confusion(det, count, gt_labels, gt_bboxes, mask_gt, nc, conf_thr=0.25, iou_thr=0.45, matrix=None):
+    """The validator's confusion matrix (csrc/valreport.hip; Ultralytics `ConfusionMatrix.process_batch` for OBB restated from recall, UNPINNED): the
+    inputs of `val_match` -> matrix int32 [nc+1, nc+1], ADDED to (`matrix` None: a zeroed one): [pred, gt] per kept pair, [pred, nc] per
+    detection above conf_thr without a ground truth, [nc, gt] per ground truth without a detection.  Class-agnostic ProbIoU > iou_thr; ties to
+    the lower index.  Integer adds only."""
+    d = _chk(det, torch.float32, "det")
+    if d.dim() != 3 or d.shape[2] != 7 or d.shape[1] < 1:
+        raise ValueError(f"val_confusion: det must be [B, max_det >= 1, 7], got {tuple(d.shape)}")
+    B = d.shape[0]
+    cnt, gl, gb = _chk(count, torch.int32, "count"), _chk(gt_labels, torch.int32, "gt_labels"), _chk(gt_bboxes, torch.float32, "gt_bboxes")
+    mk = mask_gt.view(torch.uint8) if mask_gt.dtype == torch.bool else mask_gt
+    mk = _chk(mk, torch.uint8, "mask_gt")
+    n_cap = gl.shape[1] if gl.dim() == 2 else 0
+    if cnt.shape != (B,) or gl.shape != (B, n_cap) or gb.shape != (B, n_cap, 5) or mk.shape != (B, n_cap):
+        raise ValueError("val_confusion: count [B], gt_labels [B,n_cap], gt_bboxes [B,n_cap,5], mask_gt [B,n_cap] expected")
+    if not 1 <= n_cap <= _lib.VAL_MAX_GT or not 1 <= nc <= 32766:
+        raise ValueError(f"val_confusion: n_cap = {n_cap} outside [1, {_lib.VAL_MAX_GT}] or nc = {nc} outside [1, 32766]")
+    if conf_thr != conf_thr or iou_thr != iou_thr:
+        raise ValueError("val_confusion: a NaN threshold")
+    matrix = torch.zeros((nc + 1, nc + 1), dtype=torch.int32, device=d.device) if matrix is None else _chk(matrix, torch.int32, "matrix")
+    if tuple(matrix.shape) != (nc + 1, nc + 1):
+        raise ValueError(f"val_confusion: matrix must be [{nc + 1}, {nc + 1}]")
+    if B:
+        _O.val_confusion(d, cnt, gl, gb, mk, int(nc), float(conf_thr), float(iou_thr), matrix)
+    return matrix
 
 
 def dfl_loss(pred_dist, target_ltrb, weight=None, target_scores_sum=1.0, reg_max=16):

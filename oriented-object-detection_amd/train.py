@@ -1547,9 +1547,18 @@ class Validator:
     Targets: the label kernel runs with NEUTRAL candidate thresholds (no minimum side, aspect or area ratio: the training filter of
     `AugmentConfig` is not applied), so every label of the pool counts, with two exceptions that are the trainer's own -- a label whose rectangle
     clipped to the tile has a side under 2 px is dropped (`pad_targets`' rule, inside ops.aug_labels), and a tile with more than `n_cap` labels
-    raises ValueError at the read-back rather than losing ground truth silently."""
+    raises ValueError at the read-back rather than losing ground truth silently.
+    report=True adds the rest of the trainer's per-epoch row (UNPINNED like the above).  Per batch, on the device and without a host read: the
+    training loss of the engine's own head rows -- ops.val_crit_decode -> ops.rotated_tal_assign (the net's `OBBCriterion` topk / alpha / beta) ->
+    ops.val_crit_items, ACCUMULATED into one items buffer -- and ops.val_confusion (detections above `cm_conf`, class-agnostic ProbIoU above
+    `cm_iou`) into one matrix.  Both come back with `result()`'s read-back, and `report()` then returns the six keys of `__call__` plus
+    {"box_loss", "cls_loss", "dfl_loss" (accumulated item / number of batches: the trainer's rule), "precision", "recall" (`mp` / `mr` of
+    metrics.pr_curves), "f1" (the class mean at that point), "conf_best", "curves" (pr_curves' whole dict), "confusion" int64 [nc+1, nc+1]:
+    [predicted, true], the last row / column = background}.  `__call__`'s return value and `best_fitness` / `is_best` do not change with the flag.
+    `update(..., head=None)` without head rows counts the confusion matrix and no loss batch."""
 
-    def __init__(self, net, pool, batch=16, conf=0.001, iou=0.7, max_det=300, precision="f32", ema=None, n_cap=64, swap_rb=False):
+    def __init__(self, net, pool, batch=16, conf=0.001, iou=0.7, max_det=300, precision="f32", ema=None, n_cap=64, swap_rb=False, report=False,
+                 cm_conf=0.25, cm_iou=0.45):
         from .augment import TrainBatcher
         if isinstance(pool, TrainBatcher):
             pool = (pool.tiles, pool.labels, pool.counts)
@@ -1569,6 +1578,11 @@ class Validator:
         self.bufs = self.batcher.buffers(min(self.batch, self.batcher.N))
         self.tiles = None  # the tiles of the latest batch as the engine read them
         self.best_fitness, self.is_best, self.last = None, False, None
+        self.report_on, self.cm_conf, self.cm_iou = bool(report), float(cm_conf), float(cm_iou)
+        if self.report_on:
+            self.loss_items = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self.loss_tss = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self.confusion = torch.zeros((net.nc + 1, net.nc + 1), dtype=torch.int32, device=self.device)
         self.reset()
 
     def _identity_table(self):
@@ -1582,6 +1596,10 @@ class Validator:
 
     def reset(self):
         self.stats, self._label_counts = [], []
+        self._loss_batches, self._report = 0, None
+        if self.report_on:
+            self.loss_items.zero_()
+            self.confusion.zero_()
 
     def close(self):
         """releases the validator's engine slot (weights, plans, slabs); the next call loads a model again"""
@@ -1589,11 +1607,20 @@ class Validator:
             self.model.close()
             self.model = None
 
-    def update(self, det, count, gt_labels, gt_bboxes, mask_gt):
+    def update(self, det, count, gt_labels, gt_bboxes, mask_gt, head=None):
         """det [B,max_det,7] / count [B] as `YOLO.predict_tiles` returns them, the padded targets in pixels (device) -> (tp, best_iou, best_gt) of
-        ops.val_match; the batch joins the statistics `result()` cumulates (device tensors: nothing is read back here)."""
+        ops.val_match; the batch joins the statistics `result()` cumulates (device tensors: nothing is read back here).  With report=True the
+        batch also joins the confusion matrix and, given `head` (the raw head rows of `predict_tiles(..., return_head=True)`), the loss items."""
         tp, bi, bg = ops.val_match(det, count, gt_labels, gt_bboxes, mask_gt, self.net.nc, self.thr)
         self.stats.append((tp, det[:, :, 4:6].contiguous(), count.clone(), gt_labels.clone(), mask_gt.clone()))
+        if self.report_on:
+            ops.val_confusion(det, count, gt_labels, gt_bboxes, mask_gt, self.net.nc, self.cm_conf, self.cm_iou, matrix=self.confusion)
+            if head is not None:
+                c, s = self.net.criterion, self.batcher.s
+                ps, pb, ap, _ = ops.val_crit_decode(head, s, s, self.net.nc)
+                _, tb, ts, fg, _ = ops.rotated_tal_assign(ps, pb, ap, gt_labels, gt_bboxes, mask_gt, c.topk, c.alpha, c.beta)
+                ops.val_crit_items(head, s, s, self.net.nc, tb, ts, fg, c.gains, items=self.loss_items, tss=self.loss_tss, accumulate=True)
+                self._loss_batches += 1
         return tp, bi, bg
 
     def result(self):
@@ -1614,7 +1641,22 @@ class Validator:
         else:
             tpb, conf, cls, target = np.zeros((0, nt), bool), np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.int32)
         r = metrics.ap_per_class(tpb, conf, cls, target, self.net.nc)
-        return {"map50": r["map50"], "map": r["map"], "fitness": r["fitness"], "ap": r["ap"], "n_det": int(len(conf)), "n_gt": int(len(target))}
+        out = {"map50": r["map50"], "map": r["map"], "fitness": r["fitness"], "ap": r["ap"], "n_det": int(len(conf)), "n_gt": int(len(target))}
+        if self.report_on:
+            items = self.loss_items.cpu().numpy().astype(np.float64) / max(self._loss_batches, 1)  # (with the read-back above)
+            c = metrics.pr_curves(tpb, conf, cls, target, self.net.nc)
+            self._report = dict(out, box_loss=float(items[0]), cls_loss=float(items[1]), dfl_loss=float(items[2]), precision=c["mp"], recall=c["mr"],
+                                f1=float(c["f1"].mean()) if len(c["f1"]) else 0.0, conf_best=c["conf_best"], curves=c,
+                                confusion=self.confusion.cpu().numpy().astype(np.int64))
+        return out
+
+    def report(self):
+        """the report of the statistics `result()` (or `__call__`) last cumulated; see the class docstring.  Needs report=True."""
+        if not self.report_on:
+            raise RuntimeError("Validator: built with report=False; pass report=True for the losses, curves and confusion matrix")
+        if self._report is None:
+            self.result()
+        return self._report
 
     def __call__(self):
         from .model import YOLO
@@ -1631,8 +1673,12 @@ class Validator:
                 tiles, gl, gb, mk, cnt = (t[:nb] for t in self.bufs[1:])
                 b.batch_into(self.table[b0:b0 + nb], tiles, gl, gb, mk, cnt)
                 self._label_counts.append(cnt.clone())
-                det, count = self.model.predict_tiles(tiles, self.conf, self.iou, self.max_det)
-                self.update(det, count, gl, gb, mk)
+                if self.report_on:
+                    det, count, head = self.model.predict_tiles(tiles, self.conf, self.iou, self.max_det, return_head=True)
+                    self.update(det, count, gl, gb, mk, head=head)
+                else:
+                    det, count = self.model.predict_tiles(tiles, self.conf, self.iou, self.max_det)
+                    self.update(det, count, gl, gb, mk)
                 self.tiles = tiles
             out = self.result()
         self.is_best = self.best_fitness is None or out["fitness"] >= self.best_fitness
